@@ -20,14 +20,20 @@ PLACEMENT.  The sweeps' rate depends on which physical memory backs source, dest
 library's LL scratch relative to each other (profiles/r04_placement.md).  The library places
 what it allocates (dwt_hip_alloc_batch: up to `--placements` candidates of destination + scratch, each
 timed with the first two levels of the batch's own transform, untimed for the benchmark); the bench
-allocates its shard through it, as a caller that keeps a batch resident would.  Beside `value` the line
-carries `value_first_placement`: a short run (5 steps) on PLAIN first allocations with the library's
+allocates its shard through it, as a caller that keeps a batch resident would.  With `--full`, beside `value` the
+line carries `value_first_placement`: a short run (5 steps) on PLAIN first allocations with the library's
 search off -- what a caller that ignores placement gets in this process.  `--placements 1` makes that
 the whole run.
 
-Prints ONE JSON line on rank 0.  For N > 1 the line also carries `batch_split`: the time to
+Prints ONE JSON line on rank 0.  For N > 1 with `--full` the line also carries `batch_split`: the time to
 scatter the whole batch from rank 0 and gather the coefficients back over RCCL (grouped
 point-to-point, libdwt_amd.batch) -- reported beside the transform, never inside `value`.
+
+A plain run sets up, warms up, times the steps and prints the line.  `--full` adds the side
+measurements that take runs of their own: the first-placement figure (`value_first_placement`),
+the host-pointer leg, the shard-size sweep, the single-image entry timings, the batch inverse and
+in-place legs, the CPU baseline and, for N > 1, the batch split.  `--dump-outputs DIR` writes what the timed path computed in
+its last step (rank 0's shard) as DIR/<name>.npy, see dump_outputs().
 """
 import argparse
 import json
@@ -752,6 +758,39 @@ def batch_split_times(torch, plane, src, total, n, rank, world, dev):
                     if loop else "rank 0 -> all ranks and back, grouped isend/irecv (batch_isend_irecv), root-egress bound")}
 
 
+DUMP_BUDGET_BYTES = 48 << 20  # all arrays of one --dump-outputs together (below 64 MB)
+DUMP_SAMPLE_SEED = 20240601
+
+
+def dump_outputs(torch, outdir, arrays):
+    """--dump-outputs: every tensor of `arrays` (name -> device tensor, what a caller of the timed path receives)
+    as DIR/<name>.npy, float32 (float results) or float64 (int32 results, exactly).  An array that fits its share
+    of DUMP_BUDGET_BYTES is written whole in its own shape; a larger one as DIR/<name>_sample.npy, the values at a
+    fixed sample of flat indices: np.random.default_rng(DUMP_SAMPLE_SEED).integers(0, numel, k), sorted.  Returns
+    {file name: shape}."""
+    import numpy as np
+
+    os.makedirs(outdir, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // max(1, len(arrays))
+    torch.cuda.synchronize()
+    written = {}
+    for name, t in arrays.items():
+        out_dt = np.float32 if t.dtype.is_floating_point else np.float64
+        isz = np.dtype(out_dt).itemsize
+        flat = t.reshape(-1)
+        if flat.numel() * isz <= share:
+            a = t.cpu().numpy().astype(out_dt)
+            fname = f"{name}.npy"
+        else:
+            k = share // isz
+            idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).integers(0, flat.numel(), k, dtype=np.int64))
+            a = flat[torch.from_numpy(idx).to(flat.device)].cpu().numpy().astype(out_dt)
+            fname = f"{name}_sample.npy"
+        np.save(os.path.join(outdir, fname), a)
+        written[fname] = list(a.shape)
+    return written
+
+
 def seeded_images(torch, gen, out, first):
     """image k of the batch is seeded 1234 + k (its GLOBAL index, whatever rank holds it), generated on
     the device it lives on -- so a rank's shard is the same data at every N and any image can be regenerated alone."""
@@ -944,6 +983,8 @@ def other_workload(args, dwt, torch, plane, world, rank, dev):
         step()
     barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(torch, args.dump_outputs, {"forward": bufs[1], "roundtrip": bufs[2]} if w == "config3" else {"coefficients": bufs[1]})
     my_elapsed = elapsed
     elapsed = plane.max(elapsed)
     per_rank = plane.gather_json({"rank": rank, "elapsed_ms_per_step": round(my_elapsed / args.steps * 1e3, 4),
@@ -958,7 +999,7 @@ def other_workload(args, dwt, torch, plane, world, rank, dev):
     cfg = {"workload": name, "parallelism": f"batch-sharded x{world}"}
     cfg.update(checks)
     cpu = None
-    if world == 1 and not args.no_cpu and w in ("config3", "config5"):
+    if args.full and world == 1 and not args.no_cpu and w in ("config3", "config5"):
         try:
             cpu = cpu_baseline_config3(n, J) if w == "config3" else cpu_baseline_config5(512)
         except Exception as e:  # noqa: BLE001 -- the checker is optional equipment of the bench
@@ -1081,32 +1122,35 @@ def run_rank(args):
         return round(time.perf_counter() - t0, 3)
 
     host_leg = None
-    if world == 1 and not args.no_single and not args.inplace:
+    if args.full and world == 1 and not args.no_single and not args.inplace:
         try:
             host_leg = host_pointer_leg(torch, dwt, n, J)
         except Exception as e:  # noqa: BLE001
             host_leg = {"error": f"{type(e).__name__}: {e}"}
     dwt.set_option("place_tries", 1)
-    src = seeded_images(torch, gen, torch.empty((nb, n, n), device=dev, dtype=torch.float32), lo)
-    dst = src.clone() if args.inplace else torch.empty_like(src)
-    tune_first_s = tune_shard(src, dst)  # (search off: tile heights only)
-    for _ in range(2):
-        run_once(src, dst)
-    torch.cuda.synchronize()
-    if placed:
-        t0 = time.perf_counter()
-        for _ in range(5):
+    tune_first_s = None
+    if args.full or not placed:
+        src = seeded_images(torch, gen, torch.empty((nb, n, n), device=dev, dtype=torch.float32), lo)
+        dst = src.clone() if args.inplace else torch.empty_like(src)
+        tune_first_s = tune_shard(src, dst)  # (search off: tile heights only)
+        for _ in range(2):
             run_once(src, dst)
         torch.cuda.synchronize()
-        dt = (time.perf_counter() - t0) / 5
-        first = {"gsamples_per_s_this_rank": round(nb * n * n / dt / 1e9, 2), "ms_per_step": round(dt * 1e3, 4),
-                 "level0_GBps": round(level0_rate(lambda: run_once(src, dst), 3), 1),
-                 "how": "plain first allocations of the shard and of the library's scratch, no placement search (dwt_hip_tune with "
-                        "place_tries = 1: tile heights only), 5 steps (untimed for `value`)"}
+    if placed:
+        if args.full:
+            t0 = time.perf_counter()
+            for _ in range(5):
+                run_once(src, dst)
+            torch.cuda.synchronize()
+            dt = (time.perf_counter() - t0) / 5
+            first = {"gsamples_per_s_this_rank": round(nb * n * n / dt / 1e9, 2), "ms_per_step": round(dt * 1e3, 4),
+                     "level0_GBps": round(level0_rate(lambda: run_once(src, dst), 3), 1),
+                     "how": "plain first allocations of the shard and of the library's scratch, no placement search (dwt_hip_tune with "
+                            "place_tries = 1: tile heights only), 5 steps (untimed for `value`)"}
+            src = dst = None
+            dwt.dwt_util_finish()  # drops the plainly placed scratch
+            torch.cuda.empty_cache()
         # ---- the placed shard: dwt_hip_alloc_batch (destination + scratch chosen by timing), same data ----
-        src = dst = None
-        dwt.dwt_util_finish()  # drops the plainly placed scratch
-        torch.cuda.empty_cache()
         dwt.set_option("place_tries", args.placements)
         t0 = time.perf_counter()
         try:
@@ -1155,6 +1199,8 @@ def run_rank(args):
     k_ms, k_launches = dwt.prof_read()
     dwt.prof_enable(False)
     step_ms = [marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps)]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(torch, args.dump_outputs, {"coefficients": dst})
 
     my_elapsed = elapsed
     elapsed = plane.max(elapsed)
@@ -1222,19 +1268,19 @@ def run_rank(args):
         if shared:
             out["devices_shared"] = True
         STATE["line"] = dict(out)  # from here on the watchdog has something to print
-        if world == 1 and not args.inplace and not args.no_sweep and chunk >= nb:
+        if args.full and world == 1 and not args.inplace and not args.no_sweep and chunk >= nb:
             try:
                 out["shard_sweep"], out["projected_scaling"] = shard_sweep(torch, dwt, src, dst, n, J, nb)
             except Exception as e:  # noqa: BLE001
                 out["shard_sweep"] = {"error": f"{type(e).__name__}: {e}"}
             STATE["line"] = dict(out)
-        if not args.no_single and not args.inplace:
+        if args.full and not args.no_single and not args.inplace:
             try:
                 out["single_image"] = single_image_stats(torch, dwt, src, dst, n, J)
             except Exception as e:  # noqa: BLE001
                 out["single_image"] = {"error": f"{type(e).__name__}: {e}"}
             STATE["line"] = dict(out)
-        if world == 1 and not args.no_single and not args.inplace:
+        if args.full and world == 1 and not args.no_single and not args.inplace:
             try:
                 dwt.transform2d_batch("cdf97_s", 0, src, dst, img_bytes, nb, n * 4, n, n, J)  # coefficients of the whole batch in dst again
                 out.update(extra_legs(torch, dwt, src, dst, n, J, nb))
@@ -1243,7 +1289,7 @@ def run_rank(args):
             except Exception as e:  # noqa: BLE001
                 out["extra_legs"] = {"error": f"{type(e).__name__}: {e}"}
             STATE["line"] = dict(out)
-        if world == 1 and not args.no_cpu:
+        if args.full and world == 1 and not args.no_cpu:
             try:
                 out["cpu_baseline"] = cpu_baseline(n, J)
             except Exception as e:  # the checker is optional equipment of the bench
@@ -1252,7 +1298,7 @@ def run_rank(args):
     # the side measurement comes LAST and under its own deadline: the scatter / gather of the whole
     # batch over RCCL (never inside `value`); its first execution on real ranks may be the driver's
     split_fn = None
-    if use_dist and not args.no_split and not args.inplace:
+    if args.full and use_dist and not args.no_split and not args.inplace:
         if shared:
             split_fn = lambda: {"skipped": "ranks share a device (gloo rehearsal); the RCCL batch split needs one GPU per rank"}
         elif not plane.on_device:
@@ -1335,6 +1381,11 @@ def main():
                     help="headline = BASELINE.json's metric (default); config3/4/5 = the other BASELINE configs, same JSON contract")
     ap.add_argument("--force-dist", action="store_true",
                     help="take the torch.distributed branch (gloo + RCCL group, batch split) even with one rank: the one-GPU rehearsal of the N > 1 run")
+    ap.add_argument("--full", action="store_true",
+                    help="also the side measurements: first placement, host-pointer leg, shard sweep, single-image entries, "
+                         "batch inverse / in-place legs, CPU baseline, RCCL batch split (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (rank 0)")
     ap.add_argument("--selftest-launcher", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.gpus < 1:

@@ -371,7 +371,7 @@ def test_bench_distributed_branch_with_one_rank_over_rccl():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--force-dist", "--images", "4", "--size", "2048",
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--full", "--force-dist", "--images", "4", "--size", "2048",
                           "--steps", "2", "--warmup", "1", "--placements", "1", "--no-cpu", "--no-sweep", "--no-single", "--timeout", "240",
                           "--pg-timeout", "120", "--split-timeout", "60"], env=env, capture_output=True, text=True, timeout=300)
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
