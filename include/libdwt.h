@@ -136,6 +136,25 @@ void dwt_cdf97_2f_inplace_sdl_s(void *ptr, int stride_x, int stride_y,
 	int size_o_big_x, int size_o_big_y, int size_i_big_x, int size_i_big_y,
 	int *j_max_ptr, int decompose_one, int zero_padding);
 
+/* ---- 1-D multi-level transforms, float, Mallat layout (L_J, then H_J .. H_1) --------- */
+
+/* Forward CDF 9/7 / 5/3 of one line, in place; elements stride_y bytes apart.  *j_max_ptr:
+ * requested levels in, levels done out (negative or above ceil(log2(size_o_big_x)): all).
+ * src/libdwt.h:1128, 1144. */
+void dwt_cdf97_1f_s(void *ptr, int stride_y, int size_o_big_x, int size_i_big_x, int *j_max_ptr, int zero_padding);
+void dwt_cdf53_1f_s(void *ptr, int stride_y, int size_o_big_x, int size_i_big_x, int *j_max_ptr, int zero_padding);
+
+/* Inverse of the above; j_max < 0 (or too large) undoes a full decomposition.  src/libdwt.h:1185, 1201. */
+void dwt_cdf97_1i_s(void *ptr, int stride_y, int size_o_big_x, int size_i_big_x, int j_max, int zero_padding);
+void dwt_cdf53_1i_s(void *ptr, int stride_y, int size_o_big_x, int size_i_big_x, int j_max, int zero_padding);
+
+/* Forward 1-D transform of each of the rows 0 .. size_i_big_y-1 ("series"), rows stride_x bytes
+ * apart; size_o_big_y is not used.  One batched call.  src/libdwt.h:1233, 1252. */
+void dwt_cdf97_2f1_s(void *ptr, int stride_x, int stride_y, int size_o_big_x, int size_o_big_y,
+	int size_i_big_x, int size_i_big_y, int *j_max_ptr, int zero_padding);
+void dwt_cdf53_2f1_s(void *ptr, int stride_x, int stride_y, int size_o_big_x, int size_o_big_y,
+	int size_i_big_x, int size_i_big_y, int *j_max_ptr, int zero_padding);
+
 /* ---- lifecycle and backend knobs (src/libdwt.h:1667-1745, 1974-1986) -------------- */
 void dwt_util_init(void);   /* brings the device up (the reference loads BCE firmware here) */
 void dwt_util_finish(void); /* releases device workspace */

@@ -167,6 +167,21 @@ int dwt_hip_transform2d(int wavelet, int inverse, const void *src, void *dst,
 	int stride_x, int stride_y, int size_o_big_x, int size_o_big_y,
 	int size_i_big_x, int size_i_big_y, int *j, int decompose_one, int zero_padding);
 
+/* Multi-level 1-D transform of one float line (wavelet DWT_HIP_CDF97_S or
+ * DWT_HIP_CDF53_S), Mallat layout, arguments as in libdwt's 1-D drivers
+ * (src/libdwt.h:1128-1208): elements `stride` bytes apart, `*j` in/out for forward
+ * (clamped as the reference does), in for inverse.  src == dst: in place; otherwise
+ * dst receives the transform of src's frame.  Host or device pointers (host: the call
+ * is synchronous; device: ordered on the context's stream). */
+int dwt_hip_transform1d(int wavelet, int inverse, const void *src, void *dst,
+	int stride, int size_o, int size_i, int *j, int zero_padding);
+
+/* The same on `n_lines` lines `line_stride` bytes apart, elements `elem_stride` bytes
+ * apart (one channel of interleaved data: elem_stride = channels * 4).  Dense lines of
+ * up to 8192 samples run all levels in one kernel launch. */
+int dwt_hip_transform1d_batch(int wavelet, int inverse, const void *src, void *dst,
+	size_t line_stride, int elem_stride, int n_lines, int size_o, int size_i, int *j, int zero_padding);
+
 /* Batch of independent equally sized dense images resident in HBM, `batch_stride`
  * bytes apart; one launch per level covers the whole batch. */
 int dwt_hip_transform2d_batch(int wavelet, int inverse, const void *src, void *dst,

@@ -104,6 +104,10 @@ lib.dwt_hip_get_option.restype = _I
 lib.dwt_hip_transform2d.argtypes = [_I, _I, _P, _P, _I, _I, _I, _I, _I, _I, C.POINTER(_I), _I, _I]
 lib.dwt_hip_transform2d.restype = _I
 lib.dwt_hip_transform2d_batch.argtypes = [_I, _I, _P, _P, _S, _I, _I, _I, _I, C.POINTER(_I)]
+lib.dwt_hip_transform1d.argtypes = [_I, _I, _P, _P, _I, _I, _I, C.POINTER(_I), _I]
+lib.dwt_hip_transform1d.restype = _I
+lib.dwt_hip_transform1d_batch.argtypes = [_I, _I, _P, _P, _S, _I, _I, _I, _I, C.POINTER(_I), _I]
+lib.dwt_hip_transform1d_batch.restype = _I
 lib.dwt_hip_transform2d_batch.restype = _I
 lib.dwt_hip_transform2d_interleaved.argtypes = [_I, _I, _I, _P, _P, _I, _I, _I, _I, _I, _I, C.POINTER(_I), _I]
 lib.dwt_hip_transform2d_interleaved.restype = _I
@@ -418,6 +422,63 @@ def _newapi(wavelet):
 # src/dwt-simple.c:2224 / :1615 / :3034 and :2356 / :1927 / :3166 (argument order of dwt-simple.h)
 fdwt2_cdf97_horizontal_s = fdwt2_cdf97_vertical_s = fdwt2_cdf97_diagonal_s = _newapi(CDF97_S)
 fdwt2_cdf53_horizontal_s = fdwt2_cdf53_vertical_s = fdwt2_cdf53_diagonal_s = _newapi(CDF53_S)
+
+
+# ---- the reference's 1-D entry points (float, Mallat layout) ---------------------------
+def _line(wavelet, inverse, ptr, stride, size_o, size_i, j_max, zero_padding, who):
+    j = _I(j_max)
+    p = _addr(ptr)
+    _check(lib.dwt_hip_transform1d(wavelet, int(inverse), p, p, stride, size_o, size_i, C.byref(j), zero_padding), who)
+    return j.value
+
+
+def dwt_cdf97_1f_s(ptr, stride, size_o, size_i, j_max=-1, zero_padding=0):
+    """src/libdwt.c:16025.  Returns the level count the C function stores in *j_max_ptr."""
+    return _line(CDF97_S, 0, ptr, stride, size_o, size_i, j_max, zero_padding, "dwt_cdf97_1f_s")
+
+
+def dwt_cdf53_1f_s(ptr, stride, size_o, size_i, j_max=-1, zero_padding=0):
+    """src/libdwt.c:16097"""
+    return _line(CDF53_S, 0, ptr, stride, size_o, size_i, j_max, zero_padding, "dwt_cdf53_1f_s")
+
+
+def dwt_cdf97_1i_s(ptr, stride, size_o, size_i, j_max=-1, zero_padding=0):
+    """src/libdwt.c:15766.  Returns j_max as passed (the C function takes it by value)."""
+    return _line(CDF97_S, 1, ptr, stride, size_o, size_i, j_max, zero_padding, "dwt_cdf97_1i_s")
+
+
+def dwt_cdf53_1i_s(ptr, stride, size_o, size_i, j_max=-1, zero_padding=0):
+    """src/libdwt.c:15835"""
+    return _line(CDF53_S, 1, ptr, stride, size_o, size_i, j_max, zero_padding, "dwt_cdf53_1i_s")
+
+
+def _series(wavelet, who):
+    def f(ptr, stride_x, stride_y, size_o_big_x, size_o_big_y, size_i_big_x, size_i_big_y, j_max=-1, zero_padding=0):
+        """The forward 1-D transform of rows 0 .. size_i_big_y-1 (size_o_big_y unused), as one batch.  Returns
+        *j_max_ptr as the C function leaves it (unchanged when there are no rows)."""
+        if size_i_big_y <= 0:
+            return j_max
+        j = _I(j_max)
+        p = _addr(ptr)
+        _check(lib.dwt_hip_transform1d_batch(wavelet, 0, p, p, stride_x, stride_y, size_i_big_y, size_o_big_x,
+                                             size_i_big_x, C.byref(j), zero_padding), who)
+        return j.value
+    f.__name__ = who
+    return f
+
+
+dwt_cdf97_2f1_s = _series(CDF97_S, "dwt_cdf97_2f1_s")  # src/libdwt.c:15965
+dwt_cdf53_2f1_s = _series(CDF53_S, "dwt_cdf53_2f1_s")  # src/libdwt.c:15995
+
+
+def transform1d_batch(wavelet, inverse, src, dst, line_stride, n_lines, size, j_max=-1, elem_stride=4):
+    """Dense-frame 1-D transform of `n_lines` lines of `size` float samples (`line_stride` / `elem_stride` in bytes);
+    numpy arrays, torch tensors (host or device) or raw pointers.  Returns the level count (forward: clamped)."""
+    j = _I(j_max)
+    _check(lib.dwt_hip_transform1d_batch(WAVELET_ID.get(wavelet, wavelet), int(inverse), _addr(src), _addr(dst),
+                                         line_stride, elem_stride, n_lines, size, size, C.byref(j), 0),
+           "dwt_hip_transform1d_batch")
+    return j.value
 
 
 # ---- batches resident in HBM -----------------------------------------------------------

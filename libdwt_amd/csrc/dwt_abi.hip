@@ -2,6 +2,8 @@
 // kernel timing and the 2-D transform entries (argument checks, host / device dispatch).
 #include "dwt_backend.h"
 
+#include <climits>
+
 using namespace dwtb;
 
 #pragma GCC visibility push(default)
@@ -444,6 +446,30 @@ int dwt_hip_transform2d(int wavelet, int inverse, const void *src, void *dst, in
 	if (rc)
 		return rc;
 	return download(dst, B.p);
+}
+
+// ---- 1-D (dwt_backend_1d.hip) ----
+int dwt_hip_transform1d_batch(int wavelet, int inverse, const void *src, void *dst, size_t line_stride, int elem_stride,
+	int n_lines, int size_o, int size_i, int *j, int zero_padding)
+{
+	if (check_inited())
+		return 1;
+	if (wavelet != DWT_HIP_CDF97_S && wavelet != DWT_HIP_CDF53_S)
+		return fail("1-D transforms exist for DWT_HIP_CDF97_S and DWT_HIP_CDF53_S only (wavelet %d)", wavelet);
+	if (!src || !dst || !j)
+		return fail("null pointer argument");
+	if (n_lines < 0 || size_o < 0 || size_i < 0 || size_i > size_o)
+		return fail("bad sizes: %d lines, outer %d inner %d", n_lines, size_o, size_i);
+	if (elem_stride < 4 || line_stride > (size_t)LONG_MAX / 2)
+		return fail("bad strides: line %zu bytes, element %d bytes", line_stride, elem_stride);
+	g_elems_are_32bit = true;
+	return transform1d((Wavelet)wavelet, inverse != 0, src, dst, (long)line_stride, elem_stride, n_lines, size_o, size_i, j, zero_padding);
+}
+
+int dwt_hip_transform1d(int wavelet, int inverse, const void *src, void *dst, int stride, int size_o, int size_i, int *j,
+	int zero_padding)
+{
+	return dwt_hip_transform1d_batch(wavelet, inverse, src, dst, 0, stride, 1, size_o, size_i, j, zero_padding);
 }
 
 int dwt_hip_transform2d_batch(int wavelet, int inverse, const void *src, void *dst, size_t batch_stride, int batch,

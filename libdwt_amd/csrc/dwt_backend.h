@@ -156,7 +156,11 @@ int tuned_tile_pairs(Wavelet w, const InvLevelArgs &a);
 void apply_tile_choice(int choice, SweepTuning *t, bool inverse); // ... applied to the launch's tuning
 int forward2d(Wavelet w, Img src, Img dst, const Geom &ge, int *jp, int decompose_one, int zero_padding, int batch, long src_bstride, long dst_bstride);
 int inverse2d(Wavelet w, Img src, Img dst, const Geom &ge, int j_max, int decompose_one, int zero_padding, int batch, long src_bstride, long dst_bstride);
-bool level_fused_ok(const Geom &ge, int j); // level j runs on the fused sweeps (dense frame, both sides >= 2)
+bool level_fused_ok(const Geom &ge, int j);
+// the 1-D drivers (dwt_backend_1d.hip): n_lines lines `line_stride` bytes apart, elements `elem_stride` bytes apart, host
+// or device; *jp as the reference's forward (clamped, stored) / inverse (read) takes it
+int transform1d(Wavelet w, bool inverse, const void *src, void *dst, long line_stride, long elem_stride, int n_lines,
+	int so, int si, int *jp, int zero_padding); // level j runs on the fused sweeps (dense frame, both sides >= 2)
 // host-pointer calls on large images, band by band under their own PCIe transfers (dwt_host_xfer.hip):
 // 0 done, 1 error, -1 not applicable (the caller takes the plain path)
 int host_forward_pipelined(Wavelet w, const void *src, void *dst, int stride_x, int W, int H, int *jp, int decompose_one);

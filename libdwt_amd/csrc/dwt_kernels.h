@@ -140,6 +140,14 @@ bool have_fused_inverse(Wavelet w);
 hipError_t launch_line_pass(Wavelet w, bool inverse, const void *src, void *dst, long line_stride, long elem_stride,
 	int n_lines, int N, int hoff, bool lanes_along_lines, hipStream_t s);
 
+// All levels of a 1-D transform (float 9/7 / 5/3) of `n_lines` lines of N <= N1D_MAX samples in one launch
+// (dwt_line1d.hip): line i starts at src + i*line_stride, its elements `elem_stride` bytes apart (a multiple of 4);
+// the result (L_J, then the H bands from coarse to fine, Mallat order) goes to the same place in dst, which may be src.
+// Forward: `levels` levels from the full line down; inverse: the `levels` coarsest levels back to the full line.
+constexpr int N1D_MAX = 8192; // LDS: 56 KiB per line of an inverse at this length -- two workgroups per CU
+hipError_t launch_line_levels(Wavelet w, bool inverse, const void *src, void *dst, long line_stride, long elem_stride,
+	int n_lines, int N, int levels, hipStream_t s);
+
 // z-pass knobs of the 3-D path (measured defaults; options vol_cpt / vol_tile_pairs / vol_nt)
 struct VolTuning {
 	int cpt = 8;        // columns per lane: 4 or 8 (two groups of 4, 256 columns apart; +4 % at 1024^3)
