@@ -88,15 +88,6 @@ lib.dwt_hip_placement_report.restype = _I
 lib.dwt_hip_alloc_volumes.argtypes = [_I, _I, _I, _I, C.POINTER(_P), C.POINTER(_P)]
 lib.dwt_hip_alloc_volumes.restype = _I
 lib.dwt_hip_alloc_batch_report.argtypes = [C.POINTER(_I)] * 5 + [C.POINTER(C.c_double)] * 2
-lib.dwt_hip_probe_pair_us.argtypes = [_P, _P, C.c_size_t]
-lib.dwt_hip_probe_pair_us.restype = C.c_double
-lib.dwt_hip_probe_copy_us.argtypes = [_P, _P, C.c_size_t]
-lib.dwt_hip_probe_copy_us.restype = C.c_double
-lib.dwt_hip_malloc_mapped.argtypes = [C.c_size_t, C.c_size_t, _I, C.c_size_t]
-lib.dwt_hip_malloc_mapped.restype = _P
-lib.dwt_hip_free_mapped.argtypes = [_P]
-lib.dwt_hip_malloc_spread.argtypes = [C.c_size_t, C.c_size_t]
-lib.dwt_hip_malloc_spread.restype = _P
 lib.dwt_hip_set_option.argtypes = [C.c_char_p, _I]
 lib.dwt_hip_set_option.restype = _I
 lib.dwt_hip_get_option.argtypes = [C.c_char_p]

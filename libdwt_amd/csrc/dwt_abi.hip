@@ -6,6 +6,38 @@
 
 using namespace dwtb;
 
+// One table for dwt_hip_set_option / dwt_hip_get_option: the option's name, where it lives in the calling thread's
+// context, whether measured tile heights depend on it (they are forgotten when it changes), how a value is normalised.
+namespace {
+enum OptKind { kPlain, kSweep /* tile heights were measured under it */, kBool, kNonNegative };
+struct Opt {
+	const char *name;
+	int *(*ref)(Ctx &);
+	OptKind kind;
+};
+#define DWT_OPT(name_, member_, kind_) {name_, [](Ctx &c) -> int * { return &c.member_; }, kind_}
+const Opt kOpts[] = {
+	DWT_OPT("generic", force_generic, kSweep), DWT_OPT("cpt", tune.cpt, kSweep), DWT_OPT("tile_pairs", tune.tile_pairs, kSweep),
+	DWT_OPT("waves", tune.waves, kSweep), DWT_OPT("xcd_swizzle", tune.xcd_swizzle, kSweep), DWT_OPT("ring", tune.ring, kSweep),
+	DWT_OPT("ring_inv", tune.ring_inv, kSweep), DWT_OPT("inv_ll_temporal", tune.inv_ll_temporal, kSweep), DWT_OPT("inv_pairs", tune.inv_pairs, kSweep), DWT_OPT("nt", tune.nt, kSweep), DWT_OPT("nt_auto", tune.nt_auto, kSweep),
+	DWT_OPT("fma", fma, kSweep), DWT_OPT("fused_d", fused_d, kPlain), DWT_OPT("ride_copy", ride_copy, kBool), DWT_OPT("ride_mib", ride_mib, kNonNegative), DWT_OPT("il_exact_borders", il_exact_borders, kPlain),
+	DWT_OPT("il_inplace_shell", il_inplace_shell, kPlain), DWT_OPT("host_pipeline", host_pipeline, kPlain),
+	DWT_OPT("tune_tiles", tune_tiles, kPlain), DWT_OPT("tune_in_call", tune_in_call, kBool), DWT_OPT("place_tries", place_tries, kPlain),
+	DWT_OPT("place_min_mib", place_min_mib, kNonNegative), DWT_OPT("place_max_gib", place_max_gib, kNonNegative),
+	DWT_OPT("vol_ip_waves", vol.ip_waves, kPlain), DWT_OPT("vol_tile_pairs", vol.tile_pairs, kPlain), DWT_OPT("vol_nt", vol.nt, kPlain),
+	DWT_OPT("vol_fused", vol.fused, kPlain), DWT_OPT("vol_direct", vol.direct, kPlain), DWT_OPT("vol_whole", vol.whole, kPlain),
+	DWT_OPT("vol_inplace_fused", vol.inplace_fused, kBool), DWT_OPT("vol_swizzle", vol.swizzle, kPlain), DWT_OPT("vol_rows", vol.rows, kPlain),
+};
+#undef DWT_OPT
+const Opt *find_opt(const char *name)
+{
+	for (const Opt &o : kOpts)
+		if (!strcmp(name, o.name))
+			return &o;
+	return nullptr;
+}
+} // namespace
+
 #pragma GCC visibility push(default)
 extern "C" {
 
@@ -188,38 +220,6 @@ void dwt_hip_sync(void)
 	if (g.inited)
 		hipStreamSynchronize(g.stream);
 }
-
-// One table for dwt_hip_set_option / dwt_hip_get_option: the option's name, where it lives in the calling thread's
-// context, whether measured tile heights depend on it (they are forgotten when it changes), how a value is normalised.
-namespace {
-enum OptKind { kPlain, kSweep /* tile heights were measured under it */, kBool, kNonNegative };
-struct Opt {
-	const char *name;
-	int *(*ref)(Ctx &);
-	OptKind kind;
-};
-#define DWT_OPT(name_, member_, kind_) {name_, [](Ctx &c) -> int * { return &c.member_; }, kind_}
-const Opt kOpts[] = {
-	DWT_OPT("generic", force_generic, kSweep), DWT_OPT("cpt", tune.cpt, kSweep), DWT_OPT("tile_pairs", tune.tile_pairs, kSweep),
-	DWT_OPT("waves", tune.waves, kSweep), DWT_OPT("xcd_swizzle", tune.xcd_swizzle, kSweep), DWT_OPT("ring", tune.ring, kSweep),
-	DWT_OPT("ring_inv", tune.ring_inv, kSweep), DWT_OPT("inv_ll_temporal", tune.inv_ll_temporal, kSweep), DWT_OPT("inv_pairs", tune.inv_pairs, kSweep), DWT_OPT("probe_fuse1", tune.probe_fuse1, kSweep), DWT_OPT("nt", tune.nt, kSweep), DWT_OPT("nt_auto", tune.nt_auto, kSweep),
-	DWT_OPT("fma", fma, kSweep), DWT_OPT("fused_d", fused_d, kPlain), DWT_OPT("ride_copy", ride_copy, kBool), DWT_OPT("ride_mib", ride_mib, kNonNegative), DWT_OPT("il_exact_borders", il_exact_borders, kPlain),
-	DWT_OPT("il_inplace_shell", il_inplace_shell, kPlain), DWT_OPT("host_pipeline", host_pipeline, kPlain),
-	DWT_OPT("tune_tiles", tune_tiles, kPlain), DWT_OPT("tune_in_call", tune_in_call, kBool), DWT_OPT("place_tries", place_tries, kPlain),
-	DWT_OPT("place_min_mib", place_min_mib, kNonNegative), DWT_OPT("place_max_gib", place_max_gib, kNonNegative),
-	DWT_OPT("vol_ip_waves", vol.ip_waves, kPlain), DWT_OPT("vol_tile_pairs", vol.tile_pairs, kPlain), DWT_OPT("vol_nt", vol.nt, kPlain),
-	DWT_OPT("vol_fused", vol.fused, kPlain), DWT_OPT("vol_direct", vol.direct, kPlain), DWT_OPT("vol_whole", vol.whole, kPlain),
-	DWT_OPT("vol_inplace_fused", vol.inplace_fused, kBool), DWT_OPT("vol_swizzle", vol.swizzle, kPlain), DWT_OPT("vol_rows", vol.rows, kPlain),
-};
-#undef DWT_OPT
-const Opt *find_opt(const char *name)
-{
-	for (const Opt &o : kOpts)
-		if (!strcmp(name, o.name))
-			return &o;
-	return nullptr;
-}
-} // namespace
 
 int dwt_hip_set_option(const char *name, int value)
 {

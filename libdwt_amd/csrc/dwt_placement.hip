@@ -6,18 +6,12 @@
 // class slow each other down (level 0 of 64 images: 5.2 ... 6.2 TB/s on the same virtual addresses), while
 // nothing depends on fine address bits.  The reference hands its callers a placement-aware allocator for the
 // same kind of reason (dwt_util_get_opt_stride / dwt_util_get_stride, src/libdwt.c:20641-20707: power-of-two
-// pitches alias in the CPU caches).  This file holds
-//   - the product's allocators: dwt_hip_alloc_batch / dwt_hip_alloc_volumes over arena_place -- most of the
-//     free memory mapped as ONE arena (HIP virtual-memory API, 1 GiB physical chunks), every arrangement of
-//     destination and workspace measured with the workload itself, the best kept mapped where it was measured;
-//   - the instruments the diagnosis was made with and scripts/archive/probes/r04_*.py call: dense two-stream write /
-//     copy probes (dwt_hip_probe_pair_us / _copy_us: they do NOT see the classes the sweeps see -- their DRAM
-//     pages stay open), buffers mapped from physical pieces of far-apart groups (dwt_hip_malloc_mapped) or from
-//     pieces at even distances through ALL free memory (dwt_hip_malloc_spread: the same mix of the classes for
-//     every buffer -- the same rate in every process, but the rate of the mix, 5.7 TB/s, not of the best
-//     arrangement, 6.2).
-// Buffers of every kind are freed by dwt_hip_free.  (The library's own scratch for callers who bring their
-// buffers: place_ll_scratch in dwt_backend.hip.)
+// pitches alias in the CPU caches).  This file holds the product's allocators, dwt_hip_alloc_batch /
+// dwt_hip_alloc_volumes over arena_place: most of the free memory mapped as ONE arena (HIP virtual-memory API,
+// 1 GiB physical chunks) at a fresh address range (reserve_fresh), every arrangement of destination and workspace
+// measured with the workload itself, the best kept mapped where it was measured.  Their buffers are freed by
+// dwt_hip_free (dev_free), and dwt_hip_grant_access opens them to peer devices.  (The library's own scratch for
+// callers who bring their buffers: place_ll_scratch in dwt_backend.hip.)
 #include "dwt_backend.h"
 
 #include <algorithm>
@@ -29,75 +23,16 @@
 
 namespace dwtb {
 
-// ---- the probe: two (or one) streaming write streams, the way the sweeps store ----------------
-// Every wave stores 1 KiB pieces (16 B per lane, non-temporal) alternately to a and b; consecutive
-// waves take consecutive pieces, so each stream is one dense sequential write of `bytes`.
-__global__ __launch_bounds__(256) void k_probe_streams(char *a, char *b, size_t bytes)
-{
-	typedef unsigned u4 __attribute__((ext_vector_type(4)));
-	const size_t wave = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = ((size_t)gridDim.x * blockDim.x) >> 6;
-	const unsigned lane = threadIdx.x & 63;
-	const u4 v = {lane, 1u, 2u, 3u};
-	for (size_t piece = wave; piece * 1024 < bytes; piece += nwaves) {
-		const size_t off = piece * 1024 + lane * 16;
-		__builtin_nontemporal_store(v, (u4 *)(a + off));
-		if (b)
-			__builtin_nontemporal_store(v, (u4 *)(b + off));
-	}
-}
-
-// Read stream + write stream: a dense copy a -> b, 1 KiB pieces, non-temporal both ways.
-__global__ __launch_bounds__(256) void k_probe_copy(const char *a, char *b, size_t bytes)
-{
-	typedef unsigned u4 __attribute__((ext_vector_type(4)));
-	const size_t wave = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = ((size_t)gridDim.x * blockDim.x) >> 6;
-	const unsigned lane = threadIdx.x & 63;
-	for (size_t piece = wave; piece * 1024 < bytes; piece += nwaves) {
-		const size_t off = piece * 1024 + lane * 16;
-		const u4 v = __builtin_nontemporal_load((const u4 *)(a + off));
-		__builtin_nontemporal_store(v, (u4 *)(b + off));
-	}
-}
-
-// microseconds of one probe launch (median of `reps` after one warm-up); < 0 on error
-static double probe_us(void *a, void *b, size_t bytes, int reps = 5, bool copy = false)
-{
-	hipEvent_t e0, e1;
-	if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess)
-		return -1;
-	std::vector<float> t;
-	for (int r = 0; r <= reps; r++) {
-		hipEventRecord(e0, g.stream);
-		if (copy)
-			k_probe_copy<<<1024, 256, 0, g.stream>>>((const char *)a, (char *)b, bytes);
-		else
-			k_probe_streams<<<1024, 256, 0, g.stream>>>((char *)a, (char *)b, bytes);
-		hipEventRecord(e1, g.stream);
-		if (hipEventSynchronize(e1) != hipSuccess)
-			break;
-		float ms = 0;
-		hipEventElapsedTime(&ms, e0, e1);
-		if (r)
-			t.push_back(ms * 1e3f);
-	}
-	hipEventDestroy(e0);
-	hipEventDestroy(e1);
-	if (t.empty())
-		return -1;
-	std::sort(t.begin(), t.end());
-	return t[t.size() / 2];
-}
-
-// ---- buffers mapped from physical pieces (HIP virtual-memory API) ---------------------------------
-struct VmmArena { // one address reservation shared by several buffers (dwt_hip_alloc_batch)
+// ---- buffers mapped from physical chunks of a placement arena (HIP virtual-memory API) ---------------------
+struct VmmArena { // one address reservation shared by several buffers (arena_place)
 	void *base;
 	size_t bytes;
 	int live;
 };
 struct VmmBuf {
-	size_t bytes = 0, piece = 0;
+	size_t bytes, piece;
 	std::vector<hipMemGenericAllocationHandle_t> handles;
-	VmmArena *arena = nullptr; // set: the range is part of that reservation, which goes when its last part goes
+	VmmArena *arena; // the reservation the range is part of, which goes when its last part goes
 };
 static std::map<void *, VmmBuf> g_vmm;
 static std::mutex g_vmm_mu;
@@ -156,14 +91,13 @@ static bool set_access(void *va, size_t bytes, int owner, bool peers)
 // wrong results from the second alloc / free cycle of a placed batch on; never with fresh addresses).  Keeping the ranges
 // reserved instead is no cure: the runtime then holds on to the physical memory as well.  So every reservation gets a
 // hint below everything this process has reserved before (the runtime honours hints; 47 bits of address space hold
-// thousands of arenas), and a reservation that lands on a used range nevertheless is given up for the next hint.
-// DWT_HIP_VMM_REUSE_RANGES=1: no hints (the behaviour of rounds 4-5; for the soak that shows why not).
+// thousands of arenas), and a reservation that lands on a used range nevertheless is given up for the next hint.  When
+// eight attempts found no fresh range, the reservation fails.
 static hipError_t reserve_fresh(void **out, size_t bytes)
 {
 	static std::mutex mu;
 	static std::vector<std::pair<uintptr_t, uintptr_t>> used; // [lo, hi) of every range ever reserved here
 	static uintptr_t lowest = 0;
-	static const bool reuse = getenv("DWT_HIP_VMM_REUSE_RANGES") && atoi(getenv("DWT_HIP_VMM_REUSE_RANGES")) > 0;
 	std::lock_guard<std::mutex> lk(mu);
 	const size_t gap = (size_t)1 << 30, al = (size_t)2 << 20;
 	auto overlaps = [&](uintptr_t lo, uintptr_t hi) {
@@ -175,7 +109,9 @@ static hipError_t reserve_fresh(void **out, size_t bytes)
 	hipError_t e = hipSuccess;
 	for (int attempt = 0; attempt < 8; attempt++) {
 		void *va = nullptr;
-		void *hint = (lowest && !reuse) ? (void *)((lowest - bytes - gap * (attempt + 1)) / al * al) : nullptr;
+		const size_t below = bytes + gap * (attempt + 1);
+		// (no room below the lowest range: no hint, the overlap check judges where the runtime puts it)
+		void *hint = lowest > below ? (void *)((lowest - below) / al * al) : nullptr;
 		e = hipMemAddressReserve(&va, bytes, 0, hint, 0);
 		if (e != hipSuccess) {
 			(void)hipGetLastError();
@@ -184,207 +120,41 @@ static hipError_t reserve_fresh(void **out, size_t bytes)
 			continue; // (a hint the system cannot serve: the next one, further down)
 		}
 		const uintptr_t lo = (uintptr_t)va, hi = lo + bytes;
-		if (!reuse && overlaps(lo, hi) && attempt < 7) {
+		if (!lowest || lo < lowest)
+			lowest = lo;
+		if (overlaps(lo, hi)) {
 			hipMemAddressFree(va, bytes);
-			if (!lowest || lo < lowest)
-				lowest = lo;
 			continue;
 		}
 		used.push_back({lo, hi});
-		if (!lowest || lo < lowest)
-			lowest = lo;
 		*out = va;
 		return hipSuccess;
 	}
 	return e != hipSuccess ? e : hipErrorOutOfMemory;
 }
 
-static int vmm_release(void *va, VmmBuf &b, size_t mapped_pieces)
+// A buffer back to the system; the arena's address range goes with the last of its buffers (reserve_fresh never asks
+// for these addresses again).
+static bool vmm_free(void *va)
 {
-	for (size_t i = 0; i < mapped_pieces; i++)
+	std::unique_lock<std::mutex> lk(g_vmm_mu);
+	auto it = g_vmm.find(va);
+	if (it == g_vmm.end())
+		return false;
+	VmmBuf b = std::move(it->second);
+	g_vmm.erase(it);
+	lk.unlock();
+	// hipFree waits for the device by itself; unmapping does not: work still queued on the range would fault
+	(void)hipDeviceSynchronize();
+	for (size_t i = 0; i < b.handles.size(); i++)
 		hipMemUnmap((char *)va + i * b.piece, b.piece);
 	for (auto h : b.handles)
 		hipMemRelease(h);
-	// (the range goes back to the system; reserve_fresh never asks for these addresses again)
-	if (b.arena) {
-		std::lock_guard<std::mutex> lk(g_vmm_mu);
-		if (--b.arena->live == 0) {
-			hipMemAddressFree(b.arena->base, b.arena->bytes);
-			delete b.arena;
-		}
-	} else if (va) {
-		hipMemAddressFree(va, b.bytes);
+	lk.lock();
+	if (--b.arena->live == 0) {
+		hipMemAddressFree(b.arena->base, b.arena->bytes);
+		delete b.arena;
 	}
-	return 1;
-}
-
-// `bytes` of device memory as ONE virtual range mapped from physical pieces of `piece` bytes taken in
-// `slices` groups, with `ballast` bytes of ordinary allocations made between the groups (and freed
-// before returning) so that the groups come from physical memory far apart; piece i of the range is
-// piece i / slices of group i % slices.  slices == 1: plain pieces in creation order.
-static void *vmm_alloc(size_t bytes, size_t piece, int slices, size_t ballast)
-{
-	hipMemAllocationProp prop = {};
-	prop.type = hipMemAllocationTypePinned;
-	prop.location.type = hipMemLocationTypeDevice;
-	prop.location.id = g.device;
-	size_t gran = 0;
-	if (hipMemGetAllocationGranularity(&gran, &prop, hipMemAllocationGranularityRecommended) != hipSuccess || gran == 0) {
-		fail("hipMemGetAllocationGranularity failed");
-		return nullptr;
-	}
-	piece = (piece + gran - 1) / gran * gran;
-	const size_t n = (bytes + piece - 1) / piece;
-	VmmBuf b;
-	b.piece = piece;
-	b.bytes = n * piece;
-	void *va = nullptr;
-	if (reserve_fresh(&va, b.bytes) != hipSuccess) {
-		fail("hipMemAddressReserve(%zu) failed", b.bytes);
-		return nullptr;
-	}
-	if (slices < 1)
-		slices = 1;
-	std::vector<std::vector<hipMemGenericAllocationHandle_t>> grp(slices);
-	std::vector<void *> ballasts;
-	bool ok = true;
-	for (int k = 0; k < slices && ok; k++) {
-		const size_t cnt = n / slices + ((size_t)k < n % slices ? 1 : 0);
-		for (size_t i = 0; i < cnt && ok; i++) {
-			hipMemGenericAllocationHandle_t h;
-			ok = hipMemCreate(&h, piece, &prop, 0) == hipSuccess;
-			if (ok) {
-				grp[k].push_back(h);
-				b.handles.push_back(h);
-			}
-		}
-		if (ballast && k + 1 < slices) {
-			void *p = nullptr;
-			if (hipMalloc(&p, ballast) == hipSuccess)
-				ballasts.push_back(p);
-			else
-				(void)hipGetLastError(); // not enough room left for the spacing: go on without it
-		}
-	}
-	for (void *p : ballasts)
-		hipFree(p);
-	size_t mapped = 0;
-	for (size_t i = 0; i < n && ok; i++) {
-		ok = hipMemMap((char *)va + i * piece, piece, 0, grp[i % slices][i / slices], 0) == hipSuccess;
-		if (ok)
-			mapped++;
-	}
-	if (ok)
-		ok = set_access(va, b.bytes, g.device, false);
-	if (!ok) {
-		fail("mapping %zu bytes from %zu-byte pieces failed: %s", bytes, piece, hipGetErrorString(hipGetLastError()));
-		vmm_release(va, b, mapped);
-		return nullptr;
-	}
-	std::lock_guard<std::mutex> lk(g_vmm_mu);
-	g_vmm[va] = std::move(b);
-	return va;
-}
-
-// SPREAD allocation: `bytes` mapped from pieces taken at even distances through ALL the physical memory
-// that is free right now ("comb"): between two pieces that are kept, one filler allocation of
-// (free - bytes) / pieces bytes is made and released again at the end.  Successive physical allocations
-// come from neighbouring physical memory, so the kept pieces sample every region of the card in
-// proportion -- every buffer allocated this way is the same mix of the physical classes, whatever else
-// is allocated, and any two such buffers have the same relation to each other.
-static void *spread_alloc(size_t bytes, size_t piece, size_t reserve)
-{
-	hipMemAllocationProp prop = {};
-	prop.type = hipMemAllocationTypePinned;
-	prop.location.type = hipMemLocationTypeDevice;
-	prop.location.id = g.device;
-	size_t gran = 0;
-	if (hipMemGetAllocationGranularity(&gran, &prop, hipMemAllocationGranularityRecommended) != hipSuccess || gran == 0) {
-		fail("hipMemGetAllocationGranularity failed");
-		return nullptr;
-	}
-	piece = (piece + gran - 1) / gran * gran;
-	const size_t n = (bytes + piece - 1) / piece;
-	size_t free_b = 0, total_b = 0;
-	if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) {
-		fail("hipMemGetInfo failed");
-		return nullptr;
-	}
-	VmmBuf b;
-	b.piece = piece;
-	b.bytes = n * piece;
-	if (free_b < b.bytes + reserve / 4) {
-		fail("spread allocation of %zu bytes: only %zu bytes free", bytes, free_b);
-		return nullptr;
-	}
-	const size_t spare = free_b > b.bytes + reserve ? free_b - b.bytes - reserve : 0;
-	const size_t filler = spare / n / gran * gran;
-	void *va = nullptr;
-	if (reserve_fresh(&va, b.bytes) != hipSuccess) {
-		fail("hipMemAddressReserve(%zu) failed", b.bytes);
-		return nullptr;
-	}
-	std::vector<hipMemGenericAllocationHandle_t> fillers;
-	bool ok = true, fill = filler > 0;
-	for (size_t i = 0; i < n && ok; i++) {
-		hipMemGenericAllocationHandle_t h;
-		ok = hipMemCreate(&h, piece, &prop, 0) == hipSuccess;
-		if (!ok && !fillers.empty()) {
-			// the fillers ate what was left (another process allocated meanwhile): give them back, go on plainly
-			(void)hipGetLastError();
-			for (auto f : fillers)
-				hipMemRelease(f);
-			fillers.clear();
-			fill = false;
-			ok = hipMemCreate(&h, piece, &prop, 0) == hipSuccess;
-		}
-		if (!ok)
-			break;
-		b.handles.push_back(h);
-		if (fill && i + 1 < n) {
-			hipMemGenericAllocationHandle_t f;
-			if (hipMemCreate(&f, filler, &prop, 0) == hipSuccess)
-				fillers.push_back(f);
-			else {
-				(void)hipGetLastError();
-				fill = false;
-			}
-		}
-	}
-	for (auto f : fillers)
-		hipMemRelease(f);
-	size_t mapped = 0;
-	for (size_t i = 0; i < n && ok; i++) {
-		ok = hipMemMap((char *)va + i * piece, piece, 0, b.handles[i], 0) == hipSuccess;
-		if (ok)
-			mapped++;
-	}
-	if (ok)
-		ok = set_access(va, b.bytes, g.device, false);
-	if (!ok) {
-		fail("spread allocation of %zu bytes from %zu-byte pieces failed: %s", bytes, piece, hipGetErrorString(hipGetLastError()));
-		vmm_release(va, b, mapped);
-		return nullptr;
-	}
-	std::lock_guard<std::mutex> lk(g_vmm_mu);
-	g_vmm[va] = std::move(b);
-	return va;
-}
-
-static bool vmm_free(void *va)
-{
-	VmmBuf b;
-	{
-		std::lock_guard<std::mutex> lk(g_vmm_mu);
-		auto it = g_vmm.find(va);
-		if (it == g_vmm.end())
-			return false;
-		b = std::move(it->second);
-		g_vmm.erase(it);
-	}
-	// hipFree waits for the device by itself; unmapping does not: work still queued on the range would fault
-	(void)hipDeviceSynchronize();
-	vmm_release(va, b, b.handles.size());
 	return true;
 }
 
@@ -489,9 +259,9 @@ static int arena_place(const ArenaJob &job, void **out)
 		return -1;
 	}
 	char *arena = nullptr;
-	if (reserve_fresh((void **)&arena, n_chunks * C) != hipSuccess) {
+	if (hipError_t e = reserve_fresh((void **)&arena, n_chunks * C)) {
 		release_chunks();
-		return fail("hipMemAddressReserve(%zu) failed", n_chunks * C);
+		return fail("no fresh address range of %zu bytes could be reserved for the placement arena: %s", n_chunks * C, hipGetErrorString(e));
 	}
 	size_t mapped = 0;
 	bool ok = true;
@@ -604,17 +374,14 @@ static int arena_place(const ArenaJob &job, void **out)
 	std::vector<char> used(n_chunks, 0);
 	VmmArena *ar = new VmmArena{arena, n_chunks * C, (int)keep.size()};
 	for (size_t k = 0; k < keep.size(); k++) {
-		VmmBuf b;
-		b.piece = C;
-		b.bytes = keep[k].count * C;
-		b.arena = ar;
+		VmmBuf b{keep[k].count * C, C, {}, ar};
 		for (size_t i = 0; i < keep[k].count; i++) {
 			b.handles.push_back(chunk[keep[k].first + i]);
 			used[keep[k].first + i] = 1;
 		}
 		out[k] = arena + keep[k].first * C;
 		std::lock_guard<std::mutex> lk(g_vmm_mu);
-		g_vmm[out[k]] = std::move(b);
+		g_vmm.emplace(out[k], std::move(b));
 	}
 	for (size_t i = 0; i < n_chunks; i++)
 		if (!used[i]) {
@@ -821,37 +588,6 @@ using namespace dwtb;
 #pragma GCC visibility push(default)
 extern "C" {
 
-// Time of the two-stream probe on device buffers a and b (`bytes` each; b may be NULL: one stream),
-// in microseconds; negative on error.  Diagnostic entry (scripts/archive/probes/r04_*).
-double dwt_hip_probe_pair_us(void *a, void *b, size_t bytes)
-{
-	if (check_inited())
-		return -1;
-	return probe_us(a, b, bytes);
-}
-
-double dwt_hip_probe_copy_us(const void *a, void *b, size_t bytes)
-{
-	if (check_inited())
-		return -1;
-	return probe_us((void *)a, b, bytes, 5, true);
-}
-
-// Experimental: see vmm_alloc.  Freed with dwt_hip_free_mapped.
-void *dwt_hip_malloc_mapped(size_t bytes, size_t piece_bytes, int slices, size_t ballast_bytes)
-{
-	if (check_inited())
-		return nullptr;
-	return vmm_alloc(bytes, piece_bytes, slices, ballast_bytes);
-}
-
-void *dwt_hip_malloc_spread(size_t bytes, size_t piece_bytes)
-{
-	if (check_inited())
-		return nullptr;
-	return spread_alloc(bytes, piece_bytes ? piece_bytes : (size_t)2 << 20, (size_t)1 << 30);
-}
-
 // Source and destination of a resident batch, allocated WITH their placement -- the analogue of the
 // reference's dwt_util_get_opt_stride / dwt_util_get_stride for its callers (src/libdwt.c:20641-20707).  Dense
 // pitch (size_x elements), images size_x * size_y elements apart; the LL scratch stays with the calling
@@ -928,7 +664,7 @@ void dwt_hip_alloc_batch_report(int *chunks, int *dst_tried, int *ll_tried, int 
 const char *dwt_hip_alloc_batch_note(void) { return g_arena_note; }
 
 // Makes a device buffer reachable from other devices of this process (peer copies): buffers of dwt_hip_alloc_batch /
-// _volumes / _malloc_mapped get the access on their mapping (they are created with access for their owner alone;
+// _volumes get the access on their mapping (they are created with access for their owner alone;
 // dwt_hip_transform2d_batch_sharded grants its slots' devices by itself), plain allocations through
 // hipDeviceEnablePeerAccess from each of the devices.  `ptr` may point anywhere into the buffer.  0 = every device
 // named can reach it.
@@ -976,12 +712,6 @@ int dwt_hip_grant_access(void *ptr, const int *devices, int n_devices)
 	if (bad)
 		return fail("peer access to device %d could not be enabled from %d device(s)", owner, bad);
 	return 0;
-}
-
-void dwt_hip_free_mapped(void *p)
-{
-	if (p)
-		vmm_free(p);
 }
 
 } // extern "C"

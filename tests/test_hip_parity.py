@@ -1190,25 +1190,6 @@ def test_measured_tile_heights_do_not_change_the_bits(dwt, oracle):
         L.dwt_hip_free(dst)
 
 
-def test_mapped_buffers_are_ordinary_device_memory(dwt, oracle):
-    """The diagnosis instruments (dwt_hip_malloc_mapped / _spread: buffers mapped from physical pieces
-    through HIP's virtual-memory API) hand out memory every entry accepts and dwt_hip_free releases."""
-    L = dwt.lib
-    h, w = 300, 700
-    img = np.random.default_rng(5).random((h, w), dtype=np.float32)
-    want = img.copy()
-    jw = oracle.fwd("cdf97_2f_s", want, 3)
-    for p in (L.dwt_hip_malloc_mapped(img.nbytes, 2 << 20, 2, 0), L.dwt_hip_malloc_spread(img.nbytes, 2 << 20)):
-        assert p, dwt.last_error()
-        assert L.dwt_hip_is_device_pointer(p)
-        assert L.dwt_hip_memcpy_h2d(p, img.ctypes.data, img.nbytes) == 0
-        assert dwt.dwt_cdf97_2f_s(p, w * 4, 4, w, h, w, h, 3) == jw
-        got = np.empty_like(img)
-        assert L.dwt_hip_memcpy_d2h(got.ctypes.data, p, got.nbytes) == 0
-        assert np.array_equal(bits(got), bits(want))
-        L.dwt_hip_free(p)
-
-
 def test_randomised_soak():
     """scripts/stress.py for 20 s: random shapes, levels, wavelets, entries and layouts; the fused
     kernels against the exact line-pass / two-pass kernels bit for bit, plus round trips."""

@@ -4,6 +4,7 @@ compute entry is called here (there is no GPU in the build container)."""
 import ctypes as C
 import os
 import re
+import shutil
 import subprocess
 
 import numpy as np
@@ -48,6 +49,22 @@ def test_exports_every_declared_symbol(dwt, header):
             assert n in names
     missing = [n for n in names if not hasattr(dwt.lib, n)]
     assert not missing, missing
+
+
+def test_exports_nothing_the_headers_do_not_declare(dwt):
+    """Every C function the library exports is declared in a public header: no diagnosis entry or
+    internal helper leaks out as a plain C symbol (C++ mangled names are not the C-ABI)."""
+    if not shutil.which("nm"):
+        pytest.skip("nm is not installed")
+    out = subprocess.check_output(["nm", "-D", "--defined-only", os.path.join(ROOT, "libdwt_amd", "libdwt_hip.so")]).decode()
+    exported = {f[2] for f in (line.split() for line in out.splitlines()) if len(f) == 3 and f[1] in ("T", "W") and not f[2].startswith("_Z")}
+    declared = set()
+    for header in os.listdir(INCLUDE):
+        if header.endswith(".h"):
+            declared.update(declared_functions(header))
+    assert len(exported) > 100
+    undeclared = sorted(exported - declared)
+    assert not undeclared, undeclared
 
 
 def test_exports_every_function_the_opencv_wrapper_calls(dwt):
