@@ -155,6 +155,40 @@ void dwt_cdf97_2f1_s(void *ptr, int stride_x, int stride_y, int size_o_big_x, in
 void dwt_cdf53_2f1_s(void *ptr, int stride_x, int stride_y, int size_o_big_x, int size_o_big_y,
 	int size_i_big_x, int size_i_big_y, int *j_max_ptr, int zero_padding);
 
+/* ---- edge-avoiding CDF 5/3 wavelets (EAW, Fattal 2009), float -------------------------- */
+
+/* Forward, Mallat layout, in place.  Allocates wH[j] (size_o_src_y x size_i_src_x, row-major) and wV[j]
+ * (size_o_src_x x size_i_src_y, column-major) of every level j with dwt_util_alloc -- host memory the caller
+ * free()s -- and fills them; so a call on device memory copies its weights to the host (8 bytes per sample of
+ * each level).  Entries of one-sample lines are not written (the reference leaves them uninitialised).
+ * alpha 1 and 0 are bit-exact; any other alpha is within 1 ulp in the weights (include/libdwt_hip.h).
+ * src/libdwt.h:742, src/libdwt.c:16663. */
+void dwt_eaw53_2f_s(void *ptr, int stride_x, int stride_y, int size_o_big_x, int size_o_big_y,
+	int size_i_big_x, int size_i_big_y, int *j_max_ptr, int decompose_one, int zero_padding,
+	float *wH[], float *wV[], float alpha);
+
+/* Inverse of the above with the forward's weights (host arrays).  src/libdwt.h:1073, src/libdwt.c:18373. */
+void dwt_eaw53_2i_s(void *ptr, int stride_x, int stride_y, int size_o_big_x, int size_o_big_y,
+	int size_i_big_x, int size_i_big_y, int j_max, int decompose_one, int zero_padding,
+	float *wH[], float *wV[]);
+
+/* Interleaved layout (level j on the lattice of stride 2^j over the inner frame); wH[j], wV[j] both
+ * size_i_src_y x size_i_src_x (wV column-major); zero_padding is not used.  src/libdwt.h:758, 1088;
+ * src/libdwt.c:16602, 17932. */
+void dwt_eaw53_2f_inplace_s(void *ptr, int stride_x, int stride_y, int size_o_big_x, int size_o_big_y,
+	int size_i_big_x, int size_i_big_y, int *j_max_ptr, int decompose_one, int zero_padding,
+	float *wH[], float *wV[], float alpha);
+void dwt_eaw53_2i_inplace_s(void *ptr, int stride_x, int stride_y, int size_o_big_x, int size_o_big_y,
+	int size_i_big_x, int size_i_big_y, int j_max, int decompose_one, int zero_padding,
+	float *wH[], float *wV[]);
+
+/* Only clamps *j_max_ptr as the forward would.  src/libdwt.h:796, src/libdwt.c:16759. */
+void dwt_eaw53_2f_dummy_s(void *ptr, int stride_x, int stride_y, int size_o_big_x, int size_o_big_y,
+	int size_i_big_x, int size_i_big_y, int *j_max_ptr, int decompose_one);
+
+/* malloc(elems * elem_size): what the EAW forward allocates its weights with.  src/libdwt.h:3743. */
+void *dwt_util_alloc(int elems, size_t elem_size);
+
 /* ---- lifecycle and backend knobs (src/libdwt.h:1667-1745, 1974-1986) -------------- */
 void dwt_util_init(void);   /* brings the device up (the reference loads BCE firmware here) */
 void dwt_util_finish(void); /* releases device workspace */

@@ -182,6 +182,31 @@ int dwt_hip_transform1d(int wavelet, int inverse, const void *src, void *dst,
 int dwt_hip_transform1d_batch(int wavelet, int inverse, const void *src, void *dst,
 	size_t line_stride, int elem_stride, int n_lines, int size_o, int size_i, int *j, int zero_padding);
 
+/* Edge-avoiding CDF 5/3 wavelets (EAW, Fattal 2009; libdwt's dwt_eaw53_*: src/libdwt.h:742-796, 1073-1100), float.
+ * layout DWT_HIP_EAW_MALLAT: dwt_eaw53_2f_s / _2i_s; DWT_HIP_EAW_INTERLEAVED: dwt_eaw53_2f_inplace_s / _2i_inplace_s.
+ * In place on `ptr` (host or device memory, any byte strides); `*j` in/out for forward (clamped as the reference
+ * does), in for inverse.  `weights` is ONE caller-owned buffer in the same memory space as `ptr`, laid out as
+ * dwt_hip_eaw53_weights_layout says for the call's level count: the forward writes every level's wH / wV there (the
+ * reference's shapes and orders; entries of one-sample lines are left as they were), the inverse reads them.  alpha 1
+ * and 0 give the reference's bits; any other alpha computes |d|^alpha in double rounded once to float (within 1 ulp
+ * of glibc's powf).  The inverse is exact for every alpha.  A dense Mallat frame in HBM runs one launch per level. */
+#define DWT_HIP_EAW_MALLAT 0
+#define DWT_HIP_EAW_INTERLEAVED 1
+int dwt_hip_eaw53_2d(int inverse, int layout, void *ptr, int stride_x, int stride_y, int size_o_x, int size_o_y,
+	int size_i_x, int size_i_y, int *j, int decompose_one, int zero_padding, float *weights, float alpha);
+
+/* The same on `batch` dense Mallat images in HBM (size_o == size_i), `batch_stride` bytes apart, zero_padding 0;
+ * image b's weights at weights + b * weights_stride floats.  One launch per level covers the whole batch. */
+int dwt_hip_eaw53_2d_batch(int inverse, void *ptr, size_t batch_stride, int batch, int stride_x, int size_x, int size_y,
+	int *j, int decompose_one, float *weights, size_t weights_stride, float alpha);
+
+/* Floats of the weight buffer of a `j`-level EAW call (-1: bad arguments); off_h[k] / off_v[k] (k < j; either may be
+ * NULL) receive where level k's wH / wV start.  Mallat: wH[k] is size_o_src_y x size_i_src_x row-major, wV[k]
+ * size_o_src_x x size_i_src_y column-major (wV[k][x * size_i_src_y + y]); interleaved: both size_i_src_y x size_i_src_x
+ * (wV column-major too). */
+long dwt_hip_eaw53_weights_layout(int layout, int size_o_x, int size_o_y, int size_i_x, int size_i_y, int j,
+	long *off_h, long *off_v);
+
 /* Batch of independent equally sized dense images resident in HBM, `batch_stride`
  * bytes apart; one launch per level covers the whole batch. */
 int dwt_hip_transform2d_batch(int wavelet, int inverse, const void *src, void *dst,

@@ -472,6 +472,160 @@ def transform1d_batch(wavelet, inverse, src, dst, line_stride, n_lines, size, j_
     return j.value
 
 
+# ---- edge-avoiding 5/3 (EAW) entry points ---------------------------------------------
+EAW_MALLAT, EAW_INTERLEAVED = 0, 1
+lib.dwt_hip_eaw53_2d.argtypes = [_I, _I, _P, _I, _I, _I, _I, _I, _I, C.POINTER(_I), _I, _I, _P, C.c_float]
+lib.dwt_hip_eaw53_2d.restype = _I
+lib.dwt_hip_eaw53_2d_batch.argtypes = [_I, _P, _S, _I, _I, _I, _I, C.POINTER(_I), _I, _P, _S, C.c_float]
+lib.dwt_hip_eaw53_2d_batch.restype = _I
+lib.dwt_hip_eaw53_weights_layout.argtypes = [_I, _I, _I, _I, _I, _I, C.POINTER(C.c_long), C.POINTER(C.c_long)]
+lib.dwt_hip_eaw53_weights_layout.restype = C.c_long
+lib.dwt_eaw53_2f_dummy_s.argtypes = [_P, _I, _I, _I, _I, _I, _I, C.POINTER(_I), _I]
+lib.dwt_eaw53_2f_dummy_s.restype = None
+
+
+def eaw53_weights_layout(layout, size_o_x, size_o_y, size_i_x, size_i_y, j):
+    """dwt_hip_eaw53_weights_layout: (floats of the weight buffer, [(offset, shape) of wH[k]], [(offset, shape) of
+    wV[k]]).  wV[k] has shape (columns, samples per column): the C array is column-major."""
+    oh, ov = (C.c_long * 33)(), (C.c_long * 33)()
+    total = lib.dwt_hip_eaw53_weights_layout(layout, size_o_x, size_o_y, size_i_x, size_i_y, j, oh, ov)
+    if total < 0:
+        raise DwtError("dwt_hip_eaw53_weights_layout: bad arguments")
+
+    def cd(a, k):
+        return (a + (1 << k) - 1) >> k
+    hs, vs = [], []
+    for k in range(j):
+        if layout == EAW_MALLAT:
+            hs.append((oh[k], (cd(size_o_y, k), cd(size_i_x, k))))
+            vs.append((ov[k], (cd(size_o_x, k), cd(size_i_y, k))))
+        else:
+            hs.append((oh[k], (cd(size_i_y, k), cd(size_i_x, k))))
+            vs.append((ov[k], (cd(size_i_x, k), cd(size_i_y, k))))
+    return total, hs, vs
+
+
+def dwt_eaw53_2f_dummy_s(ptr, stride_x, stride_y, size_o_x, size_o_y, size_i_x, size_i_y, j_max=-1, decompose_one=0):
+    """src/libdwt.c:16759: the level count the forward would take."""
+    j = _I(j_max)
+    lib.dwt_eaw53_2f_dummy_s(None, stride_x, stride_y, size_o_x, size_o_y, size_i_x, size_i_y, C.byref(j), decompose_one)
+    return j.value
+
+
+def _eaw_levels(inverse, size_o_x, size_o_y, j_max, decompose_one):
+    n = max(size_o_x, size_o_y) if decompose_one else min(size_o_x, size_o_y)
+    lim = 0 if n else 32  # src/inline.h:443: 32 for an empty frame
+    while lim < 31 and (1 << lim) < n:
+        lim += 1
+    if not inverse:
+        return lim if (j_max < 0 or j_max > lim) else j_max
+    return j_max if 0 <= j_max < lim else lim
+
+
+def _eaw_call(inverse, layout, ptr, stride_x, stride_y, sox, soy, six, siy, j_max, decompose_one, zero_padding, wbuf, alpha, who):
+    j = _I(j_max)
+    _check(lib.dwt_hip_eaw53_2d(int(inverse), layout, _addr(ptr), stride_x, stride_y, sox, soy, six, siy, C.byref(j),
+                                decompose_one, zero_padding, wbuf, float(alpha)), who)
+    return j.value
+
+
+def _eaw_forward(layout, ptr, stride_x, stride_y, sox, soy, six, siy, j_max, decompose_one, zero_padding, alpha, who):
+    import numpy as np
+
+    J = _eaw_levels(False, sox, soy, j_max, decompose_one)
+    total, hs, vs = eaw53_weights_layout(layout, sox, soy, six, siy, J)
+    w = np.zeros(max(total, 1), dtype=np.float32)
+    p = _addr(ptr)
+    if lib.dwt_hip_is_device_pointer(p):
+        d = lib.dwt_hip_malloc(w.nbytes)
+        if not d:
+            raise DwtError("dwt_hip_malloc: " + last_error())
+        try:
+            _check(lib.dwt_hip_memcpy_h2d(d, w.ctypes.data, w.nbytes), who)
+            j = _eaw_call(0, layout, p, stride_x, stride_y, sox, soy, six, siy, j_max, decompose_one, zero_padding, d, alpha, who)
+            _check(lib.dwt_hip_memcpy_d2h(w.ctypes.data, d, w.nbytes), who)
+        finally:
+            lib.dwt_hip_free(d)
+    else:
+        j = _eaw_call(0, layout, p, stride_x, stride_y, sox, soy, six, siy, j_max, decompose_one, zero_padding, w.ctypes.data,
+                      alpha, who)
+    wH = [w[o:o + a * b].reshape(a, b).copy() for o, (a, b) in hs]
+    wV = [w[o:o + a * b].reshape(a, b).copy() for o, (a, b) in vs]
+    return j, wH, wV
+
+
+def _eaw_inverse(layout, ptr, stride_x, stride_y, sox, soy, six, siy, j_max, decompose_one, zero_padding, wH, wV, who):
+    import numpy as np
+
+    J = _eaw_levels(True, sox, soy, j_max, decompose_one)
+    total, hs, vs = eaw53_weights_layout(layout, sox, soy, six, siy, J)
+    w = np.zeros(max(total, 1), dtype=np.float32)
+    for k in range(J):
+        for (o, (a, b)), arr in ((hs[k], wH[k]), (vs[k], wV[k])):
+            w[o:o + a * b] = np.asarray(arr, dtype=np.float32).reshape(-1)[:a * b]
+    p = _addr(ptr)
+    if lib.dwt_hip_is_device_pointer(p):
+        d = lib.dwt_hip_malloc(w.nbytes)
+        if not d:
+            raise DwtError("dwt_hip_malloc: " + last_error())
+        try:
+            _check(lib.dwt_hip_memcpy_h2d(d, w.ctypes.data, w.nbytes), who)
+            _eaw_call(1, layout, p, stride_x, stride_y, sox, soy, six, siy, j_max, decompose_one, zero_padding, d, 1.0, who)
+        finally:
+            lib.dwt_hip_free(d)
+    else:
+        _eaw_call(1, layout, p, stride_x, stride_y, sox, soy, six, siy, j_max, decompose_one, zero_padding, w.ctypes.data, 1.0, who)
+    return j_max
+
+
+def dwt_eaw53_2f_s(ptr, stride_x, stride_y, size_o_x, size_o_y, size_i_x, size_i_y, j_max=-1, decompose_one=0,
+                   zero_padding=0, alpha=1.0):
+    """src/libdwt.c:16663.  Returns (levels done, wH, wV): wH[k] a (size_o_src_y, size_i_src_x) array, wV[k] a
+    (size_o_src_x, size_i_src_y) array (wV[k][x, y], the C array's column-major order)."""
+    return _eaw_forward(EAW_MALLAT, ptr, stride_x, stride_y, size_o_x, size_o_y, size_i_x, size_i_y, j_max, decompose_one,
+                        zero_padding, alpha, "dwt_eaw53_2f_s")
+
+
+def dwt_eaw53_2i_s(ptr, stride_x, stride_y, size_o_x, size_o_y, size_i_x, size_i_y, j_max, decompose_one, zero_padding, wH, wV):
+    """src/libdwt.c:18373, with the forward's weight arrays."""
+    return _eaw_inverse(EAW_MALLAT, ptr, stride_x, stride_y, size_o_x, size_o_y, size_i_x, size_i_y, j_max, decompose_one,
+                        zero_padding, wH, wV, "dwt_eaw53_2i_s")
+
+
+def dwt_eaw53_2f_inplace_s(ptr, stride_x, stride_y, size_o_x, size_o_y, size_i_x, size_i_y, j_max=-1, decompose_one=0,
+                           zero_padding=0, alpha=1.0):
+    """src/libdwt.c:16602 (interleaved layout).  wH[k], wV[k] as for dwt_eaw53_2f_s over the inner frame."""
+    return _eaw_forward(EAW_INTERLEAVED, ptr, stride_x, stride_y, size_o_x, size_o_y, size_i_x, size_i_y, j_max,
+                        decompose_one, zero_padding, alpha, "dwt_eaw53_2f_inplace_s")
+
+
+def dwt_eaw53_2i_inplace_s(ptr, stride_x, stride_y, size_o_x, size_o_y, size_i_x, size_i_y, j_max, decompose_one, zero_padding,
+                           wH, wV):
+    """src/libdwt.c:17932"""
+    return _eaw_inverse(EAW_INTERLEAVED, ptr, stride_x, stride_y, size_o_x, size_o_y, size_i_x, size_i_y, j_max, decompose_one,
+                        zero_padding, wH, wV, "dwt_eaw53_2i_inplace_s")
+
+
+def eaw53_2d_batch(inverse, ptr, batch_stride, batch, stride_x, size_x, size_y, weights, weights_stride, j_max=-1,
+                   decompose_one=0, alpha=1.0):
+    """EAW 5/3 of `batch` dense float images (Mallat layout, in place) `batch_stride` bytes apart, image b's weights
+    (one buffer laid out as eaw53_weights_layout says) at `weights` + b * weights_stride floats.  numpy arrays, torch
+    tensors or raw pointers: device memory runs one launch per level for the whole batch, host memory image by image.
+    Returns the level count (forward: clamped)."""
+    p, w = _addr(ptr), _addr(weights)
+    j = _I(j_max)
+    if lib.dwt_hip_is_device_pointer(p):
+        _check(lib.dwt_hip_eaw53_2d_batch(int(inverse), p, batch_stride, batch, stride_x, size_x, size_y, C.byref(j),
+                                          decompose_one, w, weights_stride, float(alpha)), "dwt_hip_eaw53_2d_batch")
+        return j.value
+    for b in range(batch):
+        j = _I(j_max)
+        _check(lib.dwt_hip_eaw53_2d(int(inverse), EAW_MALLAT, p + b * batch_stride, stride_x, 4, size_x, size_y, size_x, size_y,
+                                    C.byref(j), decompose_one, 0, w + 4 * b * weights_stride, float(alpha)),
+               "dwt_hip_eaw53_2d")
+    return _eaw_levels(bool(inverse), size_x, size_y, j_max, decompose_one) if batch == 0 else j.value
+
+
 # ---- batches resident in HBM -----------------------------------------------------------
 def transform2d_batch(wavelet, inverse, src, dst, batch_stride, batch, stride_x, size_x, size_y, j_max=-1):
     j = _I(j_max)

@@ -47,11 +47,14 @@ struct Ctx {
 	hipEvent_t pipe_ev[3][16] = {};
 	int host_pipeline = 1; // 0: upload, transform, download one after the other
 	void *pin = nullptr; // pinned host staging for host-pointer calls with awkward strides
+	void *eaw_w = nullptr, *eaw_ll[2] = {nullptr, nullptr}; // EAW: device weights of a host-pointer call, LL ping-pong of the fused levels
+	size_t eaw_w_bytes = 0, eaw_ll_bytes[2] = {0, 0};
 	size_t pin_bytes = 0;
 	// options
 	SweepTuning tune;
 	VolTuning vol;
 	int force_generic = 0;
+	int eaw_two_pass = 0; // EAW: every level as a row pass and a column pass (dwt_backend_eaw.hip), the fused levels' cross-check
 	int fma = 0; // opt-in: contract the float 9/7 lifting steps (not bit-identical to libdwt)
 	int il_temporal = 0; // set per interleaved call: the forward sweep of level 0 stores its even rows temporal (in place: the copy back reads them)
 	int il_inplace_shell = 1; // interleaved in-place calls: level 0 over a snapshot of the tile halos (0: through a staging image, the cross-check)
