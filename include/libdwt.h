@@ -155,6 +155,20 @@ void dwt_cdf97_2f1_s(void *ptr, int stride_x, int stride_y, int size_o_big_x, in
 void dwt_cdf53_2f1_s(void *ptr, int stride_x, int stride_y, int size_o_big_x, int size_o_big_y,
 	int size_i_big_x, int size_i_big_y, int *j_max_ptr, int zero_padding);
 
+/* ---- interpolating 5/3 wavelet, float --------------------------------------------------- */
+
+/* CDF 5/3 with the predict step only (no update), then the CDF 5/3 scaling; Mallat layout, in place, all
+ * arguments as for dwt_cdf53_2f_s / _2i_s and dwt_cdf53_1f_s / _1i_s.  src/libdwt.h:813, 1108, 1160, 1217;
+ * src/libdwt.c:16801, 18457, 16166, 15900. */
+void dwt_interp53_2f_s(void *ptr, int stride_x, int stride_y,
+	int size_o_big_x, int size_o_big_y, int size_i_big_x, int size_i_big_y,
+	int *j_max_ptr, int decompose_one, int zero_padding);
+void dwt_interp53_2i_s(void *ptr, int stride_x, int stride_y,
+	int size_o_big_x, int size_o_big_y, int size_i_big_x, int size_i_big_y,
+	int j_max, int decompose_one, int zero_padding);
+void dwt_interp53_1f_s(void *ptr, int stride_y, int size_o_big_x, int size_i_big_x, int *j_max_ptr, int zero_padding);
+void dwt_interp53_1i_s(void *ptr, int stride_y, int size_o_big_x, int size_i_big_x, int j_max, int zero_padding);
+
 /* ---- edge-avoiding CDF 5/3 wavelets (EAW, Fattal 2009), float -------------------------- */
 
 /* Forward, Mallat layout, in place.  Allocates wH[j] (size_o_src_y x size_i_src_x, row-major) and wV[j]

@@ -48,7 +48,10 @@ enum dwt_hip_wavelet {
 	DWT_HIP_CDF53_S = 2, /* float CDF 5/3: dwt_cdf53_2f_s / dwt_cdf53_2i_s (src/libdwt.c:16470, 18296) */
 	DWT_HIP_CDF97_D = 3, /* double CDF 9/7: dwt_cdf97_2f_d / dwt_cdf97_2i_d (src/libdwt.c:12451, 16884) */
 	DWT_HIP_CDF53_D = 4, /* double CDF 5/3: dwt_cdf53_2f_d / dwt_cdf53_2i_d (src/libdwt.c:12535, 16962) */
-	DWT_HIP_CDF97_I = 5  /* int32 fixed-point CDF 9/7: dwt_cdf97_2f_i / dwt_cdf97_2i_i (src/libdwt.c:16387, 18219) */
+	DWT_HIP_CDF97_I = 5, /* int32 fixed-point CDF 9/7: dwt_cdf97_2f_i / dwt_cdf97_2i_i (src/libdwt.c:16387, 18219) */
+	DWT_HIP_INTERP53_S = 6 /* float interpolating 5/3 (CDF 5/3 predict step, no update): dwt_interp53_2f_s / dwt_interp53_2i_s
+	                          (src/libdwt.c:16801, 18457), 1-D dwt_interp53_1f_s / _1i_s (:16166, :15900); not in the
+	                          interleaved layout */
 };
 
 /* Lifecycle.  dwt_hip_init picks the device from DWT_HIP_DEVICE, else LOCAL_RANK,
@@ -167,8 +170,8 @@ int dwt_hip_transform2d(int wavelet, int inverse, const void *src, void *dst,
 	int stride_x, int stride_y, int size_o_big_x, int size_o_big_y,
 	int size_i_big_x, int size_i_big_y, int *j, int decompose_one, int zero_padding);
 
-/* Multi-level 1-D transform of one float line (wavelet DWT_HIP_CDF97_S or
- * DWT_HIP_CDF53_S), Mallat layout, arguments as in libdwt's 1-D drivers
+/* Multi-level 1-D transform of one float line (wavelet DWT_HIP_CDF97_S,
+ * DWT_HIP_CDF53_S or DWT_HIP_INTERP53_S), Mallat layout, arguments as in libdwt's 1-D drivers
  * (src/libdwt.h:1128-1208): elements `stride` bytes apart, `*j` in/out for forward
  * (clamped as the reference does), in for inverse.  src == dst: in place; otherwise
  * dst receives the transform of src's frame.  Host or device pointers (host: the call

@@ -27,6 +27,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DWT_HIP_LIB") or os.path.join(_HERE, "libdwt_hip.so")  # (DWT_HIP_LIB: another build of the library, for A/B scripts)
 
 CDF97_S, CDF53_I, CDF53_S, CDF97_D, CDF53_D, CDF97_I = 0, 1, 2, 3, 4, 5
+INTERP53_S = 6  # interpolating 5/3 float: the CDF 5/3 predict step alone (DWT_HIP_INTERP53_S)
 
 
 class DwtError(RuntimeError):
@@ -53,7 +54,8 @@ _INV2 = [_P, _P] + _INV[1:]
 for _n, _sig in (("dwt_cdf97_2f_s", _FWD), ("dwt_cdf97_2i_s", _INV), ("dwt_cdf97_2f_s2", _FWD2),
                  ("dwt_cdf97_2i_s2", _INV2), ("dwt_cdf53_2f_i", _FWD), ("dwt_cdf53_2i_i", _INV),
                  ("dwt_cdf53_2f_s", _FWD), ("dwt_cdf53_2i_s", _INV), ("dwt_cdf97_2f_d", _FWD), ("dwt_cdf97_2i_d", _INV),
-                 ("dwt_cdf53_2f_d", _FWD), ("dwt_cdf53_2i_d", _INV), ("dwt_cdf97_2f_i", _FWD), ("dwt_cdf97_2i_i", _INV)):
+                 ("dwt_cdf53_2f_d", _FWD), ("dwt_cdf53_2i_d", _INV), ("dwt_cdf97_2f_i", _FWD), ("dwt_cdf97_2i_i", _INV),
+                 ("dwt_interp53_2f_s", _FWD), ("dwt_interp53_2i_s", _INV)):
     getattr(lib, _n).argtypes = _sig
     getattr(lib, _n).restype = None
 
@@ -339,12 +341,28 @@ def dwt_cdf97_2i_i(ptr, stride_x, stride_y, size_o_big_x, size_o_big_y, size_i_b
          j_max, decompose_one, zero_padding, "dwt_cdf97_2i_i")
 
 
+def dwt_interp53_2f_s(ptr, stride_x, stride_y, size_o_big_x, size_o_big_y, size_i_big_x, size_i_big_y,
+                      j_max=-1, decompose_one=0, zero_padding=0):
+    """src/libdwt.c:16801 (interpolating 5/3: CDF 5/3 without the update step)"""
+    return _fwd(INTERP53_S, ptr, ptr, stride_x, stride_y, size_o_big_x, size_o_big_y, size_i_big_x, size_i_big_y,
+                j_max, decompose_one, zero_padding, "dwt_interp53_2f_s")
+
+
+def dwt_interp53_2i_s(ptr, stride_x, stride_y, size_o_big_x, size_o_big_y, size_i_big_x, size_i_big_y,
+                      j_max=-1, decompose_one=0, zero_padding=0):
+    """src/libdwt.c:18457"""
+    _inv(INTERP53_S, ptr, ptr, stride_x, stride_y, size_o_big_x, size_o_big_y, size_i_big_x, size_i_big_y,
+         j_max, decompose_one, zero_padding, "dwt_interp53_2i_s")
+
+
 FORWARD = {"cdf97_s": dwt_cdf97_2f_s, "cdf53_i": dwt_cdf53_2f_i, "cdf53_s": dwt_cdf53_2f_s,
-           "cdf97_d": dwt_cdf97_2f_d, "cdf53_d": dwt_cdf53_2f_d, "cdf97_i": dwt_cdf97_2f_i}
+           "cdf97_d": dwt_cdf97_2f_d, "cdf53_d": dwt_cdf53_2f_d, "cdf97_i": dwt_cdf97_2f_i,
+           "interp53_s": dwt_interp53_2f_s}
 INVERSE = {"cdf97_s": dwt_cdf97_2i_s, "cdf53_i": dwt_cdf53_2i_i, "cdf53_s": dwt_cdf53_2i_s,
-           "cdf97_d": dwt_cdf97_2i_d, "cdf53_d": dwt_cdf53_2i_d, "cdf97_i": dwt_cdf97_2i_i}
+           "cdf97_d": dwt_cdf97_2i_d, "cdf53_d": dwt_cdf53_2i_d, "cdf97_i": dwt_cdf97_2i_i,
+           "interp53_s": dwt_interp53_2i_s}
 WAVELET_ID = {"cdf97_s": CDF97_S, "cdf53_i": CDF53_I, "cdf53_s": CDF53_S, "cdf97_d": CDF97_D, "cdf53_d": CDF53_D,
-              "cdf97_i": CDF97_I}
+              "cdf97_i": CDF97_I, "interp53_s": INTERP53_S}
 
 
 # ---- interleaved (in-place lifting) layout ------------------------------------------------
@@ -441,6 +459,16 @@ def dwt_cdf97_1i_s(ptr, stride, size_o, size_i, j_max=-1, zero_padding=0):
 def dwt_cdf53_1i_s(ptr, stride, size_o, size_i, j_max=-1, zero_padding=0):
     """src/libdwt.c:15835"""
     return _line(CDF53_S, 1, ptr, stride, size_o, size_i, j_max, zero_padding, "dwt_cdf53_1i_s")
+
+
+def dwt_interp53_1f_s(ptr, stride, size_o, size_i, j_max=-1, zero_padding=0):
+    """src/libdwt.c:16166"""
+    return _line(INTERP53_S, 0, ptr, stride, size_o, size_i, j_max, zero_padding, "dwt_interp53_1f_s")
+
+
+def dwt_interp53_1i_s(ptr, stride, size_o, size_i, j_max=-1, zero_padding=0):
+    """src/libdwt.c:15900"""
+    return _line(INTERP53_S, 1, ptr, stride, size_o, size_i, j_max, zero_padding, "dwt_interp53_1i_s")
 
 
 def _series(wavelet, who):

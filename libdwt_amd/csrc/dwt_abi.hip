@@ -363,15 +363,15 @@ int dwt_hip_transform2d(int wavelet, int inverse, const void *src, void *dst, in
 {
 	if (check_inited())
 		return 1;
-	if (wavelet < 0 || wavelet > 5)
+	Wavelet w;
+	if (!wavelet_of(wavelet, &w))
 		return fail("unknown wavelet %d", wavelet);
 	if (!src || !dst || !j)
 		return fail("null pointer argument");
-	const int es = elem_size((Wavelet)wavelet);
+	const int es = elem_size(w);
 	g_elems_are_32bit = (es == 4);
 	if (sox <= 0 || soy <= 0 || six < 0 || siy < 0 || six > sox || siy > soy)
 		return fail("bad sizes: outer %dx%d inner %dx%d", sox, soy, six, siy);
-	const Wavelet w = (Wavelet)wavelet;
 	const Geom ge{sox, soy, six, siy};
 	const bool dev_src = dwt_hip_is_device_pointer(src), dev_dst = dwt_hip_is_device_pointer(dst);
 	if (dev_src != dev_dst)
@@ -455,8 +455,10 @@ int dwt_hip_transform1d_batch(int wavelet, int inverse, const void *src, void *d
 {
 	if (check_inited())
 		return 1;
-	if (wavelet != DWT_HIP_CDF97_S && wavelet != DWT_HIP_CDF53_S)
-		return fail("1-D transforms exist for DWT_HIP_CDF97_S and DWT_HIP_CDF53_S only (wavelet %d)", wavelet);
+	if (wavelet != DWT_HIP_CDF97_S && wavelet != DWT_HIP_CDF53_S && wavelet != DWT_HIP_INTERP53_S)
+		return fail("1-D transforms exist for DWT_HIP_CDF97_S, DWT_HIP_CDF53_S and DWT_HIP_INTERP53_S only (wavelet %d)", wavelet);
+	Wavelet w;
+	wavelet_of(wavelet, &w);
 	if (!src || !dst || !j)
 		return fail("null pointer argument");
 	if (n_lines < 0 || size_o < 0 || size_i < 0 || size_i > size_o)
@@ -464,7 +466,7 @@ int dwt_hip_transform1d_batch(int wavelet, int inverse, const void *src, void *d
 	if (elem_stride < 4 || line_stride > (size_t)LONG_MAX / 2)
 		return fail("bad strides: line %zu bytes, element %d bytes", line_stride, elem_stride);
 	g_elems_are_32bit = true;
-	return transform1d((Wavelet)wavelet, inverse != 0, src, dst, (long)line_stride, elem_stride, n_lines, size_o, size_i, j, zero_padding);
+	return transform1d(w, inverse != 0, src, dst, (long)line_stride, elem_stride, n_lines, size_o, size_i, j, zero_padding);
 }
 
 int dwt_hip_transform1d(int wavelet, int inverse, const void *src, void *dst, int stride, int size_o, int size_i, int *j,
@@ -478,9 +480,10 @@ int dwt_hip_transform2d_batch(int wavelet, int inverse, const void *src, void *d
 {
 	if (check_inited())
 		return 1;
-	if (wavelet < 0 || wavelet > 5)
+	Wavelet w;
+	if (!wavelet_of(wavelet, &w))
 		return fail("unknown wavelet %d", wavelet);
-	const int es = elem_size((Wavelet)wavelet);
+	const int es = elem_size(w);
 	g_elems_are_32bit = es == 4;
 	if (!src || !dst || !j || batch < 1 || batch > 65535)
 		return fail("bad argument (batch must be 1..65535)");
@@ -492,10 +495,10 @@ int dwt_hip_transform2d_batch(int wavelet, int inverse, const void *src, void *d
 		return fail("in-place batches are not supported; use distinct src and dst");
 	const Geom ge{size_x, size_y, size_x, size_y};
 	Img s{(char *)src, stride_x, es}, d{(char *)dst, stride_x, es};
-	if (!inverse && (*j < 0 || *j >= 2) && place_ll_scratch((Wavelet)wavelet, s, d, ge, *j, batch, (long)batch_stride, (long)batch_stride))
+	if (!inverse && (*j < 0 || *j >= 2) && place_ll_scratch(w, s, d, ge, *j, batch, (long)batch_stride, (long)batch_stride))
 		return 1;
-	return inverse ? inverse2d((Wavelet)wavelet, s, d, ge, *j, 0, 0, batch, (long)batch_stride, (long)batch_stride)
-	               : forward2d((Wavelet)wavelet, s, d, ge, j, 0, 0, batch, (long)batch_stride, (long)batch_stride);
+	return inverse ? inverse2d(w, s, d, ge, *j, 0, 0, batch, (long)batch_stride, (long)batch_stride)
+	               : forward2d(w, s, d, ge, j, 0, 0, batch, (long)batch_stride, (long)batch_stride);
 }
 
 int dwt_hip_conv_show(int is_int, const void *src, void *dst, int stride_x, int stride_y, int size_x, int size_y)

@@ -102,6 +102,21 @@ extern thread_local bool g_elems_are_32bit; // set per call: the fused sweeps ex
 
 int fail(const char *fmt, ...);
 
+// The public wavelet id of a C-ABI call (enum dwt_hip_wavelet) as the internal enum Wavelet: ids 0..5 are the same
+// numbers, DWT_HIP_INTERP53_S (6) is kInterp53S -- internal 6 is the contracted float 9/7.  false: no such public id.
+static inline bool wavelet_of(int id, Wavelet *w)
+{
+	if (id >= 0 && id <= 5) {
+		*w = (Wavelet)id;
+		return true;
+	}
+	if (id == DWT_HIP_INTERP53_S) {
+		*w = kInterp53S;
+		return true;
+	}
+	return false;
+}
+
 #define HIP_TRY(expr)                                                                          \
 	do {                                                                                       \
 		hipError_t e_ = (expr);                                                                \

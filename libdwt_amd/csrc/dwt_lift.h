@@ -212,6 +212,34 @@ struct Cdf53S {
 	static __device__ __forceinline__ T step_k(T k, T c, T l, T r) { return c + k * (l + r); }
 };
 
+// Interpolating 5/3 (src/libdwt.c:11252-11291 forward, :12004-12044 inverse; constants inline.h:332-335): the CDF 5/3
+// predict step alone, no update, and the CDF 5/3 scaling.  ONE lifting step, so the conventions above shift by one
+// sample: a forward window starts at an even sample (its step 0 acts on odd entries), and so does an inverse window --
+// the inverse step 0 undoes the predict, on odd samples too.  Not Cdf53S with a zero update: c + 0 (l + r) turns an
+// Inf / NaN neighbour into NaN and -0 into +0.
+struct Interp53S {
+	using T = float;
+	static constexpr bool kEndForms = DWT_FLOAT_END_FORMS != 0; // the reference adds (2c)*x at a line end
+	static constexpr int K = 1;
+	static constexpr bool kScaleSingle = true;     // :11264-11266, :12017-12019
+	static constexpr bool kSkipSingleLine = false; // the 2-D drivers run every direction (as dwt_cdf53_2f_s / _2i_s)
+	static constexpr bool kInvColsFirst = false;   // inverse: rows then columns
+	static __device__ __forceinline__ T s1() { return 1.41421356237309504880f; }
+	static __device__ __forceinline__ T s2() { return 0.70710678118654752440f; }
+	static __device__ __forceinline__ T fwd_step(int, T c, T l, T r) { return c - 0.5f * (l + r); }
+	static __device__ __forceinline__ T inv_step(int, T c, T l, T r) { return c + 0.5f * (l + r); }
+	static __device__ __forceinline__ T fwd_scale(int parity, T v) { return parity ? v * s2() : v * s1(); }
+	static __device__ __forceinline__ T inv_scale(int parity, T v) { return parity ? v * s1() : v * s2(); }
+	static __device__ __forceinline__ T fwd_single(T v) { return v * s1(); }
+	static __device__ __forceinline__ T inv_single(T v) { return v * s2(); }
+	// line end (:11280-11283, :12034-12037): the last odd sample of an even-length line `-= 2*p1*x` / `+= 2*p1*x`
+	static __device__ __forceinline__ T fwd_end(int, T c, T m) { return c - (2 * 0.5f) * m; }
+	static __device__ __forceinline__ T inv_end(int, T c, T m) { return c + (2 * 0.5f) * m; }
+	static __device__ __forceinline__ T fk(int) { return -0.5f; }
+	static __device__ __forceinline__ T ik(int) { return 0.5f; }
+	static __device__ __forceinline__ T step_k(T k, T c, T l, T r) { return c + k * (l + r); }
+};
+
 // dwt-simple.c's 5/3 (fdwt2_cdf53_*, :1031-1078, :1531-1570): same steps, but the odd
 // coefficients are scaled by `1/zeta` computed in float instead of the stored s2.
 struct Cdf53SNew : Cdf53S {

@@ -78,7 +78,9 @@ __global__ __launch_bounds__(256) void k_line_levels(const char *__restrict__ sr
 				} else {
 					for (int k = t; k < nl; k += tpl) {
 						T w[2 * K + 1];
-						const int g0 = 2 * k - K;
+						// (F = 1: a policy of one step, whose window 2k .. 2k+2 starts at the even sample)
+						constexpr int F = K & 1;
+						const int g0 = 2 * k - K + F;
 						if (g0 >= 0 && g0 + 2 * K < n) {
 #pragma unroll
 							for (int j = 0; j <= 2 * K; j++)
@@ -89,9 +91,9 @@ __global__ __launch_bounds__(256) void k_line_levels(const char *__restrict__ sr
 								w[j] = cur[reflect(g0 + j, n)];
 						}
 						lift_fwd_regs<W, 2 * K + 1>(w, W::kEndForms ? end_mask<2 * K + 1>(g0, n) : 0u);
-						nxt[k] = W::fwd_scale(0, w[K]);
+						nxt[k] = W::fwd_scale(0, w[K - F]);
 						if (2 * k + 1 < n)
-							st(nl + k, W::fwd_scale(1, w[K + 1])); // H: final, to its Mallat offset
+							st(nl + k, W::fwd_scale(1, w[K + 1 - F])); // H: final, to its Mallat offset
 					}
 				}
 			}
@@ -176,6 +178,7 @@ hipError_t launch_line_levels(Wavelet w, bool inverse, const void *src, void *ds
 	switch (w) {
 	case kCdf97S: return line_levels_t<Cdf97S>(inverse, src, dst, line_stride, elem_stride, n_lines, N, levels, s);
 	case kCdf53S: return line_levels_t<Cdf53S>(inverse, src, dst, line_stride, elem_stride, n_lines, N, levels, s);
+	case kInterp53S: return line_levels_t<Interp53S>(inverse, src, dst, line_stride, elem_stride, n_lines, N, levels, s);
 	default: return hipErrorInvalidValue;
 	}
 }

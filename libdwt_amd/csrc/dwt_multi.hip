@@ -224,7 +224,8 @@ static int batch_multi(bool tune, int wavelet, int inverse, const void *const *s
 		return 1;
 	if (!srcs || !dsts || !counts || !devices || !j || n_shards < 1 || n_shards > 64)
 		return fail("dwt_hip_transform2d_batch_multi: bad argument");
-	if (wavelet < 0 || wavelet > 5)
+	Wavelet w_;
+	if (!wavelet_of(wavelet, &w_))
 		return fail("unknown wavelet %d", wavelet);
 	const int ndev = dwt_hip_device_count();
 	for (int k = 0; k < n_shards; k++) {
@@ -332,9 +333,10 @@ int dwt_hip_transform2d_batch_sharded(int wavelet, int inverse, const void *src,
 	for (int k = 0; k < n_devices; k++)
 		if (devices[k] < 0 || devices[k] >= ndev)
 			return fail("devices[%d] = %d: the process sees %d device(s)", k, devices[k], ndev);
-	if (wavelet < 0 || wavelet > 5)
+	Wavelet w_;
+	if (!wavelet_of(wavelet, &w_))
 		return fail("unknown wavelet %d", wavelet);
-	const int es = elem_size((Wavelet)wavelet);
+	const int es = elem_size(w_);
 	const int G = n_devices < batch ? n_devices : batch; // never more slots than images
 	const bool dense = (size_t)stride_x == (size_t)size_x * es && batch_stride == (size_t)stride_x * size_y;
 	std::lock_guard<std::mutex> turn(g_slots_mu);

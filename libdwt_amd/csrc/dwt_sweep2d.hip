@@ -62,16 +62,18 @@ __global__ __launch_bounds__(256) void k_line_pass(const char *__restrict__ src,
 	}
 	T w[2 * K + 1];
 	if (!INV) {
-		// w[j] = a[2k-K+j]; w[0] is an even sample
+		// w[j] = a[2k-K+F+j]; w[0] is an even sample (F = 1 for a policy of one step, whose window is 2k .. 2k+2)
+		constexpr int F = K & 1;
 #pragma unroll
 		for (int j = 0; j <= 2 * K; j++)
-			w[j] = ld(reflect(2 * k - K + j, N));
-		lift_fwd_regs<W, 2 * K + 1>(w, W::kEndForms ? end_mask<2 * K + 1>(2 * k - K, N) : 0u);
-		st(il ? 2 * k : k, W::fwd_scale(0, w[K]));
+			w[j] = ld(reflect(2 * k - K + F + j, N));
+		lift_fwd_regs<W, 2 * K + 1>(w, W::kEndForms ? end_mask<2 * K + 1>(2 * k - K + F, N) : 0u);
+		st(il ? 2 * k : k, W::fwd_scale(0, w[K - F]));
 		if (2 * k + 1 < N)
-			st(il ? 2 * k + 1 : hoff + k, W::fwd_scale(1, w[K + 1]));
+			st(il ? 2 * k + 1 : hoff + k, W::fwd_scale(1, w[K + 1 - F]));
 	} else {
-		// w[j] = a[2k-K+1+j] of the interleaved signal; w[0] is an odd sample
+		// w[j] = a[2k-K+1+j] of the interleaved signal; w[0] is an odd sample (an even one for a policy of one step, whose
+		// step 0 undoes the predict on odd samples)
 #pragma unroll
 		for (int j = 0; j <= 2 * K; j++) {
 			const int i = reflect(2 * k - K + 1 + j, N);
@@ -115,6 +117,7 @@ hipError_t launch_line_pass(Wavelet w, bool inverse, const void *src, void *dst,
 	case kCdf97I: return line_pass_t<Cdf97I>(inverse, src, dst, line_stride, elem_stride, n_lines, N, hoff, lanes_along_lines, s);
 	case kCdf53SNew: return line_pass_t<Cdf53SNew>(inverse, src, dst, line_stride, elem_stride, n_lines, N, hoff, lanes_along_lines, s);
 	case kCdf97IIp: return line_pass_t<Cdf97IIp>(inverse, src, dst, line_stride, elem_stride, n_lines, N, hoff, lanes_along_lines, s);
+	case kInterp53S: return line_pass_t<Interp53S>(inverse, src, dst, line_stride, elem_stride, n_lines, N, hoff, lanes_along_lines, s);
 	// the contracted variant exists for the fused sweeps only: line passes of such a call are exact
 	case kCdf97SFma: return line_pass_t<Cdf97S>(inverse, src, dst, line_stride, elem_stride, n_lines, N, hoff, lanes_along_lines, s);
 	}
@@ -136,6 +139,7 @@ hipError_t launch_line_pass(Wavelet w, bool inverse, const void *src, void *dst,
 // row[0] / row[1]: the odd / even row of the iteration; st: the streaming state; lo / hi: the scaled outputs.
 // SEL: the select form of the line ends -- ve[s]: step s acts on a row that is a column's end (wave-uniform), kv[s] its
 // coefficient (doubled there); the state tap gives way to -0.0 (dwt_lift.h, SelEnds).
+// (K = 2 and 4; a policy of one step takes the scalar form of the sweep)
 template <class W, int CPT, bool SEL = false, class T>
 static __device__ __forceinline__ void vertical_pairs(const T (&row)[2][CPT], T (&st)[W::K][CPT], T (&lo)[CPT], T (&hi)[CPT],
 	const bool *ve = nullptr, const T *kv = nullptr)
@@ -198,7 +202,10 @@ static __device__ __forceinline__ void fwd_sweep_tile(const FwdLevelArgs &a, con
 	constexpr bool kShuffle = (NT & 8) != 0;
 	constexpr int TW = 64 * CPT;
 	constexpr int RS = TW + 8; // LDS row slot: [main TW | left halo 4 | right halo 4]
-	constexpr int NARR = CPT + 2 * K;
+	// horizontal halo: K samples, rounded up to even so that the lane's window starts at an even column (a policy of one
+	// step: columns c - 2 .. c + CPT + 1, whose entry 1 is lifted in vain)
+	constexpr int HK = (K + 1) & ~1;
+	constexpr int NARR = CPT + 2 * HK;
 	constexpr int kDmaPerIter = 2 * (CPT / 4 + 1); // fewest DMA instructions an iteration issues
 	// (float policies whose step is c + k (l + r) rounded product-then-sum: the horizontal lift takes both rows at once)
 	constexpr bool kPairRows = kIsSelEnds<W> && std::is_same<T, float>::value && has_coef_ends<W>::value && !std::is_base_of<Cdf97SFma, W>::value;
@@ -331,9 +338,9 @@ static __device__ __forceinline__ void fwd_sweep_tile(const FwdLevelArgs &a, con
 	[[maybe_unused]] bool h_any = false, h_simple = false;
 	// the two entries of a lane's window that meet a line end when the level's width is a multiple of CPT: column 0 is
 	// lane 0's own first column, column W - 1 a lane's own last one (entries 0 and NARR - 1 are never acted on)
-	constexpr unsigned kCand = (1u << K) | (1u << (K + CPT - 1));
+	constexpr unsigned kCand = (1u << HK) | (1u << (HK + CPT - 1));
 	if constexpr (W::kEndForms) {
-		hends = end_mask<NARR>(c0 + lane * CPT - K, a.W);
+		hends = end_mask<NARR>(c0 + lane * CPT - HK, a.W);
 		h_any = !a.plain_ends && __builtin_amdgcn_ballot_w64(hends != 0) != 0;
 		h_simple = __builtin_amdgcn_ballot_w64((hends & ~(kCand | 1u | (1u << (NARR - 1)))) != 0) == 0;
 	}
@@ -341,10 +348,10 @@ static __device__ __forceinline__ void fwd_sweep_tile(const FwdLevelArgs &a, con
 	[[maybe_unused]] bool e0 = false, e1 = false;
 	[[maybe_unused]] T kh[K];
 	if constexpr (kIsSelEnds<W>) {
-		const unsigned m = end_mask_long<NARR>(c0 + lane * CPT - K, a.W);
-		e0 = (m >> K) & 1;
-		e1 = (m >> (K + CPT - 1)) & 1;
-		sel_coefs<W, false, K>(kh, e0, e1);
+		const unsigned m = end_mask_long<NARR>(c0 + lane * CPT - HK, a.W);
+		e0 = (m >> HK) & 1;
+		e1 = (m >> (HK + CPT - 1)) & 1;
+		sel_coefs<W, false, HK>(kh, e0, e1);
 	}
 	// row r (any r the sweep meets) is an end of its column: r == 0 or r == H - 1 after reflection (one bounce when tall)
 	[[maybe_unused]] auto row_is_end = [&](int r) {
@@ -398,24 +405,24 @@ static __device__ __forceinline__ void fwd_sweep_tile(const FwdLevelArgs &a, con
 				if constexpr (CPT == 8) {
 #pragma unroll
 					for (int e = 0; e < 4; e++)
-						x[K + 4 + e] = from_bits<T>(O1[e]);
+						x[HK + 4 + e] = from_bits<T>(O1[e]);
 				}
 			} else if constexpr (CPT == 8) {
 				lds_read4(la, own, ra, L4, O0, O1, R4);
 #pragma unroll
 				for (int e = 0; e < 4; e++)
-					x[K + 4 + e] = from_bits<T>(O1[e]);
+					x[HK + 4 + e] = from_bits<T>(O1[e]);
 			} else {
 				lds_read3(la, own, ra, L4, O0, R4);
 			}
 #pragma unroll
-			for (int e = 0; e < K; e++) {
-				x[e] = from_bits<T>(L4[4 - K + e]);
-				x[K + CPT + e] = from_bits<T>(R4[e]);
+			for (int e = 0; e < HK; e++) {
+				x[e] = from_bits<T>(L4[4 - HK + e]);
+				x[HK + CPT + e] = from_bits<T>(R4[e]);
 			}
 #pragma unroll
 			for (int e = 0; e < 4; e++)
-				x[K + e] = from_bits<T>(O0[e]);
+				x[HK + e] = from_bits<T>(O0[e]);
 			if constexpr (kPairRows) {
 #pragma unroll
 				for (int j = 0; j < NARR; j++)
@@ -433,13 +440,13 @@ static __device__ __forceinline__ void fwd_sweep_tile(const FwdLevelArgs &a, con
 					lift_fwd_regs<W, NARR>(x, hends);
 				}
 			} else if constexpr (kIsSelEnds<W>) {
-				lift_regs_sel<W, NARR, false, K, K + CPT - 1>(x, e0, e1, kh);
+				lift_regs_sel<W, NARR, false, HK, HK + CPT - 1>(x, e0, e1, kh);
 			} else {
 				lift_fwd_regs<W, NARR>(x, 0u);
 			}
 #pragma unroll
 			for (int v = 0; v < CPT; v++)
-				row[rr][v] = W::fwd_scale(v & 1, x[K + v]);
+				row[rr][v] = W::fwd_scale(v & 1, x[HK + v]);
 		}
 
 		if constexpr (kPairRows) {
@@ -454,9 +461,9 @@ static __device__ __forceinline__ void fwd_sweep_tile(const FwdLevelArgs &a, con
 			for (int s_ = 0; s_ < K; s_++) {
 #pragma unroll
 				for (int j = s_ + 1; j <= NARR - 2 - s_; j += 2) {
-					if (j == K)
+					if (j == HK)
 						x2[j] = x2[j] + kh[s_] * ((e0 ? f2{-0.0f, -0.0f} : x2[j - 1]) + x2[j + 1]);
-					else if (j == K + CPT - 1)
+					else if (j == HK + CPT - 1)
 						x2[j] = x2[j] + kh[s_] * (x2[j - 1] + (e1 ? f2{-0.0f, -0.0f} : x2[j + 1]));
 					else
 						x2[j] = x2[j] + W::fk(s_) * (x2[j - 1] + x2[j + 1]);
@@ -465,7 +472,7 @@ static __device__ __forceinline__ void fwd_sweep_tile(const FwdLevelArgs &a, con
 			const float ze = W::fwd_scale(0, 1.0f), zo = W::fwd_scale(1, 1.0f); // (the scale factors themselves)
 #pragma unroll
 			for (int v = 0; v < CPT; v++) {
-				const f2 sc = x2[K + v] * ((v & 1) ? zo : ze);
+				const f2 sc = x2[HK + v] * ((v & 1) ? zo : ze);
 				row[0][v] = sc[0];
 				row[1][v] = sc[1];
 			}
@@ -487,14 +494,20 @@ static __device__ __forceinline__ void fwd_sweep_tile(const FwdLevelArgs &a, con
 		// `ENDS`: the iteration meets a column end -- the steps on that row take the end form
 		auto vertical = [&](auto ends_tag) {
 			constexpr bool ENDS = decltype(ends_tag)::value;
-			if constexpr (kPairRows && !ENDS) {
+			if constexpr (kPairRows && !ENDS && K != 1) { // (one step: the scalar form below keeps the state in registers)
 				vertical_pairs<W, CPT>(row, st, lo, hi);
 				return;
 			}
 #pragma unroll
 			for (int v = 0; v < CPT; v++) {
 				const T ov = row[0][v], ev = row[1][v];
-				if constexpr (K == 4) {
+				if constexpr (K == 1) {
+					// predict only (st[0]: the even row 2q-2, which leaves as it is)
+					const T d1n = fwd_step_at<W>(0, ENDS && vend[0], ov, st[0][v], ev);
+					lo[v] = W::fwd_scale(0, st[0][v]);
+					hi[v] = W::fwd_scale(1, d1n);
+					st[0][v] = ev;
+				} else if constexpr (K == 4) {
 					const T d1n = fwd_step_at<W>(0, ENDS && vend[0], ov, st[0][v], ev);
 					const T s1n = fwd_step_at<W>(1, ENDS && vend[1], st[0][v], st[1][v], d1n);
 					const T d2n = fwd_step_at<W>(2, ENDS && vend[2], st[1][v], st[2][v], s1n);
@@ -537,14 +550,19 @@ static __device__ __forceinline__ void fwd_sweep_tile(const FwdLevelArgs &a, con
 #pragma unroll
 				for (int s_ = 0; s_ < K; s_++)
 					kv[s_] = sel_coef<W, false>(s_, ve[s_]);
-				if constexpr (kPairRows) {
+				if constexpr (kPairRows && K != 1) {
 					vertical_pairs<W, CPT, true>(row, st, lo, hi, ve, kv);
 					return;
 				}
 #pragma unroll
 				for (int v = 0; v < CPT; v++) {
 					const T ov = row[0][v], ev = row[1][v];
-					if constexpr (K == 4) {
+					if constexpr (K == 1) {
+						const T d1n = sel_step<W, false>(0, ve[0], kv[0], ov, st[0][v], ev);
+						lo[v] = W::fwd_scale(0, st[0][v]);
+						hi[v] = W::fwd_scale(1, d1n);
+						st[0][v] = ev;
+					} else if constexpr (K == 4) {
 						const T d1n = sel_step<W, false>(0, ve[0], kv[0], ov, st[0][v], ev);
 						const T s1n = sel_step<W, false>(1, ve[1], kv[1], st[0][v], st[1][v], d1n);
 						const T d2n = sel_step<W, false>(2, ve[2], kv[2], st[1][v], st[2][v], s1n);
@@ -875,6 +893,7 @@ hipError_t launch_fwd_level(Wavelet w, const FwdLevelArgs &a, const SweepTuning 
 	case kCdf97I: return fwd_level_t<Cdf97I>(a, t, s);
 	case kCdf97SFma: return fwd_level_t<Cdf97SFma>(a, t, s);
 	case kCdf53SNew: return a.interleaved ? fwd_level_t<Cdf53SNew>(a, t, s, strip) : hipErrorInvalidValue;
+	case kInterp53S: return a.interleaved ? hipErrorInvalidValue : fwd_level_t<Interp53S>(a, t, s);
 	default: break; // the double-precision drivers run on the line-pass kernels
 	}
 	return hipErrorInvalidValue;

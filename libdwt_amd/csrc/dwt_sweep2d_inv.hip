@@ -237,9 +237,11 @@ static __device__ __forceinline__ void inv_sweep_tile(const InvLevelArgs &a, con
 	// vertical state: per group CG columns when rows are undone first, NARR when columns are
 	// undone first and the horizontal halo must be carried
 	constexpr int NVG = W::kInvColsFirst ? NARR : CG;
-	T st[K][G][NVG];
+	// (a policy of one step keeps two rows as well: the odd row p-1 and the even row p-1 it is lifted from)
+	constexpr int KS = K == 1 ? 2 : K;
+	T st[KS][G][NVG];
 #pragma unroll
-	for (int s = 0; s < K; s++)
+	for (int s = 0; s < KS; s++)
 #pragma unroll
 		for (int gi = 0; gi < G; gi++)
 #pragma unroll
@@ -426,13 +428,15 @@ static __device__ __forceinline__ void inv_sweep_tile(const InvLevelArgs &a, con
 
 		// vertical inverse, streaming.  K == 4: at step p the rows 2p-3 (odd) and
 		// 2p-2 (even) are final; K == 2: rows 2p-1 and 2p.
-		// step s of this iteration acts on row 2p-s: which of them are column ends (wave-uniform; almost never any)
+		// step s of this iteration acts on row 2p-s (a policy of one step: its step 0 on the odd row 2p-1): which of them are
+		// column ends (wave-uniform; almost never any)
+		const int r0 = K == 1 ? 2 * p - 1 : 2 * p;
 		[[maybe_unused]] bool vend[K] = {};
 		[[maybe_unused]] bool v_any = false;
 		if constexpr (W::kEndForms) {
 #pragma unroll
 			for (int s_ = 0; s_ < K; s_++) {
-				vend[s_] = row_is_end(2 * p - s_);
+				vend[s_] = row_is_end(r0 - s_);
 				v_any = !a.plain_ends && (v_any || vend[s_]);
 			}
 		}
@@ -444,7 +448,14 @@ static __device__ __forceinline__ void inv_sweep_tile(const InvLevelArgs &a, con
 #pragma unroll
 			for (int v = 0; v < NVG; v++) {
 				const T s2 = val[0][gi][v], d2 = val[1][gi][v];
-				if constexpr (K == 4) {
+				if constexpr (K == 1) {
+					// st: [0] d[p-1], [1] e[p-1]; the even row p is final as it comes
+					const T on = inv_step_at<W>(0, ENDS && vend[0], st[0][gi][v], st[1][gi][v], s2);      // o[p-1]
+					odd_row[gi][v] = on;
+					even_row[gi][v] = s2;
+					st[0][gi][v] = d2;
+					st[1][gi][v] = s2;
+				} else if constexpr (K == 4) {
 					// st: [0] d2[p-1], [1] s1[p-1], [2] d1[p-2], [3] e[p-2]
 					const T s1n = inv_step_at<W>(0, ENDS && vend[0], s2, st[0][gi][v], d2);               // s1[p]
 					const T d1n = inv_step_at<W>(1, ENDS && vend[1], st[0][gi][v], st[1][gi][v], s1n);    // d1[p-1]
@@ -481,7 +492,7 @@ static __device__ __forceinline__ void inv_sweep_tile(const InvLevelArgs &a, con
 			bool ve[K], any = false;
 #pragma unroll
 			for (int s_ = 0; s_ < K; s_++) {
-				ve[s_] = row_is_end(2 * p - s_);
+				ve[s_] = row_is_end(r0 - s_);
 				any = any || ve[s_];
 			}
 			auto vertical_sel = [&]() {
@@ -494,7 +505,13 @@ static __device__ __forceinline__ void inv_sweep_tile(const InvLevelArgs &a, con
 #pragma unroll
 				for (int v = 0; v < NVG; v++) {
 					const T s2 = val[0][gi][v], d2 = val[1][gi][v];
-					if constexpr (K == 4) {
+					if constexpr (K == 1) {
+						const T on = sel_step<W, true>(0, ve[0], kv[0], st[0][gi][v], st[1][gi][v], s2);
+						odd_row[gi][v] = on;
+						even_row[gi][v] = s2;
+						st[0][gi][v] = d2;
+						st[1][gi][v] = s2;
+					} else if constexpr (K == 4) {
 						const T s1n = sel_step<W, true>(0, ve[0], kv[0], s2, st[0][gi][v], d2);
 						const T d1n = sel_step<W, true>(1, ve[1], kv[1], st[0][gi][v], st[1][gi][v], s1n);
 						const T en = sel_step<W, true>(2, ve[2], kv[2], st[1][gi][v], st[2][gi][v], d1n);
@@ -528,8 +545,8 @@ static __device__ __forceinline__ void inv_sweep_tile(const InvLevelArgs &a, con
 			vertical(std::false_type{});
 		}
 		// output rows and their validity inside this tile
-		const int pe = (K == 4) ? p - 1 : p;     // pair index of even_row
-		const int po = (K == 4) ? p - 2 : p - 1; // pair index of odd_row
+		const int pe = (K == 4) ? p - 1 : p;     // pair index of even_row (K == 1 and 2: the row p)
+		const int po = (K == 4) ? p - 2 : p - 1; // pair index of odd_row (K == 1 and 2: the row p - 1)
 		const bool ve = pe >= A && pe < B && (!X || pe >= kIlKeepTop / 2);
 		const bool vo = po >= A && po < B && (2 * po + 1 < a.H) && (!X || po >= kIlKeepTop / 2);
 		const unsigned row_bytes = (unsigned)(X ? a.W - kIlKeepRight : a.W) * 4;
@@ -745,6 +762,7 @@ hipError_t launch_inv_level(Wavelet w, const InvLevelArgs &a, const SweepTuning 
 	case kCdf53S: return inv_level_t<Cdf53S>(a, t, s);
 	case kCdf97I: return inv_level_t<Cdf97I>(a, t, s);
 	case kCdf97SFma: return inv_level_t<Cdf97SFma>(a, t, s);
+	case kInterp53S: return a.interleaved ? hipErrorInvalidValue : inv_level_t<Interp53S>(a, t, s);
 	default: break;
 	}
 	return hipErrorInvalidValue;

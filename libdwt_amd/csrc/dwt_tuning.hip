@@ -295,9 +295,10 @@ int dwt_hip_tune(int wavelet, int inverse, const void *src, void *dst, size_t ba
 {
 	if (check_inited())
 		return 1;
-	if (wavelet < 0 || wavelet > 5)
+	Wavelet w;
+	if (!wavelet_of(wavelet, &w))
 		return fail("unknown wavelet %d", wavelet);
-	const int es = elem_size((Wavelet)wavelet);
+	const int es = elem_size(w);
 	g_elems_are_32bit = es == 4;
 	if (!src || !dst || batch < 1 || batch > 65535)
 		return fail("dwt_hip_tune: bad argument (batch must be 1..65535)");
@@ -310,7 +311,7 @@ int dwt_hip_tune(int wavelet, int inverse, const void *src, void *dst, size_t ba
 	if (src == dst)
 		return 0; // (the in-place entries stage level 0: nothing of theirs is measured)
 	const Geom ge{size_x, size_y, size_x, size_y};
-	return tune2d((Wavelet)wavelet, inverse != 0, Img{(char *)src, stride_x, es}, Img{(char *)dst, stride_x, es}, ge, levels, batch, (long)batch_stride,
+	return tune2d(w, inverse != 0, Img{(char *)src, stride_x, es}, Img{(char *)dst, stride_x, es}, ge, levels, batch, (long)batch_stride,
 		(long)batch_stride);
 }
 
