@@ -286,6 +286,55 @@ void dwt_util_subband_s(void *ptr, int stride_x, int stride_y, int size_o_big_x,
 void dwt_util_subband_i(void *ptr, int stride_x, int stride_y, int size_o_big_x, int size_o_big_y,
 	int size_i_big_x, int size_i_big_y, int j_max, enum dwt_subbands band,
 	void **dst_ptr, int *dst_size_x, int *dst_size_y);
+
+/* Feature vectors of a transformed image (src/libdwt.h:2875-3309): one float per non-empty detail band of levels
+ * 1 .. j_max-1 (level j_max itself is not visited), HL, LH, HH within a level; dwt_util_count_subbands_s of them.
+ * ptr is host or device memory, fv host memory.  The bands are reduced on the device: sums in double in a fixed
+ * order, rounded once and finished in float; maxnorm, maxidx and med are exact for NaN-free input (med as a value;
+ * NaN inputs are not pinned).  See include/libdwt_hip.h. */
+int dwt_util_count_subbands_s(const void *ptr, int stride_x, int stride_y, int size_o_big_x, int size_o_big_y,
+	int size_i_big_x, int size_i_big_y, int j_max);
+void dwt_util_wps_s(const void *ptr, int stride_x, int stride_y, int size_o_big_x, int size_o_big_y,
+	int size_i_big_x, int size_i_big_y, int j_max, float *fv);
+void dwt_util_maxidx_s(const void *ptr, int stride_x, int stride_y, int size_o_big_x, int size_o_big_y,
+	int size_i_big_x, int size_i_big_y, int j_max, float *fv);
+void dwt_util_mean_s(const void *ptr, int stride_x, int stride_y, int size_o_big_x, int size_o_big_y,
+	int size_i_big_x, int size_i_big_y, int j_max, float *fv);
+void dwt_util_med_s(const void *ptr, int stride_x, int stride_y, int size_o_big_x, int size_o_big_y,
+	int size_i_big_x, int size_i_big_y, int j_max, float *fv);
+void dwt_util_var_s(const void *ptr, int stride_x, int stride_y, int size_o_big_x, int size_o_big_y,
+	int size_i_big_x, int size_i_big_y, int j_max, float *fv);
+void dwt_util_stdev_s(const void *ptr, int stride_x, int stride_y, int size_o_big_x, int size_o_big_y,
+	int size_i_big_x, int size_i_big_y, int j_max, float *fv);
+void dwt_util_skew_s(const void *ptr, int stride_x, int stride_y, int size_o_big_x, int size_o_big_y,
+	int size_i_big_x, int size_i_big_y, int j_max, float *fv);
+void dwt_util_kurt_s(const void *ptr, int stride_x, int stride_y, int size_o_big_x, int size_o_big_y,
+	int size_i_big_x, int size_i_big_y, int j_max, float *fv);
+void dwt_util_maxnorm_s(const void *ptr, int stride_x, int stride_y, int size_o_big_x, int size_o_big_y,
+	int size_i_big_x, int size_i_big_y, int j_max, float *fv);
+void dwt_util_norm_s(const void *ptr, int stride_x, int stride_y, int size_o_big_x, int size_o_big_y,
+	int size_i_big_x, int size_i_big_y, int j_max, float *fv);
+void dwt_util_lpnorm_s(const void *ptr, int stride_x, int stride_y, int size_o_big_x, int size_o_big_y,
+	int size_i_big_x, int size_i_big_y, int j_max, float *fv, float p);
+/* one statistic of one band of size_x x size_y coefficients */
+float dwt_util_band_wps_s(const void *ptr, int stride_x, int stride_y, int size_x, int size_y, int j);
+float dwt_util_band_maxidx_s(const void *ptr, int stride_x, int stride_y, int size_x, int size_y);
+float dwt_util_band_mean_s(const void *ptr, int stride_x, int stride_y, int size_x, int size_y);
+float dwt_util_band_med_s(const void *ptr, int stride_x, int stride_y, int size_x, int size_y);
+float dwt_util_band_var_s(const void *ptr, int stride_x, int stride_y, int size_x, int size_y);
+float dwt_util_band_stdev_s(const void *ptr, int stride_x, int stride_y, int size_x, int size_y);
+float dwt_util_band_skew_s(const void *ptr, int stride_x, int stride_y, int size_x, int size_y);
+float dwt_util_band_kurt_s(const void *ptr, int stride_x, int stride_y, int size_x, int size_y);
+float dwt_util_band_maxnorm_s(const void *ptr, int stride_x, int stride_y, int size_x, int size_y);
+float dwt_util_band_norm_s(const void *ptr, int stride_x, int stride_y, int size_x, int size_y);
+float dwt_util_band_lpnorm_s(const void *ptr, int stride_x, int stride_y, int size_x, int size_y, float p);
+float dwt_util_band_moment_s(const void *ptr, int stride_x, int stride_y, int size_x, int size_y, int n, float c);
+float dwt_util_band_cmoment_s(const void *ptr, int stride_x, int stride_y, int size_x, int size_y, int n);
+float dwt_util_band_smoment_s(const void *ptr, int stride_x, int stride_y, int size_x, int size_y, int n);
+void dwt_util_subband_const_s(const void *ptr, int stride_x, int stride_y, int size_o_big_x, int size_o_big_y,
+	int size_i_big_x, int size_i_big_y, int j_max, enum dwt_subbands band, const void **dst_ptr, int *dst_size_x, int *dst_size_y);
+/* |x| in place, host or device memory */
+void dwt_util_abs_s(void *ptr, int stride_x, int stride_y, int size_x, int size_y);
 float *dwt_util_addr_coeff_s(void *ptr, int y, int x, int stride_x, int stride_y); /* src/libdwt.c:1064 */
 int *dwt_util_addr_coeff_i(void *ptr, int y, int x, int stride_x, int stride_y);
 

@@ -300,6 +300,60 @@ int dwt_hip_memcpy_h2d(void *dev_dst, const void *host_src, size_t bytes);
 int dwt_hip_memcpy_d2h(void *host_dst, const void *dev_src, size_t bytes);
 int dwt_hip_is_device_pointer(const void *p);
 
+/* Per-subband feature statistics of a transformed image (libdwt's dwt_util_wps_s, _maxidx_s, _mean_s, _med_s, _var_s,
+ * _stdev_s, _skew_s, _kurt_s, _maxnorm_s, _lpnorm_s, _norm_s: src/libdwt.h:2875-3309), reduced where the coefficients lie.
+ * The bands are those of dwt_util_subband for levels 1 .. j_max-1 (level j_max itself is not visited, as in the
+ * reference), HL, LH, HH within a level, empty bands skipped: dwt_hip_count_subbands of them.
+ * `fv` receives one block of that many floats per feature of the mask, in enum order.  It lies in the memory space of
+ * `ptr` (both host or both device); device calls are ordered on the context's stream.
+ * Numerics: maxnorm, maxidx and med are the reference's values for every NaN-free input (med as a value: which of +0 /
+ * -0 stands in the middle of equal zeros is unspecified; behaviour on NaN inputs is not pinned, the reference's
+ * qsort comparator being no order there).  Sums accumulate in double in a fixed order -- the same bits on every run
+ * and for every launch geometry -- are rounded to float once and finished on the host in float as the reference
+ * writes it; x - mean is the float subtraction of the float mean.  `p` (> 0, INFINITY allowed) is read by LPNORM only. */
+enum dwt_hip_feature {
+	DWT_HIP_FEATURE_WPS = 0,
+	DWT_HIP_FEATURE_MAXIDX,
+	DWT_HIP_FEATURE_MEAN,
+	DWT_HIP_FEATURE_MED,
+	DWT_HIP_FEATURE_VAR,
+	DWT_HIP_FEATURE_STDEV,
+	DWT_HIP_FEATURE_SKEW,
+	DWT_HIP_FEATURE_KURT,
+	DWT_HIP_FEATURE_MAXNORM,
+	DWT_HIP_FEATURE_LPNORM,
+	DWT_HIP_FEATURE_NORM,
+	DWT_HIP_FEATURE_COUNT
+};
+#define DWT_HIP_FEATURE_BIT(f) (1u << (f))
+/* number of non-empty detail bands of levels 1 .. j_max-1; -1 for bad sizes */
+int dwt_hip_count_subbands(int size_o_x, int size_o_y, int size_i_x, int size_i_y, int j_max);
+int dwt_hip_features2d(unsigned feature_mask, const void *ptr, int stride_x, int stride_y, int size_o_x, int size_o_y,
+	int size_i_x, int size_i_y, int j_max, float p, float *fv);
+/* the same with `fv` in HOST memory wherever `ptr` lies (what libdwt's dwt_util_*_s entries take) */
+int dwt_hip_features2d_hostfv(unsigned feature_mask, const void *ptr, int stride_x, int stride_y, int size_o_x, int size_o_y,
+	int size_i_x, int size_i_y, int j_max, float p, float *fv);
+/* The raw double sums behind the calling thread's last feature call, for checks of the accumulation: plane 0 sum x,
+ * 1 sum x^2, 2 sum |x|^p (p other than 2), 3 .. 5 sum (x - mean)^2, ^3, ^4; one double per (image, band) in call
+ * order.  Returns the number copied (at most n), -1 when the last call's mask did not need that plane. */
+long dwt_hip_features_raw_sums(int plane, double *out, long n);
+/* `batch` dense images batch_stride bytes apart; the vector of image b at fv + b*fv_stride floats */
+int dwt_hip_features2d_batch(unsigned feature_mask, const void *ptr, size_t batch_stride, int batch, int stride_x,
+	int size_x, int size_y, int j_max, float p, float *fv, size_t fv_stride);
+/* n_lines rows of `size` samples (each a frame with size_y = 1), strides in bytes; rows of up to 8192 samples take
+ * ONE kernel launch for every band and every feature */
+int dwt_hip_features1d_batch(unsigned feature_mask, const void *ptr, size_t line_stride, size_t elem_stride, int n_lines,
+	int size, int j_max, float p, float *fv, size_t fv_stride);
+/* one statistic of one band (the dwt_util_band_*_s primitives): size_x x size_y elements at ptr (host or device);
+ * `j` is read by WPS, `p` by LPNORM; *value is host memory */
+int dwt_hip_band_feature(int feature, const void *ptr, int stride_x, int stride_y, int size_x, int size_y, int j, float p,
+	float *value);
+/* sum powf(x - c, n) / size (dwt_util_band_moment_s); central != 0: about the band's float mean (_cmoment_s) */
+int dwt_hip_band_moment(const void *ptr, int stride_x, int stride_y, int size_x, int size_y, int n, int central, float c,
+	float *value);
+/* |x| in place (dwt_util_abs_s): the sign bit cleared, so -0 -> +0 and Inf stays Inf */
+int dwt_hip_abs(void *ptr, int stride_x, int stride_y, int size_x, int size_y);
+
 /* dwt_util_perf_cdf97_2_s's protocol (src/libdwt.c:21444-21476) with the M images
  * resident in HBM: seconds per transform, minimum over N loops. */
 void dwt_hip_perf_cdf97_2_s(int stride_x, int stride_y, int size_o_big_x, int size_o_big_y,

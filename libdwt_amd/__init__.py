@@ -654,6 +654,148 @@ def eaw53_2d_batch(inverse, ptr, batch_stride, batch, stride_x, size_x, size_y, 
     return _eaw_levels(bool(inverse), size_x, size_y, j_max, decompose_one) if batch == 0 else j.value
 
 
+# ---- per-subband feature statistics (include/libdwt_hip.h) ---------------------------------------------
+FEATURE_NAMES = ("wps", "maxidx", "mean", "med", "var", "stdev", "skew", "kurt", "maxnorm", "lpnorm", "norm")
+FEATURE = {name: 1 << i for i, name in enumerate(FEATURE_NAMES)}  # name -> bit of a feature mask (enum dwt_hip_feature)
+_F = C.c_float
+lib.dwt_hip_count_subbands.argtypes = [_I] * 5
+lib.dwt_hip_count_subbands.restype = _I
+lib.dwt_hip_features2d.argtypes = [C.c_uint, _P, _I, _I, _I, _I, _I, _I, _I, _F, _P]
+lib.dwt_hip_features2d.restype = _I
+lib.dwt_hip_features2d_hostfv.argtypes = [C.c_uint, _P, _I, _I, _I, _I, _I, _I, _I, _F, _P]
+lib.dwt_hip_features2d_hostfv.restype = _I
+lib.dwt_hip_features_raw_sums.argtypes = [_I, _P, C.c_long]
+lib.dwt_hip_features_raw_sums.restype = C.c_long
+lib.dwt_hip_features2d_batch.argtypes = [C.c_uint, _P, _S, _I, _I, _I, _I, _I, _F, _P, _S]
+lib.dwt_hip_features2d_batch.restype = _I
+lib.dwt_hip_features1d_batch.argtypes = [C.c_uint, _P, _S, _S, _I, _I, _I, _F, _P, _S]
+lib.dwt_hip_features1d_batch.restype = _I
+lib.dwt_hip_band_feature.argtypes = [_I, _P, _I, _I, _I, _I, _I, _F, C.POINTER(_F)]
+lib.dwt_hip_band_feature.restype = _I
+lib.dwt_hip_band_moment.argtypes = [_P, _I, _I, _I, _I, _I, _I, _F, C.POINTER(_F)]
+lib.dwt_hip_band_moment.restype = _I
+lib.dwt_hip_abs.argtypes = [_P, _I, _I, _I, _I]
+lib.dwt_hip_abs.restype = _I
+
+
+def feature_mask(features):
+    """A feature mask from a mask, a name or an iterable of names of FEATURE."""
+    if isinstance(features, int):
+        return features
+    if isinstance(features, str):
+        features = (features,)
+    return sum({FEATURE[f] for f in features})
+
+
+def count_subbands(size_o_x, size_o_y, size_i_x, size_i_y, j_max):
+    """dwt_util_count_subbands_s: the non-empty detail bands of levels 1 .. j_max-1."""
+    n = lib.dwt_hip_count_subbands(size_o_x, size_o_y, size_i_x, size_i_y, j_max)
+    if n < 0:
+        raise DwtError("dwt_hip_count_subbands: bad sizes")
+    return n
+
+
+def features2d(features, ptr, stride_x, stride_y, size_o_x, size_o_y, size_i_x, size_i_y, j_max, fv, p=2.0):
+    """dwt_hip_features2d: `fv` (in the memory space of `ptr`) receives one block of count_subbands floats per
+    feature of the mask, in FEATURE_NAMES order."""
+    _check(lib.dwt_hip_features2d(feature_mask(features), _addr(ptr), stride_x, stride_y, size_o_x, size_o_y, size_i_x,
+                                  size_i_y, j_max, float(p), _addr(fv)), "dwt_hip_features2d")
+
+
+def features_raw_sums(plane, n):
+    """dwt_hip_features_raw_sums: the raw double sums (plane 0 .. 5) behind this thread's last feature call."""
+    import numpy as np
+
+    out = np.zeros(n, dtype=np.float64)
+    m = lib.dwt_hip_features_raw_sums(plane, out.ctypes.data, n)
+    if m < 0:
+        raise DwtError("dwt_hip_features_raw_sums: plane %d was not part of the last call" % plane)
+    return out[:m]
+
+
+def features2d_batch(features, ptr, batch_stride, batch, stride_x, size_x, size_y, j_max, fv, fv_stride, p=2.0):
+    """dwt_hip_features2d_batch: image b's vector at fv + b * fv_stride floats."""
+    _check(lib.dwt_hip_features2d_batch(feature_mask(features), _addr(ptr), batch_stride, batch, stride_x, size_x, size_y,
+                                        j_max, float(p), _addr(fv), fv_stride), "dwt_hip_features2d_batch")
+
+
+def features1d_batch(features, ptr, line_stride, elem_stride, n_lines, size, j_max, fv, fv_stride, p=2.0):
+    """dwt_hip_features1d_batch: every row a frame with size_y = 1; rows of up to 8192 samples take one launch."""
+    _check(lib.dwt_hip_features1d_batch(feature_mask(features), _addr(ptr), line_stride, elem_stride, n_lines, size,
+                                        j_max, float(p), _addr(fv), fv_stride), "dwt_hip_features1d_batch")
+
+
+def dwt_util_count_subbands_s(ptr, stride_x, stride_y, size_o_x, size_o_y, size_i_x, size_i_y, j_max):
+    return count_subbands(size_o_x, size_o_y, size_i_x, size_i_y, j_max)
+
+
+def _vector_entry(name):
+    fn = getattr(lib, "dwt_util_%s_s" % name)
+    fn.argtypes = [_P, _I, _I, _I, _I, _I, _I, _I, _P] + ([_F] if name == "lpnorm" else [])
+    fn.restype = None
+
+    def entry(ptr, stride_x, stride_y, size_o_x, size_o_y, size_i_x, size_i_y, j_max, fv=None, *p):
+        """libdwt's prototype; `fv` is a host float32 array (made and returned when None)."""
+        import numpy as np
+
+        if fv is None:
+            fv = np.zeros(count_subbands(size_o_x, size_o_y, size_i_x, size_i_y, j_max), dtype=np.float32)
+        if not lib.dwt_hip_is_device_pointer(_addr(ptr)) and lib.dwt_hip_init():
+            raise DwtError(lib.dwt_hip_last_error().decode())  # (the C entry would abort)
+        fn(_addr(ptr), stride_x, stride_y, size_o_x, size_o_y, size_i_x, size_i_y, j_max, fv.ctypes.data, *[float(q) for q in p])
+        return fv
+
+    entry.__name__ = "dwt_util_%s_s" % name
+    return entry
+
+
+for _n in FEATURE_NAMES:
+    globals()["dwt_util_%s_s" % _n] = _vector_entry(_n)
+
+
+def _band_entry(name, extra):
+    fn = getattr(lib, "dwt_util_band_%s_s" % name)
+    fn.argtypes = [_P, _I, _I, _I, _I] + extra
+    fn.restype = _F
+
+    def entry(ptr, stride_x, stride_y, size_x, size_y, *more):
+        if lib.dwt_hip_init():
+            raise DwtError(lib.dwt_hip_last_error().decode())
+        return fn(_addr(ptr), stride_x, stride_y, size_x, size_y, *more)
+
+    entry.__name__ = "dwt_util_band_%s_s" % name
+    return entry
+
+
+for _n in FEATURE_NAMES + ("moment", "cmoment", "smoment"):
+    globals()["dwt_util_band_%s_s" % _n] = _band_entry(
+        _n, {"wps": [_I], "lpnorm": [_F], "moment": [_I, _F], "cmoment": [_I], "smoment": [_I]}.get(_n, []))
+
+lib.dwt_util_abs_s.argtypes = [_P, _I, _I, _I, _I]
+lib.dwt_util_abs_s.restype = None
+lib.dwt_util_subband_const_s.argtypes = [_P, _I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(_P), C.POINTER(_I), C.POINTER(_I)]
+lib.dwt_util_subband_const_s.restype = None
+
+
+def dwt_hip_abs(ptr, stride_x, stride_y, size_x, size_y):
+    """|x| in place, host or device memory."""
+    _check(lib.dwt_hip_abs(_addr(ptr), stride_x, stride_y, size_x, size_y), "dwt_hip_abs")
+
+
+def dwt_util_abs_s(ptr, stride_x, stride_y, size_x, size_y):
+    if lib.dwt_hip_init():
+        raise DwtError(lib.dwt_hip_last_error().decode())
+    lib.dwt_util_abs_s(_addr(ptr), stride_x, stride_y, size_x, size_y)
+
+
+def dwt_util_subband_const_s(ptr, stride_x, stride_y, size_o_x, size_o_y, size_i_x, size_i_y, j_max, band):
+    """(address, size_x, size_y) of a subband."""
+    q, sx, sy = _P(), _I(), _I()
+    lib.dwt_util_subband_const_s(_addr(ptr), stride_x, stride_y, size_o_x, size_o_y, size_i_x, size_i_y, j_max, band,
+                                 C.byref(q), C.byref(sx), C.byref(sy))
+    return q.value, sx.value, sy.value
+
+
 # ---- batches resident in HBM -----------------------------------------------------------
 def transform2d_batch(wavelet, inverse, src, dst, batch_stride, batch, stride_x, size_x, size_y, j_max=-1):
     j = _I(j_max)

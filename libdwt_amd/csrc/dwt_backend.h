@@ -50,6 +50,9 @@ struct Ctx {
 	void *eaw_w = nullptr, *eaw_ll[2] = {nullptr, nullptr}; // EAW: device weights of a host-pointer call, LL ping-pong of the fused levels
 	size_t eaw_w_bytes = 0, eaw_ll_bytes[2] = {0, 0};
 	size_t pin_bytes = 0;
+	void *feat_ws = nullptr; // feature statistics: records, slab partials, band table, select histograms (dwt_backend_features.hip)
+	size_t feat_ws_bytes = 0;
+	int feat_groups = 0; // workgroups of the feature slab passes (0: the launcher's rule); results do not depend on it
 	// options
 	SweepTuning tune;
 	VolTuning vol;

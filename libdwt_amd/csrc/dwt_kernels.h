@@ -297,6 +297,56 @@ hipError_t launch_copy_rects(CopyRects r, hipStream_t s);
 int copy_rects_plan(CopyRects *r);
 hipError_t launch_copy_rects_range(CopyRects r, int lo, int hi, hipStream_t s);
 
+// Per-subband feature statistics (dwt_features.hip).  Every kernel leaves RAW results per (image, band)
+// record in planes of 8 bytes (plane f of record r at rec[f * nrec + r]): sums as doubles, accumulated in a fixed order
+// that depends on the band geometry alone, never on the launch geometry; the host finishes them in float.
+enum FeatPlane { kFeatS1, kFeatS2, kFeatSp, kFeatM2, kFeatM3, kFeatM4, kFeatKey /* max |x| bits << 32 | ~first index */, kFeatMed /* float bits */, kFeatPlanes };
+enum FeatWork { kFeatPass2 = 1, kFeatSelect = 2 };
+// how the kernels form the term of plane kFeatSp: nothing, |x|, or (float)pow((double)|x|, (double)p)
+enum FeatPmode { kFeatPNone, kFeatPAbs, kFeatPPow };
+// one band of an image, cut into slabs of <= cw columns x rh rows (column chunk fastest); slab0: its first slab within the image
+struct FeatBand {
+	int x0, y0, w, h;
+	int cw, rh, ncc, nslab, slab0;
+};
+constexpr int FEAT_MAX_BANDS = 96;
+constexpr int FEAT_SLAB = 16384, FEAT_SLAB_COLS = 4096; // elements per slab, widest slab
+struct FeatLineArgs {
+	const char *src;
+	long line_stride; // bytes
+	int n_lines, N, nb;
+	int off[32], len[32]; // band k of a line: samples off[k] .. off[k] + len[k]
+	unsigned long long *rec;
+	long nrec;
+	int work, pmode;
+	float p;
+};
+// dense lines of N <= N1D_MAX floats, one workgroup per line, every band and every statistic in ONE launch
+hipError_t launch_feat_lines(const FeatLineArgs &a, hipStream_t s);
+struct FeatImgArgs {
+	const char *img;
+	long pitch, bstride; // bytes
+	int batch, nb, slabs; // bands and slabs of ONE image
+	const FeatBand *bands; // device table
+	unsigned long long *part; // 4 planes of batch * slabs partials
+	unsigned long long *rec;
+	long nrec;
+	unsigned *hist; // 4 passes x nrec x 256 bins, zeroed by the caller
+	unsigned *sel;  // nrec x {prefix, rank}
+	int pmode;
+	float p;
+	int use_c, mn; // pass 2 about c instead of the band's mean; mn outside 2..4: plane kFeatM2 takes (float)pow(x - c, mn)
+	float c;
+	int groups; // workgroups of the slab passes
+};
+hipError_t launch_feat_pass1(const FeatImgArgs &a, hipStream_t s); // -> part planes 0..3
+hipError_t launch_feat_pass2(const FeatImgArgs &a, hipStream_t s); // -> part planes 0..2
+hipError_t launch_feat_fold(const FeatImgArgs &a, int second, hipStream_t s); // part -> rec (first: S1 S2 Sp Key; second: M2 M3 M4)
+hipError_t launch_feat_hist(const FeatImgArgs &a, int pass, hipStream_t s);
+hipError_t launch_feat_pick(const FeatImgArgs &a, int pass, hipStream_t s);
+// |x| in place over w x h floats, element (y, x) at y*sx + x*sy bytes
+hipError_t launch_feat_abs(void *p, long sx, long sy, int w, int h, hipStream_t s);
+
 // the strided gather / scatter (dwt_util_memcpy_stride_s / _i, src/system.c:102-164) on the device: w x h elements of
 // `es` bytes between a dense image (row pitch `pitch`) and one whose element (y, x) lies at y*sx + x*sy; all in BYTES
 hipError_t launch_strided_pack(void *dense, long pitch, const void *strided, long sx, long sy, int es, int w, int h, hipStream_t st);
