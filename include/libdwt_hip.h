@@ -354,6 +354,30 @@ int dwt_hip_band_moment(const void *ptr, int stride_x, int stride_y, int size_x,
 /* |x| in place (dwt_util_abs_s): the sign bit cleared, so -0 -> +0 and Inf stays Inf */
 int dwt_hip_abs(void *ptr, int stride_x, int stride_y, int size_x, int size_y);
 
+/* The stationary (undecimated) wavelet transform of rows: swt_cdf97_f_ex_stride_s / swt_cdf53_f_ex_stride_s (src/swt.c),
+ * every level of a batch of lines in one call.  Level l (0-based) filters the low-pass plane of level
+ * l-1 (level 0: the input) with the low-pass and the high-pass filter dilated by 1 << l, borders replicated; every plane
+ * has N samples.  `wavelet` is DWT_HIP_CDF97_S or DWT_HIP_CDF53_S.  `levels` runs from 0 (nothing is written) to
+ * DWT_HIP_SWT_MAX_LEVELS; dilations beyond N are legal.  Lines are line_stride bytes apart, their elements elem_stride.
+ * H of level l of line y goes to dst_h + l*plane_stride + y*dst_line_stride (bytes), dense in x.  l_mode 0: no L is
+ * written (dst_l may be NULL); 1: only the last level's L, to plane 0 of dst_l; 2: every level's L, laid out like H.
+ * All pointers are host memory or all device memory.  src is never written; src, dst_h and dst_l must not overlap (an
+ * error).  Device lines of dense elements and up to 8192 samples take ONE kernel launch whatever `levels` and n_lines;
+ * longer lines and strided elements one launch per level.  Output is bit-identical to the reference's over the whole
+ * float range. */
+#define DWT_HIP_SWT_MAX_LEVELS 24
+int dwt_hip_swt1d_batch(int wavelet, const void *src, size_t line_stride, size_t elem_stride, int n_lines, int N, int levels,
+	void *dst_h, void *dst_l, int l_mode, size_t plane_stride, size_t dst_line_stride);
+/* ONE level at dilation 1 << level of one line, as the reference's entry takes it (include/swt.h): src, dst_l and dst_h
+ * have N elements `stride` bytes apart; level 0 .. DWT_HIP_SWT_MAX_LEVELS-1 */
+int dwt_hip_swt1d_level(int wavelet, const void *src, void *dst_l, void *dst_h, int N, int stride, int level);
+/* The feature statistics of the transform's planes without the planes: feature k of the mask (enum order) of level l of
+ * line y at fv[y*fv_line_stride + k*levels + l] (floats).  band 0: the H planes, 1: the L planes.  Each value is what
+ * dwt_util_band_<name>_s(plane, 0, sizeof(float), N, 1[, p]) gives for that plane, wps with j = l.  fv lies where src
+ * lies (host or device).  Lines the one-launch kernel takes are reduced in that launch and no coefficient is stored. */
+int dwt_hip_swt_features1d_batch(int wavelet, unsigned feature_mask, const void *src, size_t line_stride, size_t elem_stride,
+	int n_lines, int N, int levels, int band, float p, float *fv, int fv_line_stride);
+
 /* dwt_util_perf_cdf97_2_s's protocol (src/libdwt.c:21444-21476) with the M images
  * resident in HBM: seconds per transform, minimum over N loops. */
 void dwt_hip_perf_cdf97_2_s(int stride_x, int stride_y, int size_o_big_x, int size_o_big_y,

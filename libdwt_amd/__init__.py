@@ -796,6 +796,74 @@ def dwt_util_subband_const_s(ptr, stride_x, stride_y, size_o_x, size_o_y, size_i
     return q.value, sx.value, sy.value
 
 
+# ---- stationary wavelet transform of rows (include/libdwt_hip.h, include/swt.h) -------------------------
+SWT_MAX_LEVELS = 24
+lib.dwt_hip_swt1d_batch.argtypes = [_I, _P, _S, _S, _I, _I, _I, _P, _P, _I, _S, _S]
+lib.dwt_hip_swt1d_batch.restype = _I
+lib.dwt_hip_swt1d_level.argtypes = [_I, _P, _P, _P, _I, _I, _I]
+lib.dwt_hip_swt1d_level.restype = _I
+lib.dwt_hip_swt_features1d_batch.argtypes = [_I, C.c_uint, _P, _S, _S, _I, _I, _I, _I, _F, _P, _I]
+lib.dwt_hip_swt_features1d_batch.restype = _I
+
+
+def _swt_wavelet(wavelet):
+    w = WAVELET_ID.get(wavelet, wavelet) if isinstance(wavelet, str) else wavelet
+    if w not in (CDF97_S, CDF53_S):
+        raise DwtError("the SWT takes cdf97_s or cdf53_s (got %r)" % (wavelet,))
+    return w
+
+
+def _swt_sizes(n_lines, size, levels, who):
+    if n_lines < 0 or size < 0 or levels < 0 or levels > SWT_MAX_LEVELS:
+        raise DwtError("%s: bad arguments (%d lines of %d samples, %d levels of at most %d)"
+                       % (who, n_lines, size, levels, SWT_MAX_LEVELS))
+
+
+def swt1d_batch(wavelet, src, line_stride, elem_stride, n_lines, size, levels, dst_h, dst_l=None, l_mode=0, plane_stride=0,
+                dst_line_stride=0):
+    """dwt_hip_swt1d_batch: every level of the stationary transform of n_lines rows.  H of level l of row y at
+    dst_h + l*plane_stride + y*dst_line_stride bytes; l_mode 0: no L, 1: the last level's at dst_l, 2: every level's
+    laid out like H.  Rows of up to 8192 dense samples take one launch."""
+    w = _swt_wavelet(wavelet)
+    _swt_sizes(n_lines, size, levels, "swt1d_batch")
+    if l_mode not in (0, 1, 2):
+        raise DwtError("swt1d_batch: l_mode %r" % (l_mode,))
+    if l_mode and dst_l is None:
+        raise DwtError("swt1d_batch: l_mode %d needs dst_l" % l_mode)
+    _check(lib.dwt_hip_swt1d_batch(w, _addr(src), line_stride, elem_stride, n_lines, size, levels, _addr(dst_h),
+                                   0 if dst_l is None else _addr(dst_l), l_mode, plane_stride, dst_line_stride),
+           "dwt_hip_swt1d_batch")
+
+
+def swt_features1d_batch(wavelet, features, src, line_stride, elem_stride, n_lines, size, levels, fv, fv_line_stride, band=0,
+                         p=2.0):
+    """dwt_hip_swt_features1d_batch: feature k of the mask of level l of row y at fv[y*fv_line_stride + k*levels + l];
+    band 0: the H planes, 1: the L planes.  No coefficient is stored for rows of up to 8192 dense samples."""
+    w = _swt_wavelet(wavelet)
+    _swt_sizes(n_lines, size, levels, "swt_features1d_batch")
+    if band not in (0, 1):
+        raise DwtError("swt_features1d_batch: band %r" % (band,))
+    _check(lib.dwt_hip_swt_features1d_batch(w, feature_mask(features), _addr(src), line_stride, elem_stride, n_lines, size,
+                                            levels, band, float(p), _addr(fv), fv_line_stride),
+           "dwt_hip_swt_features1d_batch")
+
+
+def _swt_entry(name, wavelet):
+    def entry(src, dst_l, dst_h, size, stride, level):
+        """libdwt's prototype (include/swt.h, an inline wrapper over dwt_hip_swt1d_level as this is): one level at
+        dilation 1 << level of one line, host or device memory."""
+        if size < 0 or stride < 4 or level < 0 or level >= SWT_MAX_LEVELS:
+            raise DwtError("%s: bad arguments (%d samples, stride %d, level %d)" % (name, size, stride, level))
+        _check(lib.dwt_hip_swt1d_level(wavelet, _addr(src), _addr(dst_l), _addr(dst_h), size, stride, level), name)
+
+    entry.__name__ = name
+    return entry
+
+
+swt_cdf97_f_ex_stride_s = _swt_entry("swt_cdf97_f_ex_stride_s", CDF97_S)
+swt_cdf53_f_ex_stride_s = _swt_entry("swt_cdf53_f_ex_stride_s", CDF53_S)
+
+
 # ---- batches resident in HBM -----------------------------------------------------------
 def transform2d_batch(wavelet, inverse, src, dst, batch_stride, batch, stride_x, size_x, size_y, j_max=-1):
     j = _I(j_max)

@@ -17,7 +17,7 @@ struct Opt {
 };
 #define DWT_OPT(name_, member_, kind_) {name_, [](Ctx &c) -> int * { return &c.member_; }, kind_}
 const Opt kOpts[] = {
-	DWT_OPT("generic", force_generic, kSweep), DWT_OPT("eaw_two_pass", eaw_two_pass, kBool), DWT_OPT("feat_groups", feat_groups, kNonNegative), DWT_OPT("cpt", tune.cpt, kSweep), DWT_OPT("tile_pairs", tune.tile_pairs, kSweep),
+	DWT_OPT("generic", force_generic, kSweep), DWT_OPT("eaw_two_pass", eaw_two_pass, kBool), DWT_OPT("feat_groups", feat_groups, kNonNegative), DWT_OPT("swt_fused", swt_fused, kBool), DWT_OPT("cpt", tune.cpt, kSweep), DWT_OPT("tile_pairs", tune.tile_pairs, kSweep),
 	DWT_OPT("waves", tune.waves, kSweep), DWT_OPT("xcd_swizzle", tune.xcd_swizzle, kSweep), DWT_OPT("ring", tune.ring, kSweep),
 	DWT_OPT("ring_inv", tune.ring_inv, kSweep), DWT_OPT("inv_ll_temporal", tune.inv_ll_temporal, kSweep), DWT_OPT("inv_pairs", tune.inv_pairs, kSweep), DWT_OPT("nt", tune.nt, kSweep), DWT_OPT("nt_auto", tune.nt_auto, kSweep),
 	DWT_OPT("fma", fma, kSweep), DWT_OPT("fused_d", fused_d, kPlain), DWT_OPT("ride_copy", ride_copy, kBool), DWT_OPT("ride_mib", ride_mib, kNonNegative), DWT_OPT("il_exact_borders", il_exact_borders, kPlain),
@@ -108,7 +108,7 @@ void dwt_hip_finish(void)
 		g.ll[0] = g.ll[1] = nullptr;
 		g.ll_external = false;
 	}
-	void **bufs[] = {&g.stage_img, &g.ll[0], &g.ll[1], &g.host_a, &g.host_b, &g.vol_out, &g.vol_host[0], &g.vol_host[1], &g.eaw_w, &g.eaw_ll[0], &g.eaw_ll[1], &g.feat_ws};
+	void **bufs[] = {&g.stage_img, &g.ll[0], &g.ll[1], &g.host_a, &g.host_b, &g.vol_out, &g.vol_host[0], &g.vol_host[1], &g.eaw_w, &g.eaw_ll[0], &g.eaw_ll[1], &g.feat_ws, &g.swt_ws};
 	for (void **b : bufs) {
 		if (*b)
 			dev_free(*b);
@@ -117,7 +117,7 @@ void dwt_hip_finish(void)
 	g.stage_bytes = g.ll_bytes[0] = g.ll_bytes[1] = g.host_a_bytes = g.host_b_bytes = g.vol_out_bytes = 0;
 	g.vol_host_bytes[0] = g.vol_host_bytes[1] = 0;
 	g.eaw_w_bytes = g.eaw_ll_bytes[0] = g.eaw_ll_bytes[1] = 0;
-	g.feat_ws_bytes = 0;
+	g.feat_ws_bytes = g.swt_ws_bytes = 0;
 	for (hipEvent_t &e : g.dl_ev) {
 		if (e)
 			hipEventDestroy(e);

@@ -53,6 +53,9 @@ struct Ctx {
 	void *feat_ws = nullptr; // feature statistics: records, slab partials, band table, select histograms (dwt_backend_features.hip)
 	size_t feat_ws_bytes = 0;
 	int feat_groups = 0; // workgroups of the feature slab passes (0: the launcher's rule); results do not depend on it
+	void *swt_ws = nullptr; // SWT level by level: the L chain's two dense images (dwt_backend_swt.hip)
+	size_t swt_ws_bytes = 0;
+	int swt_fused = 1; // SWT lines of up to N1D_MAX samples in one launch (0: one launch per level, the cross-check)
 	// options
 	SweepTuning tune;
 	VolTuning vol;
@@ -186,6 +189,11 @@ int transform1d(Wavelet w, bool inverse, const void *src, void *dst, long line_s
 // 0 done, 1 error, -1 not applicable (the caller takes the plain path)
 int host_forward_pipelined(Wavelet w, const void *src, void *dst, int stride_x, int W, int H, int *jp, int decompose_one);
 int host_inverse_pipelined(Wavelet w, const void *src, void *dst, int stride_x, int W, int H, int j_max, int decompose_one);
+// the stationary wavelet transform of rows (dwt_backend_swt.hip): device memory on every side, H of level l of line y at
+// dst_h + l*plane_stride + y*dls with elements h_es bytes apart, L by l_mode; level l at dilation 1 << (level0 + l)
+bool swt_fused_ok(const void *src, long ls, long es, int N);
+int swt_device(Wavelet w, const char *src, long ls, long es, int n_lines, int N, int level0, int levels, char *dst_h, long h_es,
+	char *dst_l, long l_es, int l_mode, long plane_stride, long dls);
 int prof_drain();
 void prof_before(int level = 0);
 void prof_after(int level = 0);

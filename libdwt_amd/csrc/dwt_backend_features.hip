@@ -137,14 +137,23 @@ int launched(hipError_t e, const char *what)
 	return e == hipSuccess ? 0 : fail("feature %s launch failed: %s", what, hipGetErrorString(e));
 }
 
+// how the kernels form the term of plane kFeatSp
+int pmode_of(unsigned mask, float p)
+{
+	const bool lp = (mask & DWT_HIP_FEATURE_BIT(DWT_HIP_FEATURE_LPNORM)) != 0;
+	return !lp || p == 2.f || p == INFINITY ? kFeatPNone : p == 1.f ? kFeatPAbs : kFeatPPow;
+}
+
+int finish_records(const u64 *rec, long nrec, int batch, const Band *bands, int nb, unsigned mask, int pmode, float p, const Moment &mom,
+	float *fv, long fv_stride);
+
 // `batch` dense device images (4-byte elements, pitch d.sx) bstride bytes apart -> fv (HOST memory): per image one
 // block of nb floats per feature of `mask` in enum order, images fv_stride floats apart.
 int run_device(Img d, long bstride, int batch, const Band *bands, int nb, bool lines, int N, unsigned mask, float p, const Moment &mom,
 	float *fv, long fv_stride)
 {
 	const bool pass2 = (mask & kMomentFeatures) != 0, select = (mask & DWT_HIP_FEATURE_BIT(DWT_HIP_FEATURE_MED)) != 0;
-	const bool lp = (mask & DWT_HIP_FEATURE_BIT(DWT_HIP_FEATURE_LPNORM)) != 0;
-	const int pmode = !lp || p == 2.f || p == INFINITY ? kFeatPNone : p == 1.f ? kFeatPAbs : kFeatPPow;
+	const int pmode = pmode_of(mask, p);
 	const long nrec = (long)batch * nb;
 	Ws ws;
 	if (lines) {
@@ -219,7 +228,14 @@ int run_device(Img d, long bstride, int batch, const Band *bands, int nb, bool l
 					return 1;
 		}
 	}
-	// the raw records cross to the host: only the planes the mask needs
+	return finish_records(ws.rec, nrec, batch, bands, nb, mask, pmode, p, mom, fv, fv_stride);
+}
+
+// The raw records of `batch` x nb bands cross to the host -- only the planes the mask needs -- and are finished into fv.
+int finish_records(const u64 *rec, long nrec, int batch, const Band *bands, int nb, unsigned mask, int pmode, float p, const Moment &mom,
+	float *fv, long fv_stride)
+{
+	const bool pass2 = (mask & kMomentFeatures) != 0, select = (mask & DWT_HIP_FEATURE_BIT(DWT_HIP_FEATURE_MED)) != 0;
 	bool need[kFeatPlanes] = {};
 	need[kFeatS1] = mask & DWT_HIP_FEATURE_BIT(DWT_HIP_FEATURE_MEAN);
 	need[kFeatS2] = mask & (DWT_HIP_FEATURE_BIT(DWT_HIP_FEATURE_WPS) | DWT_HIP_FEATURE_BIT(DWT_HIP_FEATURE_NORM) | DWT_HIP_FEATURE_BIT(DWT_HIP_FEATURE_LPNORM));
@@ -237,7 +253,7 @@ int run_device(Img d, long bstride, int batch, const Band *bands, int nb, bool l
 		t_have[f] = need[f];
 	for (int f = 0; f < kFeatPlanes; f++)
 		if (need[f])
-			HIP_TRY(hipMemcpyAsync(host.data() + (size_t)f * nrec, ws.rec + (size_t)f * nrec, (size_t)nrec * 8, hipMemcpyDeviceToHost, g.stream));
+			HIP_TRY(hipMemcpyAsync(host.data() + (size_t)f * nrec, rec + (size_t)f * nrec, (size_t)nrec * 8, hipMemcpyDeviceToHost, g.stream));
 	HIP_TRY(hipStreamSynchronize(g.stream));
 	for (int b = 0; b < batch; b++) {
 		float *out = fv + (long)b * fv_stride;
@@ -338,6 +354,59 @@ int features(unsigned mask, const void *ptr, long bstride, int batch, long strid
 }
 
 bool bad_sizes(int sox, int soy, int six, int siy) { return sox < 0 || soy < 0 || six < 0 || siy < 0 || six > sox || siy > soy; }
+
+// The features of every level's H (band 0) or L (band 1) plane of the stationary transform of `n_lines` dense device
+// lines -> fv (HOST memory), feature k of level l of line y at fv[y*fv_stride + k*levels + l].  Lines the fused kernel
+// takes: ONE launch, no coefficient stored.  Otherwise the planes go level by level to library scratch and each level's
+// planes through run_device -- what dwt_hip_band_feature does with a stored plane.
+int swt_features_device(Wavelet w, unsigned mask, const char *src, long ls, int n_lines, int N, int levels, int band, float p, float *fv,
+	long fv_stride)
+{
+	const int nf = popcount(mask);
+	Band bands[SWT_MAX_LEVELS];
+	for (int l = 0; l < levels; l++)
+		bands[l] = Band{0, 0, N, 1, l}; // (wps divides by 1 << l, as the study calls it)
+	if (swt_fused_ok(src, ls, 4, N)) {
+		const long nrec = (long)n_lines * levels;
+		Ws ws;
+		if (carve(nrec, 0, 0, false, &ws))
+			return 1;
+		SwtLineArgs a{};
+		a.src = src;
+		a.line_stride = ls;
+		a.n_lines = n_lines;
+		a.N = N;
+		a.levels = levels;
+		a.vec = ls % 16 == 0 && (uintptr_t)src % 16 == 0;
+		a.rec = ws.rec;
+		a.nrec = nrec;
+		a.band = band;
+		a.work = ((mask & kMomentFeatures) ? kFeatPass2 : 0) | ((mask & DWT_HIP_FEATURE_BIT(DWT_HIP_FEATURE_MED)) ? kFeatSelect : 0);
+		a.pmode = pmode_of(mask, p);
+		a.p = p;
+		if (launched(launch_swt_lines(w, true, a, g.stream), "SWT line"))
+			return 1;
+		return finish_records(ws.rec, nrec, n_lines, bands, levels, mask, a.pmode, p, Moment{}, fv, fv_stride);
+	}
+	const long pitch = 4l * N, plane = pitch * n_lines;
+	if (grow(&g.host_b, &g.host_b_bytes, (size_t)plane * levels))
+		return 1;
+	char *planes = (char *)g.host_b;
+	if (band ? swt_device(w, src, ls, 4, n_lines, N, 0, levels, nullptr, 4, planes, 4, 2, plane, pitch) // (no H: level passes only)
+	         : swt_device(w, src, ls, 4, n_lines, N, 0, levels, planes, 4, nullptr, 4, 0, plane, pitch))
+		return 1;
+	static thread_local std::vector<float> level_fv;
+	level_fv.resize((size_t)nf * n_lines);
+	for (int l = 0; l < levels; l++) {
+		if (run_device(Img{planes + (size_t)plane * l, pitch, 4}, pitch, n_lines, bands + l, 1, N <= N1D_MAX, N, mask, p, Moment{},
+				level_fv.data(), nf))
+			return 1;
+		for (int y = 0; y < n_lines; y++)
+			for (int k = 0; k < nf; k++)
+				fv[(long)y * fv_stride + (long)k * levels + l] = level_fv[(size_t)y * nf + k];
+	}
+	return 0;
+}
 
 } // namespace
 
@@ -446,6 +515,62 @@ int dwt_hip_features1d_batch(unsigned feature_mask, const void *ptr, size_t line
 	return features(feature_mask, g.host_b, pitch, n_lines, 4l * size, 4, ge, bands, nb, p, Moment{}, fv, (long)fv_stride, true);
 }
 
+int dwt_hip_swt_features1d_batch(int wavelet, unsigned feature_mask, const void *src, size_t line_stride, size_t elem_stride, int n_lines, int N,
+	int levels, int band, float p, float *fv, int fv_line_stride)
+{
+	Wavelet w;
+	if (!wavelet_of(wavelet, &w) || (w != kCdf97S && w != kCdf53S))
+		return fail("the SWT takes DWT_HIP_CDF97_S or DWT_HIP_CDF53_S (got wavelet %d)", wavelet);
+	if (n_lines < 0 || N < 0 || levels < 0 || levels > SWT_MAX_LEVELS || band < 0 || band > 1 || line_stride > (size_t)LONG_MAX / 2 ||
+		elem_stride > INT_MAX || fv_line_stride < 0)
+		return fail("SWT features: bad arguments (%d lines of %d samples, %d levels of at most %d, band %d)", n_lines, N, levels,
+			SWT_MAX_LEVELS, band);
+	if (check_request(feature_mask, src, fv, p))
+		return 1;
+	if (elem_stride < 4 || (n_lines > 1 && line_stride < elem_stride * (size_t)N))
+		return fail("SWT features: lines must be apart (line stride %zu, element stride %zu)", line_stride, elem_stride);
+	const int nf = popcount(feature_mask);
+	if (n_lines > 1 && fv_line_stride < nf * levels)
+		return fail("feature stride %d floats, one line takes %d", fv_line_stride, nf * levels);
+	if (check_inited())
+		return 1;
+	const bool dev = dwt_hip_is_device_pointer(src);
+	if (dev != (bool)dwt_hip_is_device_pointer(fv))
+		return fail("the lines and the feature vector must both be host or both be device memory");
+	if (dev && (elem_stride % 4 || line_stride % 4 || (uintptr_t)src % 4))
+		return fail("device lines take strides and addresses that are multiples of 4 bytes");
+	if (n_lines == 0 || N == 0 || levels == 0)
+		return 0;
+	// dense device lines run where they lie; everything else is packed into the context's dense device image
+	const char *d = (const char *)src;
+	long ls = (long)line_stride;
+	if (!dev || elem_stride != 4) {
+		const long pitch = align_up(4l * N, 256);
+		if (grow(&g.host_a, &g.host_a_bytes, (size_t)pitch * n_lines))
+			return 1;
+		if (dev) {
+			if (launched(launch_strided_pack(g.host_a, pitch, src, (long)line_stride, (long)elem_stride, 4, N, n_lines, g.stream), "strided pack"))
+				return 1;
+		} else if (line_stride > INT_MAX)
+			return fail("host lines take strides below 2 GiB (%zu bytes)", line_stride);
+		else if (host_upload(src, (int)line_stride, (int)elem_stride, 4, N, n_lines, g.host_a, pitch))
+			return 1;
+		d = (const char *)g.host_a;
+		ls = pitch;
+	}
+	if (!dev)
+		return swt_features_device(w, feature_mask, d, ls, n_lines, N, levels, band, p, fv, fv_line_stride);
+	static thread_local std::vector<float> host_fv;
+	const long block = (long)nf * levels;
+	host_fv.resize((size_t)block * n_lines);
+	if (swt_features_device(w, feature_mask, d, ls, n_lines, N, levels, band, p, host_fv.data(), block))
+		return 1;
+	HIP_TRY(hipMemcpy2DAsync(fv, (size_t)(n_lines > 1 ? fv_line_stride : block) * 4, host_fv.data(), (size_t)block * 4, (size_t)block * 4, n_lines,
+		hipMemcpyHostToDevice, g.stream));
+	HIP_TRY(hipStreamSynchronize(g.stream)); // (host_fv is reused by the next call)
+	return 0;
+}
+
 int dwt_hip_band_feature(int feature, const void *ptr, int stride_x, int stride_y, int size_x, int size_y, int j, float p, float *value)
 {
 	if (feature < 0 || feature >= DWT_HIP_FEATURE_COUNT)
@@ -454,6 +579,8 @@ int dwt_hip_band_feature(int feature, const void *ptr, int stride_x, int stride_
 		return 1;
 	if (size_x <= 0 || size_y <= 0 || j < 0 || j > 30)
 		return fail("bad band: %d x %d, level %d", size_x, size_y, j);
+	if (size_y == 1)
+		stride_x = stride_y * size_x; // (one row: its stride is never used -- the reference's spectra programs pass 0)
 	const Geom ge{size_x, size_y, size_x, size_y};
 	const Band band{0, 0, size_x, size_y, j};
 	return features(DWT_HIP_FEATURE_BIT(feature), ptr, 0, 1, stride_x, stride_y, ge, &band, 1, p, Moment{}, value, 0, false);
@@ -467,6 +594,8 @@ int dwt_hip_band_moment(const void *ptr, int stride_x, int stride_y, int size_x,
 		return fail("null pointer argument");
 	if (size_x <= 0 || size_y <= 0)
 		return fail("bad band: %d x %d", size_x, size_y);
+	if (size_y == 1)
+		stride_x = stride_y * size_x; // (one row: its stride is never used -- the reference's spectra programs pass 0)
 	const Geom ge{size_x, size_y, size_x, size_y};
 	const Band band{0, 0, size_x, size_y, 0};
 	Moment mom;

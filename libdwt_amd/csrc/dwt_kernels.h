@@ -347,6 +347,38 @@ hipError_t launch_feat_pick(const FeatImgArgs &a, int pass, hipStream_t s);
 // |x| in place over w x h floats, element (y, x) at y*sx + x*sy bytes
 hipError_t launch_feat_abs(void *p, long sx, long sy, int w, int h, hipStream_t s);
 
+// The stationary (undecimated) wavelet transform of rows (dwt_swt1d.hip): level l filters the previous
+// level's low-pass plane with both filters dilated by 1 << (level0 + l), borders replicated; every plane has N samples.
+constexpr int SWT_MAX_LEVELS = 24; // level0 + levels <= 24: (half a filter) << level stays far inside int
+struct SwtLineArgs {
+	const char *src;  // dense lines of N <= N1D_MAX floats
+	long line_stride; // bytes
+	int n_lines, N, level0, levels, vec; // vec: 16-byte loads of the line are aligned
+	// coefficient mode: H of level l of line y at dst_h + l*plane_stride + y*dst_line_stride, dense; L by l_mode (0: none,
+	// 1: the last level's at plane 0, 2: every level's like H)
+	char *dst_h, *dst_l;
+	long plane_stride, dst_line_stride;
+	int l_mode;
+	// feature mode: nothing but the records of (line, level), r = line * levels + l, planes as FeatPlane
+	unsigned long long *rec;
+	long nrec;
+	int band; // 0: the H planes, 1: the L planes
+	int work, pmode;
+	float p;
+};
+// every level of every line in ONE launch, the L chain in LDS
+hipError_t launch_swt_lines(Wavelet w, bool features, const SwtLineArgs &a, hipStream_t s);
+// one level through global memory, one thread per output sample: element i of line y at base + y*ls + i*es (bytes) on
+// every side; out_l, out_l2 and out_h may each be null
+struct SwtLevelArgs {
+	const char *src;
+	long src_ls, src_es;
+	int n_lines, N, level;
+	char *out_l, *out_l2, *out_h;
+	long l_ls, l_es, l2_ls, l2_es, h_ls, h_es;
+};
+hipError_t launch_swt_level(Wavelet w, const SwtLevelArgs &a, hipStream_t s);
+
 // the strided gather / scatter (dwt_util_memcpy_stride_s / _i, src/system.c:102-164) on the device: w x h elements of
 // `es` bytes between a dense image (row pitch `pitch`) and one whose element (y, x) lies at y*sx + x*sy; all in BYTES
 hipError_t launch_strided_pack(void *dense, long pitch, const void *strided, long sx, long sy, int es, int w, int h, hipStream_t st);

@@ -1,0 +1,281 @@
+// dwt_swt1d.hip -- the stationary (undecimated) wavelet transform of a batch of rows, every level in ONE launch (gfx950).
+//
+// The reference (swt_cdf97_f_ex_stride_s / swt_cdf53_f_ex_stride_s, src/swt.c, over dwt_util_convolve1_s, src/util.c:5-48,
+// and the saturating accessors of src/signal.c:43-93) filters a level's input x of N samples twice, with the low-pass
+// and the high-pass filter g of 2c+1 taps dilated by u = 1 << level:
+//
+//     y = 0.0f;  for k = -c .. +c:  y = y + x[clamp(p - u*k, 0, N-1)] * g[k + c];   out[p] = y
+//
+// float32, product and sum rounded separately, from +0.0f, taps from the right neighbour to the left one, borders
+// replicated.  Level l+1 filters the low-pass plane of level l.  Every plane has N samples: J levels turn N samples into
+// 2*J*N coefficients.
+//
+// k_swt_lines: a line of up to N1D_MAX samples is loaded into LDS once; two LDS buffers hold the L chain, ping-ponged.
+// NT threads work on a line (64: four lines per workgroup; 256: one), thread t takes samples t, t + NT, ... -- lanes read
+// consecutive LDS addresses at every dilation -- and reads the 2*CL+1 taps once for both filters (the high-pass taps are
+// a subset).  Coefficient mode stores H (and L where asked) with coalesced 4-byte stores.  Feature mode stores no
+// coefficient: each level's plane is reduced as it is computed into the raw records of dwt_features.hip, with its
+// accumulators and its order (thread t takes samples t, t + NT, ... there too, lanes by a shuffle tree, waves in index
+// order), so the records are bit for bit those of k_feat_lines over the stored plane.  The passes that need the plane
+// again -- the central moments about the mean, the four rounds of the median's radix select -- compute it again from
+// the level's input, which is still in LDS.
+//
+// k_swt_level: one level through global memory, one thread per output sample, any byte strides: lines beyond N1D_MAX,
+// strided elements, and the cross-check of the fused kernel (option "swt_fused" = 0).
+#include "dwt_device.h"
+#include "dwt_kernels.h"
+
+namespace dwt {
+
+namespace {
+
+#include "dwt_feat_acc.h"
+
+// the filters as the reference spells them: decimal literals of type double, rounded to float
+struct Swt97 {
+	static constexpr int CL = 4, CH = 3;
+	static __device__ __forceinline__ float gl(int i)
+	{
+		constexpr float g[9] = {(float)+0.03782846, (float)-0.02384947, (float)-0.11062438, (float)+0.37740287, (float)+0.85269880,
+			(float)+0.37740287, (float)-0.11062438, (float)-0.02384947, (float)+0.03782846};
+		return g[i];
+	}
+	static __device__ __forceinline__ float gh(int i)
+	{
+		constexpr float g[7] = {(float)+0.06453887, (float)-0.04068942, (float)-0.41809219, (float)+0.78848559, (float)-0.41809219,
+			(float)-0.04068942, (float)+0.06453887};
+		return g[i];
+	}
+};
+struct Swt53 {
+	static constexpr int CL = 2, CH = 1;
+	static __device__ __forceinline__ float gl(int i)
+	{
+		constexpr float g[5] = {(float)-0.17677669, (float)+0.35355338, (float)+1.06066012, (float)+0.35355338, (float)-0.17677669};
+		return g[i];
+	}
+	static __device__ __forceinline__ float gh(int i)
+	{
+		constexpr float g[3] = {(float)-0.35355338, (float)+0.70710677, (float)-0.35355338};
+		return g[i];
+	}
+};
+
+// both outputs at sample p from one read of the taps: x(i) gives input sample i, 0 <= i < n
+template <class F, class I, class X>
+static __device__ __forceinline__ void swt_point(X x, I p, I u, I n, float *lo, float *hi)
+{
+	constexpr int CL = F::CL, CH = F::CH;
+	float v[2 * CL + 1];
+#pragma unroll
+	for (int k = -CL; k <= CL; k++) {
+		I i = p - u * k;
+		i = i < 0 ? 0 : i;
+		i = i > n - 1 ? n - 1 : i;
+		v[k + CL] = x(i);
+	}
+	// The sums start from +0.0f and that first addition counts: 0.0f + (-0.0f) is +0.0f.  The compiler drops an addition
+	// to a literal zero on this target, so the zero passes through an empty asm and stays a value it cannot see.
+	float zero = 0.0f;
+	asm("" : "+v"(zero));
+	float l = zero, h = zero;
+#pragma unroll
+	for (int k = -CL; k <= CL; k++)
+		l = l + v[k + CL] * F::gl(k + CL);
+#pragma unroll
+	for (int k = -CH; k <= CH; k++)
+		h = h + v[k + CL] * F::gh(k + CH);
+	*lo = l;
+	*hi = h;
+}
+
+template <class F, bool FEAT, int NT, int CAP>
+__global__ __launch_bounds__(256) void k_swt_lines(SwtLineArgs a)
+{
+	constexpr int LPW = 256 / NT, NW = NT / 64;
+	__shared__ float buf[LPW][2][CAP];
+	__shared__ double shd[4];
+	__shared__ u64 shk[4];
+	__shared__ unsigned hist[FEAT ? LPW : 1][256];
+	__shared__ unsigned sel[LPW][2];
+	const int sub = threadIdx.x / NT, t = threadIdx.x % NT, N = a.N;
+	const long line_raw = (long)blockIdx.x * LPW + sub;
+	// (a workgroup's spare lines follow the last line through every barrier and write nothing)
+	const bool active = line_raw < a.n_lines;
+	const long line = active ? line_raw : a.n_lines - 1;
+	const char *s = a.src + line * a.line_stride;
+	float *cur = buf[sub][0], *nxt = buf[sub][1];
+
+	if (a.vec) {
+		const int n4 = N >> 2;
+		for (int i = t; i < n4; i += NT)
+			*(float4 *)(cur + 4 * i) = *(const float4 *)(s + 16l * i);
+		for (int i = 4 * n4 + t; i < N; i += NT)
+			cur[i] = *(const float *)(s + 4l * i);
+	} else {
+		for (int i = t; i < N; i += NT)
+			cur[i] = *(const float *)(s + 4l * i);
+	}
+
+	for (int l = 0; l < a.levels; l++) {
+		__syncthreads();
+		const int u = 1 << (a.level0 + l);
+		const float *const in = cur;
+		auto x = [&](int i) { return in[i]; };
+		if constexpr (!FEAT) {
+			float *const h_out = (float *)(a.dst_h + (long)l * a.plane_stride + line * a.dst_line_stride);
+			float *const l_out = a.l_mode == 2                       ? (float *)(a.dst_l + (long)l * a.plane_stride + line * a.dst_line_stride)
+			                     : a.l_mode == 1 && l == a.levels - 1 ? (float *)(a.dst_l + line * a.dst_line_stride)
+			                                                          : nullptr;
+			for (int p = t; p < N; p += NT) {
+				float lo, hi;
+				swt_point<F, int>(x, p, u, N, &lo, &hi);
+				nxt[p] = lo;
+				if (active) {
+					h_out[p] = hi;
+					if (l_out)
+						l_out[p] = lo;
+				}
+			}
+		} else {
+			// the plane this level is reduced over, sample by sample: L was just written to nxt by this same thread
+			float *const out = nxt;
+			const int band = a.band;
+			auto val = [&](int p) {
+				if (band)
+					return out[p];
+				float lo, hi;
+				swt_point<F, int>(x, p, u, N, &lo, &hi);
+				return hi;
+			};
+			const long r = line * a.levels + l;
+			Acc1 acc;
+			for (int p = t; p < N; p += NT) {
+				float lo, hi;
+				swt_point<F, int>(x, p, u, N, &lo, &hi);
+				nxt[p] = lo;
+				acc.add(band ? lo : hi, (unsigned)p, a.pmode, a.p);
+			}
+			const double s1 = wg_sum<NW>(acc.s1, shd), s2 = wg_sum<NW>(acc.s2, shd);
+			const double sp = a.pmode != kFeatPNone ? wg_sum<NW>(acc.sp, shd) : 0.0;
+			const u64 key = wg_max<NW>(acc.key, shk);
+			if (t == 0 && active) {
+				a.rec[kFeatS1 * a.nrec + r] = dbits(s1);
+				a.rec[kFeatS2 * a.nrec + r] = dbits(s2);
+				a.rec[kFeatSp * a.nrec + r] = dbits(sp);
+				a.rec[kFeatKey * a.nrec + r] = key;
+			}
+			if (a.work & kFeatPass2) {
+				const float c = mean_of(s1, N);
+				Acc2 m;
+				for (int p = t; p < N; p += NT)
+					m.add(val(p), c, 2);
+				const double m2 = wg_sum<NW>(m.m2, shd), m3 = wg_sum<NW>(m.m3, shd), m4 = wg_sum<NW>(m.m4, shd);
+				if (t == 0 && active) {
+					a.rec[kFeatM2 * a.nrec + r] = dbits(m2);
+					a.rec[kFeatM3 * a.nrec + r] = dbits(m3);
+					a.rec[kFeatM4 * a.nrec + r] = dbits(m4);
+				}
+			}
+			if (a.work & kFeatSelect) {
+				unsigned prefix = 0, rank = (unsigned)N / 2;
+				for (int pass = 0; pass < 4; pass++) {
+					const int shift = 24 - 8 * pass;
+					for (int i = t; i < 256; i += NT)
+						hist[sub][i] = 0;
+					__syncthreads();
+					for (int p = t; p < N; p += NT) {
+						const unsigned q = okey(val(p));
+						if (pass == 0 || (q >> (shift + 8)) == prefix)
+							atomicAdd(&hist[sub][(q >> shift) & 255], 1u);
+					}
+					__syncthreads();
+					if (t < 64) {
+						unsigned kk = rank;
+						const unsigned bin = pick_bin(hist[sub], &kk);
+						if (t == 0) {
+							sel[sub][0] = bin;
+							sel[sub][1] = kk;
+						}
+					}
+					__syncthreads();
+					prefix = (prefix << 8) | sel[sub][0];
+					rank = sel[sub][1];
+					__syncthreads();
+				}
+				if (t == 0 && active)
+					a.rec[kFeatMed * a.nrec + r] = to_bits(okey_inv(prefix));
+			}
+		}
+		float *const q = cur;
+		cur = nxt;
+		nxt = q;
+	}
+}
+
+template <class F>
+__global__ __launch_bounds__(256) void k_swt_level(SwtLevelArgs a)
+{
+	const long p = (long)blockIdx.x * 256 + threadIdx.x, N = a.N, u = 1l << a.level;
+	if (p >= N)
+		return;
+	for (long y = blockIdx.y; y < a.n_lines; y += gridDim.y) {
+		const char *s = a.src + y * a.src_ls;
+		const long es = a.src_es;
+		float lo, hi;
+		swt_point<F, long>([&](long i) { return *(const float *)(s + i * es); }, p, u, N, &lo, &hi);
+		if (a.out_l)
+			*(float *)(a.out_l + y * a.l_ls + p * a.l_es) = lo;
+		if (a.out_l2)
+			*(float *)(a.out_l2 + y * a.l2_ls + p * a.l2_es) = lo;
+		if (a.out_h)
+			*(float *)(a.out_h + y * a.h_ls + p * a.h_es) = hi;
+	}
+}
+
+template <class F, bool FEAT>
+hipError_t swt_lines_t(const SwtLineArgs &a, hipStream_t s)
+{
+	// threads per line and LDS capacity: as k_feat_lines splits (64 threads up to 1024 samples), which fixes the order
+	// of the feature sums; 32 KiB of LDS per workgroup up to 4096 samples, 64 KiB up to N1D_MAX
+	if (a.N <= 1024)
+		k_swt_lines<F, FEAT, 64, 1024><<<(unsigned)((a.n_lines + 3l) / 4), 256, 0, s>>>(a);
+	else if (a.N <= 4096)
+		k_swt_lines<F, FEAT, 256, 4096><<<a.n_lines, 256, 0, s>>>(a);
+	else
+		k_swt_lines<F, FEAT, 256, N1D_MAX><<<a.n_lines, 256, 0, s>>>(a);
+	return hipGetLastError();
+}
+
+} // namespace
+
+hipError_t launch_swt_lines(Wavelet w, bool features, const SwtLineArgs &a, hipStream_t s)
+{
+	if (a.n_lines <= 0 || a.levels <= 0)
+		return hipSuccess;
+	if (a.N < 1 || a.N > N1D_MAX || a.level0 < 0 || a.level0 + a.levels > SWT_MAX_LEVELS)
+		return hipErrorInvalidValue;
+	if (w == kCdf97S)
+		return features ? swt_lines_t<Swt97, true>(a, s) : swt_lines_t<Swt97, false>(a, s);
+	if (w == kCdf53S)
+		return features ? swt_lines_t<Swt53, true>(a, s) : swt_lines_t<Swt53, false>(a, s);
+	return hipErrorInvalidValue;
+}
+
+hipError_t launch_swt_level(Wavelet w, const SwtLevelArgs &a, hipStream_t s)
+{
+	if (a.n_lines <= 0 || a.N <= 0)
+		return hipSuccess;
+	if (a.level < 0 || a.level >= SWT_MAX_LEVELS)
+		return hipErrorInvalidValue;
+	const dim3 grid((unsigned)((a.N + 255l) / 256), (unsigned)(a.n_lines < 65535 ? a.n_lines : 65535));
+	if (w == kCdf97S)
+		k_swt_level<Swt97><<<grid, 256, 0, s>>>(a);
+	else if (w == kCdf53S)
+		k_swt_level<Swt53><<<grid, 256, 0, s>>>(a);
+	else
+		return hipErrorInvalidValue;
+	return hipGetLastError();
+}
+
+} // namespace dwt
