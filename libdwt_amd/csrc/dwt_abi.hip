@@ -104,20 +104,12 @@ void dwt_hip_finish(void)
 	if (!g.inited)
 		return;
 	hipStreamSynchronize(g.stream);
-	if (g.ll_external) {
-		g.ll[0] = g.ll[1] = nullptr;
+	if (g.ll_external) { // the caller's: forgotten, not freed
+		g.ll[0] = g.ll[1] = Buf{};
 		g.ll_external = false;
 	}
-	void **bufs[] = {&g.stage_img, &g.ll[0], &g.ll[1], &g.host_a, &g.host_b, &g.vol_out, &g.vol_host[0], &g.vol_host[1], &g.eaw_w, &g.eaw_ll[0], &g.eaw_ll[1], &g.feat_ws, &g.swt_ws};
-	for (void **b : bufs) {
-		if (*b)
-			dev_free(*b);
-		*b = nullptr;
-	}
-	g.stage_bytes = g.ll_bytes[0] = g.ll_bytes[1] = g.host_a_bytes = g.host_b_bytes = g.vol_out_bytes = 0;
-	g.vol_host_bytes[0] = g.vol_host_bytes[1] = 0;
-	g.eaw_w_bytes = g.eaw_ll_bytes[0] = g.eaw_ll_bytes[1] = 0;
-	g.feat_ws_bytes = g.swt_ws_bytes = 0;
+	for (Buf *b : g.bufs())
+		drop(*b);
 	for (hipEvent_t &e : g.dl_ev) {
 		if (e)
 			hipEventDestroy(e);
@@ -186,25 +178,18 @@ int dwt_hip_set_workspace(void *band0, size_t bytes0, void *band1, size_t bytes1
 		return 1;
 	HIP_TRY(hipStreamSynchronize(g.stream));
 	if (!g.ll_external) {
-		for (int k = 0; k < 2; k++) {
-			if (g.ll[k])
-				dev_free(g.ll[k]); // (may be a range of a placement arena: dwt_hip_alloc_batch)
-			g.ll[k] = nullptr;
-			g.ll_bytes[k] = 0;
-		}
+		drop(g.ll[0]); // (may be a range of a placement arena: dwt_hip_alloc_batch)
+		drop(g.ll[1]);
 	}
 	if (!band0 || !band1) {
-		g.ll[0] = g.ll[1] = nullptr;
-		g.ll_bytes[0] = g.ll_bytes[1] = 0;
+		g.ll[0] = g.ll[1] = Buf{};
 		g.ll_external = false;
 		return 0;
 	}
 	if (!dwt_hip_is_device_pointer(band0) || !dwt_hip_is_device_pointer(band1) || ((uintptr_t)band0 & 15) || ((uintptr_t)band1 & 15))
 		return fail("dwt_hip_set_workspace takes two 16-byte aligned device buffers");
-	g.ll[0] = band0;
-	g.ll[1] = band1;
-	g.ll_bytes[0] = bytes0;
-	g.ll_bytes[1] = bytes1;
+	g.ll[0] = Buf{band0, bytes0};
+	g.ll[1] = Buf{band1, bytes1};
 	g.ll_external = true;
 	return 0;
 }
@@ -401,23 +386,12 @@ int dwt_hip_transform2d(int wavelet, int inverse, const void *src, void *dst, in
 	}
 	const long pitch = align_up((long)sox * es, 256);
 	const size_t bytes = (size_t)pitch * soy;
-	if (grow(&g.host_a, &g.host_a_bytes, bytes) || grow(&g.host_b, &g.host_b_bytes, bytes))
+	if (grow(g.frame_a, bytes) || grow(g.frame_b, bytes))
 		return 1;
 	const bool s2 = (src != dst);
-	auto upload = [&](const void *hp, void *dp) -> int {
-		if (!dev_dst)
-			return host_upload(hp, stride_x, stride_y, es, sox, soy, dp, pitch);
-		const hipError_t e = launch_strided_pack(dp, pitch, hp, stride_x, stride_y, es, sox, soy, g.stream);
-		return e == hipSuccess ? 0 : fail("strided pack launch failed: %s", hipGetErrorString(e));
-	};
-	auto download = [&](void *hp, const void *dp) -> int {
-		if (!dev_dst)
-			return host_download(hp, stride_x, stride_y, es, sox, soy, dp, pitch);
-		const hipError_t e = launch_strided_unpack(hp, stride_x, stride_y, dp, pitch, es, sox, soy, g.stream);
-		return e == hipSuccess ? 0 : fail("strided unpack launch failed: %s", hipGetErrorString(e));
-	};
-	Img A{(char *)g.host_a, pitch, es}, B{(char *)g.host_b, pitch, es};
-	if (upload(src, A.p))
+	const Frame fs{(void *)src, stride_x, stride_y, es, sox, soy, dev_dst}, fd{dst, stride_x, stride_y, es, sox, soy, dev_dst};
+	Img A{(char *)g.frame_a.p, pitch, es}, B{(char *)g.frame_b.p, pitch, es};
+	if (frame_pack(fs, A.p, pitch))
 		return 1;
 	// B receives the result.  It starts as a copy of what the destination holds so
 	// that every element the reference leaves untouched keeps its value -- unless the call
@@ -430,7 +404,7 @@ int dwt_hip_transform2d(int wavelet, int inverse, const void *src, void *dst, in
 	if (s2 && writes_all) {
 		// (nothing to preserve)
 	} else if (s2) {
-		if (upload(dst, B.p))
+		if (frame_pack(fd, B.p, pitch))
 			return 1;
 	} else {
 		if (copy_rect(B, 0, 0, A, 0, 0, sox, soy))
@@ -447,7 +421,7 @@ int dwt_hip_transform2d(int wavelet, int inverse, const void *src, void *dst, in
 	}
 	if (rc)
 		return rc;
-	return download(dst, B.p);
+	return frame_unpack(fd, B.p, pitch);
 }
 
 // ---- 1-D (dwt_backend_1d.hip) ----

@@ -10,6 +10,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <algorithm>
+#include <array>
 #include <condition_variable>
 #include <functional>
 #include <map>
@@ -22,39 +23,48 @@
 namespace dwtb {
 using namespace dwt;
 
+// a device scratch buffer of the context
+struct Buf {
+	void *p = nullptr;
+	size_t bytes = 0;
+};
+
 struct Ctx {
 	bool inited = false;
 	int device = 0;
 	int want_device = -1; // dwt_hip_set_device: the device this thread's context binds to (-1: environment / 0)
 	hipStream_t stream = nullptr;
 	char devname[256] = {0};
-	// workspace
-	void *stage_img = nullptr; // frame-sized staging image (in-place detour, generic passes)
-	size_t stage_bytes = 0;
-	void *ll[2] = {nullptr, nullptr}; // LL ping-pong
-	size_t ll_bytes[2] = {0, 0};
+	// workspace: device scratch, grown on demand (grow), never shrunk, freed by dwt_hip_finish through bufs()
+	Buf stage_img; // frame-sized staging image (in-place detour, generic passes)
+	Buf ll[2];     // LL ping-pong
 	bool ll_external = false; // the caller owns the LL scratch (dwt_hip_set_workspace): never grown, never freed
-	void *host_a = nullptr, *host_b = nullptr; // device images for host-pointer calls
-	size_t host_a_bytes = 0, host_b_bytes = 0;
-	void *vol_out = nullptr; // dense result volume of an in-place 3-D forward call (fused levels, then copied back)
-	size_t vol_out_bytes = 0;
-	void *vol_host[2] = {nullptr, nullptr}; // device staging of host volumes (struct volume_t entries)
-	size_t vol_host_bytes[2] = {0, 0};
-	hipEvent_t dl_ev[8] = {}; // strip events of host_download, created once
+	// Two general dense device frames.  frame_a holds the staged frame of a host-pointer or strided call (frame_pack /
+	// frame_unpack) for the length of that call.  frame_b is the callee's temporary: the staged destination of the 2-D
+	// Mallat calls, the line-pass temporaries of the EAW and interleaved levels, the image copy of the fused EAW levels, the
+	// plane stacks of the SWT.  The exceptions: dwt_hip_features1d_batch packs strided lines into frame_b, because
+	// features() may stage into frame_a; the 3-D drivers take both as their level pools (dwt_hip_alloc_volumes points
+	// them into its arena during a trial).
+	Buf frame_a, frame_b;
+	Buf vol_out;     // dense result volume of an in-place 3-D forward call (fused levels, then copied back)
+	Buf vol_host[2]; // device staging of host volumes (struct volume_t entries)
+	Buf eaw_w, eaw_ll[2]; // EAW: device weights of a host-pointer call, LL ping-pong of the fused levels
+	Buf feat_ws; // feature statistics: records, slab partials, band table, select histograms (dwt_backend_features.hip)
+	Buf swt_ws;  // SWT level by level: the L chain's two dense images (dwt_backend_swt.hip)
+	// every device scratch buffer above: a new one is declared there, listed here, and named nowhere else for freeing
+	auto bufs()
+	{
+		return std::array{&stage_img, &ll[0], &ll[1], &frame_a, &frame_b, &vol_out, &vol_host[0], &vol_host[1], &eaw_w, &eaw_ll[0], &eaw_ll[1], &feat_ws, &swt_ws};
+	}
+	hipEvent_t dl_ev[8] = {}; // strip events of the host downloads (dwt_host_xfer.hip), created once
 	hipEvent_t switch_ev = nullptr; // dwt_hip_set_stream: orders a newly set stream behind the old one's work
 	// host-pointer calls on large images: level 0 band by band while the image is still crossing PCIe (host_forward_pipelined)
 	hipStream_t up = nullptr, down = nullptr;
 	hipEvent_t pipe_ev[3][16] = {};
 	int host_pipeline = 1; // 0: upload, transform, download one after the other
-	void *pin = nullptr; // pinned host staging for host-pointer calls with awkward strides
-	void *eaw_w = nullptr, *eaw_ll[2] = {nullptr, nullptr}; // EAW: device weights of a host-pointer call, LL ping-pong of the fused levels
-	size_t eaw_w_bytes = 0, eaw_ll_bytes[2] = {0, 0};
+	void *pin = nullptr; // pinned host staging for host-pointer calls with awkward strides (hipHostFree: not a Buf)
 	size_t pin_bytes = 0;
-	void *feat_ws = nullptr; // feature statistics: records, slab partials, band table, select histograms (dwt_backend_features.hip)
-	size_t feat_ws_bytes = 0;
 	int feat_groups = 0; // workgroups of the feature slab passes (0: the launcher's rule); results do not depend on it
-	void *swt_ws = nullptr; // SWT level by level: the L chain's two dense images (dwt_backend_swt.hip)
-	size_t swt_ws_bytes = 0;
 	int swt_fused = 1; // SWT lines of up to N1D_MAX samples in one launch (0: one launch per level, the cross-check)
 	// options
 	SweepTuning tune;
@@ -156,15 +166,30 @@ struct Geom {
 	bool dense() const { return sox == six && soy == siy; }
 };
 
-int grow(void **p, size_t *have, size_t need);
+int grow(Buf &b, size_t need); // at least `need` bytes (never shrinks; a larger buffer replaces the old one behind a stream synchronise)
 void dev_free(void *p); // hipFree, or the release of a buffer mapped by dwt_placement.hip
+void drop(Buf &b);      // dev_free and forget (the caller has synchronised)
 int grant_range(const void *p, int owner, const int *devices, int n_devices); // a placed (VMM) buffer made reachable for these devices; plain allocations: no-op
 int copy_rect_on(hipStream_t st, Img dst, long dx, long dy, Img src, long sx_, long sy_, long w, long h);
 int copy_rect(Img dst, long dx, long dy, Img src, long sx_, long sy_, long w, long h);
 int zero_rect(Img img, long x, long y, long w, long h);
-// host images <-> dense device images (any byte strides; awkward pitches go through a pinned buffer)
-int host_upload(const void *hp, int stride_x, int stride_y, int es, int w, int h, void *dp, long pitch);
-int host_download(void *hp, int stride_x, int stride_y, int es, int w, int h, const void *dp, long pitch);
+// The staging detour of every driver (dwt_host_xfer.hip).  A frame that cannot run where it lies -- host memory, or a
+// device image whose elements are not adjacent or not aligned; each driver keeps its own rule for that -- is packed into
+// a dense device image (usually Ctx::frame_a), transformed there and spread back: only the frame's own elements are
+// written.  Device frames are packed / spread by a kernel on g.stream (dwt_strided.hip; not counted in stat_launches),
+// host frames cross PCIe and those two calls end synchronised (awkward host pitches go through the pinned buffer).
+// w x h elements of es bytes, rows sx bytes apart, elements sy bytes apart, in host or device memory
+struct Frame {
+	void *p;
+	long sx, sy;
+	int es, w, h;
+	bool dev;
+};
+// host frames take strides below 2 GiB.  The check lives in pack / unpack; a driver calls it itself only where the error
+// has to come before it allocates or writes anything (1-D, SWT)
+int frame_check(const Frame &f);
+int frame_pack(const Frame &f, void *dense, long pitch);         // -> dense device image
+int frame_unpack(const Frame &f, const void *dense, long pitch); // dense device image -> the frame's own elements
 int host_volume_xfer(bool to_device, void *dev, size_t d_sy, size_t d_sz, void *host, size_t h_sy, size_t h_sz, int nx, int ny, int nz);
 // one exact out-of-place 1-D pass over the lines of a frame (in == out is staged)
 int generic_pass(Wavelet w, bool inverse, bool rows, Img in, Img out, int frame_w, int frame_h, int n_lines, int N, int hoff);

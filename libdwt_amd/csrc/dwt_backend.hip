@@ -36,20 +36,25 @@ int fail(const char *fmt, ...)
 	return 1;
 }
 
-int grow(void **p, size_t *have, size_t need)
+int grow(Buf &b, size_t need)
 {
-	if (*have >= need)
+	if (b.bytes >= need)
 		return 0;
-	if (*p) {
+	if (b.p) {
 		HIP_TRY(hipStreamSynchronize(g.stream));
-		dev_free(*p);
-		*p = nullptr;
-		*have = 0;
+		drop(b);
 	}
-	HIP_TRY(hipMalloc(p, need));
+	HIP_TRY(hipMalloc(&b.p, need));
 	g.stat_allocs++;
-	*have = need;
+	b.bytes = need;
 	return 0;
+}
+
+void drop(Buf &b)
+{
+	if (b.p)
+		dev_free(b.p);
+	b = Buf{};
 }
 
 
@@ -159,9 +164,9 @@ int generic_pass(Wavelet w, bool inverse, bool rows, Img in, Img out, int frame_
 	Img dst = out;
 	if (alias) {
 		// staging image with the SAME pitch as the caller's image
-		if (grow(&g.stage_img, &g.stage_bytes, (size_t)out.sx * frame_h))
+		if (grow(g.stage_img, (size_t)out.sx * frame_h))
 			return 1;
-		dst = Img{(char *)g.stage_img, out.sx, out.es};
+		dst = Img{(char *)g.stage_img.p, out.sx, out.es};
 		if (copy_rect(dst, 0, 0, out, 0, 0, frame_w, frame_h))
 			return 1;
 	} else if (in.sx != out.sx) {
@@ -222,7 +227,7 @@ int prof_drain()
 }
 
 long ll_pitch_elems(int w) { return align_up(w, 4); }
-static char *ll_band(int k) { return (char *)g.ll[k]; }
+static char *ll_band(int k) { return (char *)g.ll[k].p; }
 
 size_t ll_band_bytes(const Geom &ge, int k, int batch, int es)
 {
@@ -233,11 +238,11 @@ int ensure_ll(const Geom &ge, int batch, int es)
 {
 	for (int k = 0; k < 2; k++) {
 		if (g.ll_external) {
-			if (g.ll_bytes[k] < ll_band_bytes(ge, k, batch, es))
+			if (g.ll[k].bytes < ll_band_bytes(ge, k, batch, es))
 				return fail("the caller's workspace (dwt_hip_set_workspace) is too small: band %d needs %zu bytes", k, ll_band_bytes(ge, k, batch, es));
 			continue;
 		}
-		if (grow(&g.ll[k], &g.ll_bytes[k], ll_band_bytes(ge, k, batch, es)))
+		if (grow(g.ll[k], ll_band_bytes(ge, k, batch, es)))
 			return 1;
 	}
 	return 0;
@@ -304,9 +309,9 @@ int forward2d(Wavelet w, Img src, Img dst, const Geom &ge, int *jp, int decompos
 			if (detour) {
 				if (batch != 1)
 					return fail("in-place batches are not supported; use distinct src and dst");
-				if (grow(&g.stage_img, &g.stage_bytes, (size_t)dst.sx * Ho))
+				if (grow(g.stage_img, (size_t)dst.sx * Ho))
 					return 1;
-				hdst = Img{(char *)g.stage_img, dst.sx, es};
+				hdst = Img{(char *)g.stage_img.p, dst.sx, es};
 				h_bstride = 0;
 				// a copy-back that follows at once reads the staged subbands out of the 256 MiB Infinity Cache when they were
 				// stored temporal (one 8192^2 image: 218.5 -> 205 us); a copy that rides along with the deeper levels is spread
@@ -378,9 +383,9 @@ int forward2d(Wavelet w, Img src, Img dst, const Geom &ge, int *jp, int decompos
 			// ping-pong through the staging image (rows: image -> stage, columns: stage -> image)
 			// instead of each staging and copying back a frame of its own: 4 instead of 12 frame
 			// transfers per level (the double-precision drivers and accel 1 live on these passes)
-			if (grow(&g.stage_img, &g.stage_bytes, (size_t)dst.sx * Ho))
+			if (grow(g.stage_img, (size_t)dst.sx * Ho))
 				return 1;
-			const Img S{(char *)g.stage_img, dst.sx, dst.es};
+			const Img S{(char *)g.stage_img.p, dst.sx, dst.es};
 			if (generic_pass(w, false, true, cur, S, Wo, Ho, Ho, Wi, Wd) || generic_pass(w, false, false, S, dst, Wo, Ho, Wo, Hi, Hd))
 				return 1;
 			cur = dst;
@@ -447,9 +452,9 @@ int inverse2d(Wavelet w, Img src, Img dst, const Geom &ge, int j_max, int decomp
 			carriers += sweep_ride_ok(g.tune, ge.Wo(j - 1), ge.Ho(j - 1), batch, true);
 		if (all && carriers > 0) {
 			const int Ws = ge.Wo(1), Hs = ge.Ho(1), Wo = ge.Wo(0), Ho = ge.Ho(0);
-			if (grow(&g.stage_img, &g.stage_bytes, (size_t)dst.sx * Ho))
+			if (grow(g.stage_img, (size_t)dst.sx * Ho))
 				return 1;
-			Img st{(char *)g.stage_img, dst.sx, es};
+			Img st{(char *)g.stage_img.p, dst.sx, es};
 			const Rect rc[2] = {{Ws, 0, Ws, 0, Wo - Ws, Ho}, {0, Hs, 0, Hs, Ws, Ho - Hs}};
 			ride.r = make_copy_rects(st, src, rc, 2, /* temporal both ways: the final level reads the staged subbands */ 0);
 			ride.total = copy_rects_plan(&ride.r);
@@ -488,9 +493,9 @@ int inverse2d(Wavelet w, Img src, Img dst, const Geom &ge, int j_max, int decomp
 					// move them (right half + bottom-left, and LL if it is still there) aside
 					if (batch != 1)
 						return fail("in-place batches are not supported; use distinct src and dst");
-					if (grow(&g.stage_img, &g.stage_bytes, (size_t)dst.sx * Ho))
+					if (grow(g.stage_img, (size_t)dst.sx * Ho))
 						return 1;
-					Img st{(char *)g.stage_img, dst.sx, es};
+					Img st{(char *)g.stage_img.p, dst.sx, es};
 					const Rect rc[3] = {{Ws, 0, Ws, 0, Wo - Ws, Ho}, {0, Hs, 0, Hs, Ws, Ho - Hs}, {0, 0, 0, 0, ll_in < 0 ? Ws : 0, Hs}};
 					if (ride.on) {
 						// (most of it went with the deeper levels' launches; what is left goes now)
@@ -555,9 +560,9 @@ int inverse2d(Wavelet w, Img src, Img dst, const Geom &ge, int j_max, int decomp
 		}
 		if (Wi == Wo && Hi == Ho && Wo >= 2 && Ho >= 2) {
 			// dense frame: ping-pong through the staging image, as in the forward driver
-			if (grow(&g.stage_img, &g.stage_bytes, (size_t)dst.sx * Ho))
+			if (grow(g.stage_img, (size_t)dst.sx * Ho))
 				return 1;
-			const Img S{(char *)g.stage_img, dst.sx, dst.es};
+			const Img S{(char *)g.stage_img.p, dst.sx, dst.es};
 			const bool rows_first = !cols_first;
 			if (generic_pass(w, true, rows_first, dst, S, Wo, Ho, rows_first ? Ho : Wo, rows_first ? Wi : Hi, rows_first ? Ws : Hs) ||
 				generic_pass(w, true, !rows_first, S, dst, Wo, Ho, rows_first ? Wo : Ho, rows_first ? Hi : Wi, rows_first ? Hs : Ws))

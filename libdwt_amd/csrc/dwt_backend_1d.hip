@@ -7,8 +7,6 @@
 // call under option "generic" / accel 1, run the reference's loop level by level: one exact line pass plus its zero fills.
 #include "dwt_backend.h"
 
-#include <climits>
-
 namespace dwtb {
 
 // levels whose input (forward) / output (inverse) line is longer than the fused kernel takes: they run as line passes
@@ -109,22 +107,17 @@ int transform1d(Wavelet w, bool inverse, const void *src, void *dst, long line_s
 		return inverse ? inverse_levels(w, d, n_lines, so, si, J, zero_padding) : forward_levels(w, d, n_lines, so, si, J, zero_padding);
 	}
 
-	// anything else -- host memory, strided elements -- is packed into a dense device frame, transformed in place there
-	// and spread back: host memory crosses PCIe once each way (the call is synchronous), strided device lines are packed on
-	// the device and only their own elements written back
-	if (!dev && (line_stride > INT_MAX || elem_stride > INT_MAX))
-		return fail("host lines: strides beyond 2 GiB are not supported");
+	// anything else -- host memory, strided elements -- takes the staging detour (dwt_backend.h) and is transformed in
+	// place in the dense device frame
+	const Frame fs{(void *)src, line_stride, elem_stride, 4, so, n_lines, dev};
+	if (frame_check(fs))
+		return 1;
 	const long pitch = align_up(4l * so, 256);
-	if (grow(&g.host_a, &g.host_a_bytes, (size_t)pitch * n_lines))
+	if (grow(g.frame_a, (size_t)pitch * n_lines))
 		return 1;
-	const Img A{(char *)g.host_a, pitch, 4};
-	if (dev) {
-		hipError_t e = launch_strided_pack(A.p, pitch, src, line_stride, elem_stride, 4, so, n_lines, g.stream);
-		if (e != hipSuccess)
-			return fail("strided pack launch failed: %s", hipGetErrorString(e));
-	} else if (host_upload(src, (int)line_stride, (int)elem_stride, 4, so, n_lines, A.p, pitch)) {
+	const Img A{(char *)g.frame_a.p, pitch, 4};
+	if (frame_pack(fs, A.p, pitch))
 		return 1;
-	}
 	int rc = 0;
 	if (J >= 1 && so == si && so <= N1D_MAX && !g.force_generic)
 		rc = fused_launch(w, inverse, A.p, A.p, pitch, 4, n_lines, so, J);
@@ -132,11 +125,7 @@ int transform1d(Wavelet w, bool inverse, const void *src, void *dst, long line_s
 		rc = inverse ? inverse_levels(w, A, n_lines, so, si, J, zero_padding) : forward_levels(w, A, n_lines, so, si, J, zero_padding);
 	if (rc)
 		return rc;
-	if (dev) {
-		hipError_t e = launch_strided_unpack(dst, line_stride, elem_stride, A.p, pitch, 4, so, n_lines, g.stream);
-		return e == hipSuccess ? 0 : fail("strided unpack launch failed: %s", hipGetErrorString(e));
-	}
-	return host_download(dst, (int)line_stride, (int)elem_stride, 4, so, n_lines, A.p, pitch);
+	return frame_unpack(Frame{dst, line_stride, elem_stride, 4, so, n_lines, dev}, A.p, pitch);
 }
 
 } // namespace dwtb

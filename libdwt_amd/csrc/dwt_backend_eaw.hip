@@ -58,9 +58,9 @@ int line_pass(bool inverse, char *base, long ls, long es, int n_lines, int N, in
 {
 	if (n_lines <= 0 || N <= 0)
 		return 0;
-	if (grow(&g.host_b, &g.host_b_bytes, (size_t)n_lines * N * 4))
+	if (grow(g.frame_b, (size_t)n_lines * N * 4))
 		return 1;
-	float *tmp = (float *)g.host_b;
+	float *tmp = (float *)g.frame_b.p;
 	const bool lanes_along_lines = ls < es; // columns of a row-major image
 	hipError_t e = launch_eaw_line(inverse, base, ls, es, n_lines, N, hoff, tmp, w, lanes_along_lines, alpha, g.stream);
 	g.stat_launches++;
@@ -130,16 +130,16 @@ int level_launch(bool inverse, const EawLevelArgs &a, float alpha)
 	return e == hipSuccess ? 0 : fail("EAW level launch failed: %s", hipGetErrorString(e));
 }
 
-// scratch of the fused levels: the image copy (host_b) and the LL ping-pong, for `batch` images
+// scratch of the fused levels: the image copy (frame_b) and the LL ping-pong, for `batch` images
 int fused_scratch(const EawFrame &f, int batch, float **copy, float **ll)
 {
 	const Geom &ge = f.ge;
 	const size_t img = (size_t)ge.sox * ge.soy * 4 * batch, llb = (size_t)ge.Wo(1) * ge.Ho(1) * 4 * batch;
-	if (grow(&g.host_b, &g.host_b_bytes, img) || grow(&g.eaw_ll[0], &g.eaw_ll_bytes[0], llb) || grow(&g.eaw_ll[1], &g.eaw_ll_bytes[1], llb))
+	if (grow(g.frame_b, img) || grow(g.eaw_ll[0], llb) || grow(g.eaw_ll[1], llb))
 		return 1;
-	*copy = (float *)g.host_b;
-	ll[0] = (float *)g.eaw_ll[0];
-	ll[1] = (float *)g.eaw_ll[1];
+	*copy = (float *)g.frame_b.p;
+	ll[0] = (float *)g.eaw_ll[0].p;
+	ll[1] = (float *)g.eaw_ll[1].p;
 	return 0;
 }
 
@@ -255,35 +255,27 @@ int eaw2d(bool inverse, int layout, void *ptr, int stride_x, int stride_y, const
 	if (dev && stride_y == 4 && stride_x % 4 == 0 && (uintptr_t)ptr % 4 == 0 && (fh == 1 || stride_x >= 4l * fw))
 		return run_device(inverse, f, Img{(char *)ptr, fh == 1 ? align_up(4l * fw, 4) : (long)stride_x, 4}, 1, 0, weights, f.total,
 			zero_padding, alpha);
-	// host memory, strided or unaligned device images: packed into a dense device image, transformed there, spread back
+	// host memory, strided or unaligned device images: the staging detour (dwt_backend.h)
 	const long pitch = align_up(4l * fw, 256);
-	if (grow(&g.host_a, &g.host_a_bytes, (size_t)pitch * fh))
+	if (grow(g.frame_a, (size_t)pitch * fh))
 		return 1;
-	const Img A{(char *)g.host_a, pitch, 4};
+	const Img A{(char *)g.frame_a.p, pitch, 4};
+	const Frame fr{ptr, stride_x, stride_y, 4, fw, fh, dev};
 	float *wd = weights;
-	if (dev) {
-		const hipError_t e = launch_strided_pack(A.p, pitch, ptr, stride_x, stride_y, 4, fw, fh, g.stream);
-		if (e != hipSuccess)
-			return fail("strided pack launch failed: %s", hipGetErrorString(e));
-	} else {
-		if (host_upload(ptr, stride_x, stride_y, 4, fw, fh, A.p, pitch))
+	if (frame_pack(fr, A.p, pitch))
+		return 1;
+	if (!dev) {
+		if (grow(g.eaw_w, std::max<size_t>((size_t)f.total * 4, 4)))
 			return 1;
-		if (grow(&g.eaw_w, &g.eaw_w_bytes, std::max<size_t>((size_t)f.total * 4, 4)))
-			return 1;
-		wd = (float *)g.eaw_w;
+		wd = (float *)g.eaw_w.p;
 		if (inverse)
 			HIP_TRY(hipMemcpyAsync(wd, weights, (size_t)f.total * 4, hipMemcpyHostToDevice, g.stream));
 	}
 	if (run_device(inverse, f, A, 1, 0, wd, f.total, zero_padding, alpha))
 		return 1;
-	if (dev) {
-		const hipError_t e = launch_strided_unpack(ptr, stride_x, stride_y, A.p, pitch, 4, fw, fh, g.stream);
-		return e == hipSuccess ? 0 : fail("strided unpack launch failed: %s", hipGetErrorString(e));
-	}
-	if (!inverse) {
+	if (!dev && !inverse)
 		HIP_TRY(hipMemcpyAsync(weights, wd, (size_t)f.total * 4, hipMemcpyDeviceToHost, g.stream));
-	}
-	return host_download(ptr, stride_x, stride_y, 4, fw, fh, A.p, pitch);
+	return frame_unpack(fr, A.p, pitch);
 }
 
 } // namespace

@@ -8,7 +8,7 @@
 // float exactly as the reference writes it (finish_band): equal sums give equal features.  Dense rows of up to N1D_MAX
 // samples take ONE launch; images and longer rows a fixed set of launches, whatever the batch: pass 1 and its fold,
 // pass 2 and its fold when a central moment is asked for, four histogram / pick pairs when the median is.  Host memory
-// and strided device images are packed into a dense device image first, as the transform drivers do.
+// and strided device images are packed into a dense device image first (frame_pack, dwt_backend.h).
 #include "dwt_backend.h"
 
 #include <climits>
@@ -115,9 +115,9 @@ int carve(long nrec, long npart, int nb, bool select, Ws *w)
 {
 	const size_t rec_b = (size_t)kFeatPlanes * nrec * 8, part_b = (size_t)4 * npart * 8, tab_b = align_up((long)nb * sizeof(FeatBand), 256);
 	const size_t hist_b = select ? (size_t)4 * nrec * 256 * 4 : 0, sel_b = select ? align_up(nrec * 8, 256) : 0;
-	if (grow(&g.feat_ws, &g.feat_ws_bytes, rec_b + part_b + tab_b + hist_b + sel_b + 256))
+	if (grow(g.feat_ws, rec_b + part_b + tab_b + hist_b + sel_b + 256))
 		return 1;
-	char *p = (char *)g.feat_ws;
+	char *p = (char *)g.feat_ws.p;
 	w->rec = (u64 *)p;
 	p += rec_b;
 	w->part = (u64 *)p;
@@ -135,6 +135,13 @@ int launched(hipError_t e, const char *what)
 {
 	g.stat_launches++;
 	return e == hipSuccess ? 0 : fail("feature %s launch failed: %s", what, hipGetErrorString(e));
+}
+
+// this driver counts the pack launch of a device frame among its own
+int pack(const Frame &f, void *dense, long pitch)
+{
+	g.stat_launches += f.dev;
+	return frame_pack(f, dense, pitch);
 }
 
 // how the kernels form the term of plane kFeatSp
@@ -292,28 +299,36 @@ int stage(const void *ptr, bool dev, long bstride, int batch, long stride_x, lon
 		return 0;
 	}
 	const long pitch = align_up(4l * fw, 256);
-	if (grow(&g.host_a, &g.host_a_bytes, (size_t)pitch * fh * batch))
+	if (grow(g.frame_a, (size_t)pitch * fh * batch))
 		return 1;
 	// the whole batch as ONE image of fh * batch rows where its rows are evenly apart: rows of one-row frames, or
 	// images that follow each other without a gap
 	const bool one = batch == 1 || (fh == 1 ? true : bstride == stride_x * (long)fh);
 	const long row_stride = fh == 1 && batch > 1 ? bstride : stride_x;
 	const long rows = one ? (long)fh * batch : fh;
-	if (!dev && (row_stride > INT_MAX || stride_y > INT_MAX))
-		return fail("host images take strides below 2 GiB (%ld, %ld bytes)", row_stride, stride_y);
-	for (int b = 0; b < (one ? 1 : batch); b++) {
-		const char *src = (const char *)ptr + (long)b * bstride;
-		char *dst = (char *)g.host_a + (long)b * pitch * fh;
-		if (dev) {
-			if (rows > INT_MAX)
-				return fail("too many rows to pack (%ld)", rows);
-			if (launched(launch_strided_pack(dst, pitch, src, row_stride, stride_y, 4, fw, (int)rows, g.stream), "strided pack"))
-				return 1;
-		} else if (host_upload(src, (int)row_stride, (int)stride_y, 4, fw, (int)rows, dst, pitch))
+	if (dev && rows > INT_MAX)
+		return fail("too many rows to pack (%ld)", rows);
+	for (int b = 0; b < (one ? 1 : batch); b++)
+		if (pack(Frame{(char *)ptr + (long)b * bstride, row_stride, stride_y, 4, fw, (int)rows, dev}, (char *)g.frame_a.p + (long)b * pitch * fh, pitch))
 			return 1;
-	}
-	*d = Img{(char *)g.host_a, pitch, 4};
+	*d = Img{(char *)g.frame_a.p, pitch, 4};
 	*dbs = pitch * fh;
+	return 0;
+}
+
+// The tail of a call whose feature vector is device memory: `fill` writes `n` blocks of `block` floats, back to back, into
+// host memory; they go to fv, `stride` floats apart.  Ends synchronised: the one host vector of the thread is reused by
+// the next call.
+thread_local std::vector<float> t_host_fv;
+template <class F>
+int to_device_fv(float *fv, long stride, long block, int n, F fill)
+{
+	std::vector<float> &host_fv = t_host_fv;
+	host_fv.resize((size_t)block * n);
+	if (fill(host_fv.data()))
+		return 1;
+	HIP_TRY(hipMemcpy2DAsync(fv, (size_t)(n > 1 ? stride : block) * 4, host_fv.data(), (size_t)block * 4, (size_t)block * 4, n, hipMemcpyHostToDevice, g.stream));
+	HIP_TRY(hipStreamSynchronize(g.stream));
 	return 0;
 }
 
@@ -343,14 +358,9 @@ int features(unsigned mask, const void *ptr, long bstride, int batch, long strid
 	const bool lines = ge.soy == 1 && ge.sox <= N1D_MAX && nb <= 32 && !mom.raw;
 	if (!fv_dev)
 		return run_device(d, dbs, batch, bands, nb, lines, ge.sox, mask, p, mom, fv, fv_stride);
-	static thread_local std::vector<float> host_fv;
 	const long block = (long)nf * nb;
-	host_fv.resize((size_t)block * batch);
-	if (run_device(d, dbs, batch, bands, nb, lines, ge.sox, mask, p, mom, host_fv.data(), block))
-		return 1;
-	HIP_TRY(hipMemcpy2DAsync(fv, (size_t)(batch > 1 ? fv_stride : block) * 4, host_fv.data(), (size_t)block * 4, (size_t)block * 4, batch, hipMemcpyHostToDevice, g.stream));
-	HIP_TRY(hipStreamSynchronize(g.stream)); // (host_fv is reused by the next call)
-	return 0;
+	return to_device_fv(fv, fv_stride, block, batch,
+		[&](float *host) { return run_device(d, dbs, batch, bands, nb, lines, ge.sox, mask, p, mom, host, block); });
 }
 
 bool bad_sizes(int sox, int soy, int six, int siy) { return sox < 0 || soy < 0 || six < 0 || siy < 0 || six > sox || siy > soy; }
@@ -389,9 +399,9 @@ int swt_features_device(Wavelet w, unsigned mask, const char *src, long ls, int 
 		return finish_records(ws.rec, nrec, n_lines, bands, levels, mask, a.pmode, p, Moment{}, fv, fv_stride);
 	}
 	const long pitch = 4l * N, plane = pitch * n_lines;
-	if (grow(&g.host_b, &g.host_b_bytes, (size_t)plane * levels))
+	if (grow(g.frame_b, (size_t)plane * levels))
 		return 1;
-	char *planes = (char *)g.host_b;
+	char *planes = (char *)g.frame_b.p;
 	if (band ? swt_device(w, src, ls, 4, n_lines, N, 0, levels, nullptr, 4, planes, 4, 2, plane, pitch) // (no H: level passes only)
 	         : swt_device(w, src, ls, 4, n_lines, N, 0, levels, planes, 4, nullptr, 4, 0, plane, pitch))
 		return 1;
@@ -497,22 +507,17 @@ int dwt_hip_features1d_batch(unsigned feature_mask, const void *ptr, size_t line
 	if (nb == 0 || n_lines == 0)
 		return 0;
 	const long pitch = align_up(4l * size, 256);
-	if (grow(&g.host_b, &g.host_b_bytes, (size_t)pitch * n_lines))
+	if (grow(g.frame_b, (size_t)pitch * n_lines))
 		return 1;
-	if (dev) {
-		if (launched(launch_strided_pack(g.host_b, pitch, ptr, (long)line_stride, (long)elem_stride, 4, size, n_lines, g.stream), "strided pack"))
-			return 1;
-	} else if (line_stride > INT_MAX)
-		return fail("host lines take strides below 2 GiB (%zu bytes)", line_stride);
-	else if (host_upload(ptr, (int)line_stride, (int)elem_stride, 4, size, n_lines, g.host_b, pitch))
+	if (pack(Frame{(void *)ptr, (long)line_stride, (long)elem_stride, 4, size, n_lines, dev}, g.frame_b.p, pitch))
 		return 1;
 	if (!dev) { // the packed lines are device memory, the vector is not: finish into it directly
 		const bool lines = size <= N1D_MAX && nb <= 32;
 		if (n_lines > 1 && fv_stride < (size_t)popcount(feature_mask) * nb)
 			return fail("feature stride %zu floats, one line takes %d", fv_stride, popcount(feature_mask) * nb);
-		return run_device(Img{(char *)g.host_b, pitch, 4}, pitch, n_lines, bands, nb, lines, size, feature_mask, p, Moment{}, fv, (long)fv_stride);
+		return run_device(Img{(char *)g.frame_b.p, pitch, 4}, pitch, n_lines, bands, nb, lines, size, feature_mask, p, Moment{}, fv, (long)fv_stride);
 	}
-	return features(feature_mask, g.host_b, pitch, n_lines, 4l * size, 4, ge, bands, nb, p, Moment{}, fv, (long)fv_stride, true);
+	return features(feature_mask, g.frame_b.p, pitch, n_lines, 4l * size, 4, ge, bands, nb, p, Moment{}, fv, (long)fv_stride, true);
 }
 
 int dwt_hip_swt_features1d_batch(int wavelet, unsigned feature_mask, const void *src, size_t line_stride, size_t elem_stride, int n_lines, int N,
@@ -546,29 +551,18 @@ int dwt_hip_swt_features1d_batch(int wavelet, unsigned feature_mask, const void 
 	long ls = (long)line_stride;
 	if (!dev || elem_stride != 4) {
 		const long pitch = align_up(4l * N, 256);
-		if (grow(&g.host_a, &g.host_a_bytes, (size_t)pitch * n_lines))
+		if (grow(g.frame_a, (size_t)pitch * n_lines))
 			return 1;
-		if (dev) {
-			if (launched(launch_strided_pack(g.host_a, pitch, src, (long)line_stride, (long)elem_stride, 4, N, n_lines, g.stream), "strided pack"))
-				return 1;
-		} else if (line_stride > INT_MAX)
-			return fail("host lines take strides below 2 GiB (%zu bytes)", line_stride);
-		else if (host_upload(src, (int)line_stride, (int)elem_stride, 4, N, n_lines, g.host_a, pitch))
+		if (pack(Frame{(void *)src, (long)line_stride, (long)elem_stride, 4, N, n_lines, dev}, g.frame_a.p, pitch))
 			return 1;
-		d = (const char *)g.host_a;
+		d = (const char *)g.frame_a.p;
 		ls = pitch;
 	}
 	if (!dev)
 		return swt_features_device(w, feature_mask, d, ls, n_lines, N, levels, band, p, fv, fv_line_stride);
-	static thread_local std::vector<float> host_fv;
 	const long block = (long)nf * levels;
-	host_fv.resize((size_t)block * n_lines);
-	if (swt_features_device(w, feature_mask, d, ls, n_lines, N, levels, band, p, host_fv.data(), block))
-		return 1;
-	HIP_TRY(hipMemcpy2DAsync(fv, (size_t)(n_lines > 1 ? fv_line_stride : block) * 4, host_fv.data(), (size_t)block * 4, (size_t)block * 4, n_lines,
-		hipMemcpyHostToDevice, g.stream));
-	HIP_TRY(hipStreamSynchronize(g.stream)); // (host_fv is reused by the next call)
-	return 0;
+	return to_device_fv(fv, fv_line_stride, block, n_lines,
+		[&](float *host) { return swt_features_device(w, feature_mask, d, ls, n_lines, N, levels, band, p, host, block); });
 }
 
 int dwt_hip_band_feature(int feature, const void *ptr, int stride_x, int stride_y, int size_x, int size_y, int j, float p, float *value)
@@ -626,10 +620,11 @@ int dwt_hip_abs(void *ptr, int stride_x, int stride_y, int size_x, int size_y)
 	if (stride_y < 4)
 		return fail("bad strides: %d, %d bytes", stride_x, stride_y);
 	const long pitch = align_up(4l * size_x, 256);
-	if (grow(&g.host_a, &g.host_a_bytes, (size_t)pitch * size_y) || host_upload(ptr, stride_x, stride_y, 4, size_x, size_y, g.host_a, pitch) ||
-		launched(launch_feat_abs(g.host_a, pitch, 4, size_x, size_y, g.stream), "abs"))
+	const Frame fr{ptr, stride_x, stride_y, 4, size_x, size_y, false};
+	if (grow(g.frame_a, (size_t)pitch * size_y) || frame_pack(fr, g.frame_a.p, pitch) ||
+		launched(launch_feat_abs(g.frame_a.p, pitch, 4, size_x, size_y, g.stream), "abs"))
 		return 1;
-	return host_download(ptr, stride_x, stride_y, 4, size_x, size_y, g.host_a, pitch);
+	return frame_unpack(fr, g.frame_a.p, pitch);
 }
 
 } // extern "C"

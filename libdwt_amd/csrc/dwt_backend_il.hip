@@ -89,9 +89,9 @@ static int il_level_phased(Wavelet w, bool inverse, Img in, Img out, int lx, int
 	}
 	if (n == 0)
 		return copy_rect(out, 0, 0, in, 0, 0, lx, ly);
-	if (grow(&g.host_b, &g.host_b_bytes, (size_t)in.sx * ly))
+	if (grow(g.frame_b, (size_t)in.sx * ly))
 		return 1;
-	Img tmp{(char *)g.host_b, in.sx, 4};
+	Img tmp{(char *)g.frame_b.p, in.sx, 4};
 	// ping-pong so that the last pass writes `out`
 	Img cur = in;
 	for (int i = 0; i < n; i++) {
@@ -185,9 +185,9 @@ static int il_level(Wavelet w, bool inverse, bool scale_single, Img in, Img out,
 			const size_t need = il_shell_bytes(lx, ly, tune.tile_pairs);
 			if (!need)
 				return fail("internal: this level cannot run in place");
-			if (grow(&g.stage_img, &g.stage_bytes, need))
+			if (grow(g.stage_img, need))
 				return 1;
-			e = launch_il_shell((const float *)in.p, in.sx / 4, lx, ly, tune.tile_pairs, (float *)g.stage_img, &sh, g.stream);
+			e = launch_il_shell((const float *)in.p, in.sx / 4, lx, ly, tune.tile_pairs, (float *)g.stage_img.p, &sh, g.stream);
 			if (e != hipSuccess)
 				return fail("interleaved in-place snapshot failed: %s", hipGetErrorString(e));
 		}
@@ -234,9 +234,9 @@ static int il_level(Wavelet w, bool inverse, bool scale_single, Img in, Img out,
 	}
 	if (in.sx != out.sx)
 		return fail("interleaved generic level: pitches differ");
-	if (grow(&g.host_b, &g.host_b_bytes, (size_t)in.sx * ly))
+	if (grow(g.frame_b, (size_t)in.sx * ly))
 		return 1;
-	Img tmp{(char *)g.host_b, in.sx, 4};
+	Img tmp{(char *)g.frame_b.p, in.sx, 4};
 	auto pass = [&](bool rows, Img from, Img to) -> int {
 		const int N = rows ? lx : ly, lines = rows ? ly : lx;
 		if ((N == 1 && !scale_single) || !(dirs & (rows ? 1 : 2)))
@@ -289,9 +289,9 @@ static int interleaved2d(Wavelet w, bool inverse, bool scale_single, Img src, Im
 	if (J > 1) {
 		if (g.ll_external)
 			return fail("the interleaved entries keep their level pyramid in the library's own scratch: hand it back first (dwt_hip_set_workspace(NULL, 0, NULL, 0))");
-		if (grow(&g.ll[0], &g.ll_bytes[0], pool * 4) || grow(&g.ll[1], &g.ll_bytes[1], pool * 4))
+		if (grow(g.ll[0], pool * 4) || grow(g.ll[1], pool * 4))
 			return 1;
-		float *pa = (float *)g.ll[0], *pb = (float *)g.ll[1];
+		float *pa = (float *)g.ll[0].p, *pb = (float *)g.ll[1].p;
 		for (int j = 1; j < J; j++) {
 			L[j].a = pa; L[j].b = pb;
 			pa += (size_t)L[j].pitch * L[j].ly;
@@ -314,9 +314,9 @@ static int interleaved2d(Wavelet w, bool inverse, bool scale_single, Img src, Im
 		il_shell_bytes(L[0].lx, L[0].ly, il_sweep_tile_pairs(g.tune, L[0].lx, L[0].ly, inverse)) != 0;
 	Img stage{nullptr, dst.sx, 4};
 	if ((alias && !ip0) || inverse) {
-		if (grow(&g.stage_img, &g.stage_bytes, (size_t)dst.sx * siy))
+		if (grow(g.stage_img, (size_t)dst.sx * siy))
 			return 1;
-		stage.p = (char *)g.stage_img;
+		stage.p = (char *)g.stage_img.p;
 	}
 
 	if (!inverse) {
@@ -456,26 +456,18 @@ int dwt_hip_transform2d_interleaved(int wavelet, int inverse, int flavour, const
 	}
 	if (dev_dst && (stride_y < 4 || (long)stride_x < (long)(sox - 1) * stride_y + 4))
 		return fail("device image: stride_y %d must be >= 4 and stride_x %d >= (width-1)*stride_y + 4", stride_y, stride_x);
-	// host pointers (any byte strides): the outer frame is staged through HBM; device images whose elements are not
-	// adjacent or not aligned: packed, transformed and spread back on the device (dwt_strided.hip)
+	// host pointers (any byte strides), device images whose elements are not adjacent or not aligned: the outer frame
+	// takes the staging detour (dwt_backend.h)
 	const long pitch = align_up((long)sox * 4, 256);
-	if (grow(&g.host_a, &g.host_a_bytes, (size_t)pitch * soy))
+	if (grow(g.frame_a, (size_t)pitch * soy))
 		return 1;
-	if (dev_dst) {
-		if (hipError_t e = launch_strided_pack(g.host_a, pitch, src, stride_x, stride_y, 4, sox, soy, g.stream))
-			return fail("strided pack launch failed: %s", hipGetErrorString(e));
-	} else if (host_upload(src, stride_x, stride_y, 4, sox, soy, g.host_a, pitch))
+	Img A{(char *)g.frame_a.p, pitch, 4};
+	if (frame_pack(Frame{(void *)src, stride_x, stride_y, 4, sox, soy, dev_dst}, A.p, pitch))
 		return 1;
-	Img A{(char *)g.host_a, pitch, 4};
 	if (fixed ? inplace_int2d(inverse != 0, A, A, sox, soy, six, siy, j, decompose_one)
 	          : interleaved2d(w, inverse != 0, scale_single, A, A, sox, soy, six, siy, j, decompose_one, dirs))
 		return 1;
-	if (dev_dst) {
-		if (hipError_t e = launch_strided_unpack(dst, stride_x, stride_y, g.host_a, pitch, 4, sox, soy, g.stream))
-			return fail("strided unpack launch failed: %s", hipGetErrorString(e));
-		return 0;
-	}
-	return host_download(dst, stride_x, stride_y, 4, sox, soy, g.host_a, pitch);
+	return frame_unpack(Frame{dst, stride_x, stride_y, 4, sox, soy, dev_dst}, A.p, pitch);
 }
 
 } // extern "C"

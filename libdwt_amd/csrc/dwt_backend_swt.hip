@@ -3,8 +3,8 @@
 //
 // Device lines of dense elements and up to N1D_MAX samples run every level in ONE launch of k_swt_lines (dwt_swt1d.hip).
 // Longer lines, strided elements, and every call under option "swt_fused" = 0 run one exact k_swt_level launch per level,
-// the L chain ping-ponged through library scratch.  Host memory is packed into a dense device image, transformed there
-// into dense device planes, and each plane spread back -- the call is synchronous, as the other host-pointer entries.
+// the L chain ping-ponged through library scratch.  Host memory takes the staging detour (dwt_backend.h): the lines
+// into a dense device image, transformed there into dense device planes, each plane spread back.
 #include "dwt_backend.h"
 
 #include <climits>
@@ -62,9 +62,9 @@ int swt_device(Wavelet w, const char *src, long ls, long es, int n_lines, int N,
 	const long pitch = 4l * N;
 	char *pp[2] = {nullptr, nullptr};
 	if (levels > 1) {
-		if (grow(&g.swt_ws, &g.swt_ws_bytes, (size_t)2 * pitch * n_lines))
+		if (grow(g.swt_ws, (size_t)2 * pitch * n_lines))
 			return 1;
-		pp[0] = (char *)g.swt_ws;
+		pp[0] = (char *)g.swt_ws.p;
 		pp[1] = pp[0] + (size_t)pitch * n_lines;
 	}
 	for (int l = 0; l < levels; l++) {
@@ -130,21 +130,26 @@ int swt1d(int wavelet, const void *src, long ls, long es, int n_lines, int N, in
 			plane_stride, dls);
 
 	// host memory: a dense device image of the lines, dense device planes, each plane spread back
-	if (ls > INT_MAX || es > INT_MAX || dls > INT_MAX || h_es > INT_MAX || l_es > INT_MAX)
-		return fail("host lines: strides beyond 2 GiB are not supported");
+	const Frame fs{(void *)src, ls, es, 4, N, n_lines, false}, fh{dst_h, dls, h_es, 4, N, n_lines, false}, fl{dst_l, dls, l_es, 4, N, n_lines, false};
+	if (frame_check(fs) || frame_check(fh) || frame_check(fl))
+		return 1;
 	const long pitch = align_up(4l * N, 256), plane = pitch * n_lines;
 	const int l_planes = l_mode == 2 ? levels : l_mode;
-	if (grow(&g.host_a, &g.host_a_bytes, (size_t)plane) || grow(&g.host_b, &g.host_b_bytes, (size_t)plane * (levels + l_planes)))
+	if (grow(g.frame_a, (size_t)plane) || grow(g.frame_b, (size_t)plane * (levels + l_planes)))
 		return 1;
-	char *dh = (char *)g.host_b, *dl = dh + (size_t)plane * levels;
-	if (host_upload(src, (int)ls, (int)es, 4, N, n_lines, g.host_a, pitch) ||
-		swt_device(w, (const char *)g.host_a, pitch, 4, n_lines, N, level0, levels, dh, 4, dl, 4, l_mode, plane, pitch))
+	char *dh = (char *)g.frame_b.p, *dl = dh + (size_t)plane * levels;
+	if (frame_pack(fs, g.frame_a.p, pitch) ||
+		swt_device(w, (const char *)g.frame_a.p, pitch, 4, n_lines, N, level0, levels, dh, 4, dl, 4, l_mode, plane, pitch))
 		return 1;
+	auto plane_of = [&](Frame f, int l) {
+		f.p = (char *)f.p + (long)l * plane_stride;
+		return f;
+	};
 	for (int l = 0; l < levels; l++)
-		if (host_download((char *)dst_h + (long)l * plane_stride, (int)dls, (int)h_es, 4, N, n_lines, dh + (size_t)plane * l, pitch))
+		if (frame_unpack(plane_of(fh, l), dh + (size_t)plane * l, pitch))
 			return 1;
 	for (int l = 0; l < l_planes; l++)
-		if (host_download((char *)dst_l + (long)l * plane_stride, (int)dls, (int)l_es, 4, N, n_lines, dl + (size_t)plane * l, pitch))
+		if (frame_unpack(plane_of(fl, l), dl + (size_t)plane * l, pitch))
 			return 1;
 	return 0;
 }

@@ -25,9 +25,9 @@ static int vol_forward_op(const float *src, long ssy, long ssz, float *dst, long
 		pool += (size_t)L[j].sz * L[j].lz;
 	}
 	if (levels > 1) {
-		if (grow(&g.host_a, &g.host_a_bytes, pool * 4) || grow(&g.host_b, &g.host_b_bytes, pool * 4))
+		if (grow(g.frame_a, pool * 4) || grow(g.frame_b, pool * 4))
 			return 1;
-		float *pa = (float *)g.host_a, *pb = (float *)g.host_b;
+		float *pa = (float *)g.frame_a.p, *pb = (float *)g.frame_b.p;
 		for (int j = 1; j < levels; j++) {
 			L[j].in = pa; L[j].out = pb;
 			pa += (size_t)L[j].sz * L[j].lz;
@@ -82,9 +82,9 @@ static int vol_forward_op(const float *src, long ssy, long ssz, float *dst, long
 			prof_before(j);
 			hipError_t e;
 			if (j == 0 && in_place_call) {
-				if (grow(&g.vol_out, &g.vol_out_bytes, vol_level_ip_scratch(fa, g.vol)))
+				if (grow(g.vol_out, vol_level_ip_scratch(fa, g.vol)))
 					return 1;
-				e = launch_vol_level_ip(false, fa, (float *)g.vol_out, g.vol, g.stream);
+				e = launch_vol_level_ip(false, fa, (float *)g.vol_out.p, g.vol, g.stream);
 			} else if ((fa.mode == 0 || fa.mode == 2) && g.vol.whole && g.vol.rows != 6 && vol_level_ip_can(fa)) {
 				// dense / withholding levels: the 64-row tiles of dwt_vol3d_ip.hip's kernel, out of place
 				e = launch_vol_level_op(false, fa, g.vol, g.stream);
@@ -101,9 +101,9 @@ static int vol_forward_op(const float *src, long ssy, long ssz, float *dst, long
 			// sized for the first level that needs it (the deeper ones are smaller)
 			s_sy = align_up(b.lx, 4);
 			s_sz = s_sy * b.ly;
-			if (grow(&g.stage_img, &g.stage_bytes, (size_t)s_sz * b.lz * 4))
+			if (grow(g.stage_img, (size_t)s_sz * b.lz * 4))
 				return 1;
-			S = (float *)g.stage_img;
+			S = (float *)g.stage_img.p;
 		}
 		FwdLevelArgs a;
 		a.in = b.in; a.in_pitch = j ? b.sy : ssy; a.in_bstride = j ? b.sz : ssz;
@@ -201,9 +201,9 @@ int dwt_hip_transform3d(int inverse, void *vol, size_t stride_y, size_t stride_z
 		p_total += (size_t)L[j].sz * L[j].lz;
 	}
 	if (levels > 1) {
-		if (grow(&g.host_a, &g.host_a_bytes, p_total * 4))
+		if (grow(g.frame_a, p_total * 4))
 			return 1;
-		float *p = (float *)g.host_a;
+		float *p = (float *)g.frame_a.p;
 		for (int j = 1; j < levels; j++) {
 			L[j].p = p;
 			p += (size_t)L[j].sz * L[j].lz;
@@ -215,9 +215,9 @@ int dwt_hip_transform3d(int inverse, void *vol, size_t stride_y, size_t stride_z
 	for (int j = 0; j < levels; j++)
 		if (!inverse || !ip_level(L[j].p, L[j].sy, L[j].sz, L[j].lx, L[j].ly, L[j].lz)) {
 			// S keeps level 0's strides for every level: slice z of level j at z * s_sz
-			if (grow(&g.stage_img, &g.stage_bytes, (size_t)s_sz * L[j].lz * 4))
+			if (grow(g.stage_img, (size_t)s_sz * L[j].lz * 4))
 				return 1;
-			S = (float *)g.stage_img;
+			S = (float *)g.stage_img.p;
 			break;
 		}
 
@@ -230,7 +230,7 @@ int dwt_hip_transform3d(int inverse, void *vol, size_t stride_y, size_t stride_z
 				VolFusedArgs fa{L[j].p, L[j].sy, L[j].sz, L[j].p, L[j].sy, L[j].sz, nullptr, 0, 0, L[j].lx, L[j].ly, L[j].lz};
 				shell = std::max(shell, vol_level_ip_scratch(fa, g.vol));
 			}
-		if (shell && grow(&g.vol_out, &g.vol_out_bytes, shell))
+		if (shell && grow(g.vol_out, shell))
 			return 1;
 	}
 
@@ -240,9 +240,9 @@ int dwt_hip_transform3d(int inverse, void *vol, size_t stride_y, size_t stride_z
 		if (inverse && ip_level(b.p, b.sy, b.sz, b.lx, b.ly, b.lz)) {
 			// one pass, in place (the volume itself for level 0, the dense copy of its lattice above)
 			VolFusedArgs fa{b.p, b.sy, b.sz, b.p, b.sy, b.sz, nullptr, 0, 0, b.lx, b.ly, b.lz};
-			if (grow(&g.vol_out, &g.vol_out_bytes, vol_level_ip_scratch(fa, g.vol)))
+			if (grow(g.vol_out, vol_level_ip_scratch(fa, g.vol)))
 				return 1;
-			e = launch_vol_level_ip(true, fa, (float *)g.vol_out, g.vol, g.stream);
+			e = launch_vol_level_ip(true, fa, (float *)g.vol_out.p, g.vol, g.stream);
 			if (e != hipSuccess)
 				return fail("in-place fused 3-D level launch failed: %s", hipGetErrorString(e));
 			return 0;
@@ -321,8 +321,8 @@ int dwt_hip_transform3d(int inverse, void *vol, size_t stride_y, size_t stride_z
 // whole-volume transfer between a HOST volume (any byte strides: libdwt's "optimal" strides are odd
 // byte counts) and a dense DEVICE volume of 4-byte samples.  Host rows the DMA engines like (64-byte
 // multiples, 16-byte aligned) go as one 2-D copy, or one per slice when the slices are padded; any
-// other layout goes slice by slice through host_upload / host_download (CPU repacking into a pinned
-// buffer, pipelined with the transfer).  Padding is never touched.
+// other layout goes through host_volume_xfer (CPU repacking into a pinned buffer, pipelined with the
+// transfer).  Padding is never touched.
 static int vol_xfer(bool to_device, void *dev, size_t d_sy, size_t d_sz, void *host, size_t h_sy, size_t h_sz, int nx, int ny, int nz)
 {
 	const size_t row = (size_t)nx * 4;
@@ -361,9 +361,9 @@ static int vol_check(const void *p, size_t sy, size_t sz, int nx, int ny, int nz
 static int vol_one_direction(float *vol, long sy, long sz, int nx, int ny, int nz, int dir)
 {
 	// the line pass shares its strides between source and destination: the staging volume mirrors the caller's
-	if (grow(&g.stage_img, &g.stage_bytes, (size_t)sz * nz * 4))
+	if (grow(g.stage_img, (size_t)sz * nz * 4))
 		return 1;
-	float *T = (float *)g.stage_img;
+	float *T = (float *)g.stage_img.p;
 	hipError_t e = hipSuccess;
 	if (dir == 4) {
 		// the z lines of row y: adjacent lanes take adjacent x
@@ -403,16 +403,16 @@ int dwt_hip_volume_fwd_op(const void *src, size_t s_sy, size_t s_sz, void *dst, 
 	float *D = (float *)dst;
 	long S_sy = (long)s_sy / 4, S_sz = (long)s_sz / 4, D_sy = (long)d_sy / 4, D_sz = (long)d_sz / 4;
 	if (!s_dev) {
-		if (grow(&g.vol_host[0], &g.vol_host_bytes[0], (size_t)t_sz * nz * 4) ||
-			vol_xfer(true, g.vol_host[0], t_sy * 4, t_sz * 4, (void *)src, s_sy, s_sz, nx, ny, nz))
+		if (grow(g.vol_host[0], (size_t)t_sz * nz * 4) ||
+			vol_xfer(true, g.vol_host[0].p, t_sy * 4, t_sz * 4, (void *)src, s_sy, s_sz, nx, ny, nz))
 			return 1;
-		S = (const float *)g.vol_host[0];
+		S = (const float *)g.vol_host[0].p;
 		S_sy = t_sy; S_sz = t_sz;
 	}
 	if (!d_dev) {
-		if (grow(&g.vol_host[1], &g.vol_host_bytes[1], (size_t)t_sz * nz * 4))
+		if (grow(g.vol_host[1], (size_t)t_sz * nz * 4))
 			return 1;
-		D = (float *)g.vol_host[1];
+		D = (float *)g.vol_host[1].p;
 		D_sy = t_sy; D_sz = t_sz;
 		if (!reads_src && vol_xfer(true, D, t_sy * 4, t_sz * 4, dst, d_sy, d_sz, nx, ny, nz))
 			return 1;
@@ -443,11 +443,11 @@ int dwt_hip_volume_ip(int inverse, void *data, size_t sy, size_t sz, int nx, int
 	if (dwt_hip_is_device_pointer(data))
 		return dwt_hip_transform3d(inverse, data, sy, sz, nx, ny, nz, 1);
 	const long t_sy = align_up(nx, 4), t_sz = t_sy * ny;
-	if (grow(&g.vol_host[0], &g.vol_host_bytes[0], (size_t)t_sz * nz * 4) ||
-		vol_xfer(true, g.vol_host[0], t_sy * 4, t_sz * 4, data, sy, sz, nx, ny, nz) ||
-		dwt_hip_transform3d(inverse, g.vol_host[0], t_sy * 4, t_sz * 4, nx, ny, nz, 1))
+	if (grow(g.vol_host[0], (size_t)t_sz * nz * 4) ||
+		vol_xfer(true, g.vol_host[0].p, t_sy * 4, t_sz * 4, data, sy, sz, nx, ny, nz) ||
+		dwt_hip_transform3d(inverse, g.vol_host[0].p, t_sy * 4, t_sz * 4, nx, ny, nz, 1))
 		return 1;
-	return vol_xfer(false, g.vol_host[0], t_sy * 4, t_sz * 4, data, sy, sz, nx, ny, nz);
+	return vol_xfer(false, g.vol_host[0].p, t_sy * 4, t_sz * 4, data, sy, sz, nx, ny, nz);
 }
 
 } // extern "C"

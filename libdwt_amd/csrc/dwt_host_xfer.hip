@@ -1,8 +1,11 @@
-// dwt_host_xfer.hip -- host-pointer calls: host images / volumes <-> dense device images (any byte
-// strides, src/system.c:102-164 is the reference's gather / scatter), and the pipelined host-pointer
-// calls on large images (level 0 and 1 band by band under their own PCIe transfers).
+// dwt_host_xfer.hip -- the staging detour (frame_pack / frame_unpack: host or strided device frames <-> dense device
+// images), host volumes <-> device volumes (any byte strides, src/system.c:102-164 is the reference's gather /
+// scatter), and the pipelined host-pointer calls on large images (level 0 and 1 band by band under their own PCIe
+// transfers).
 #include "dwt_backend.h"
 #include "dwt_host_pools.h"
+
+#include <climits>
 
 namespace dwtb {
 
@@ -65,7 +68,7 @@ static bool host_pitch_is_fast(const void *hp, int stride_x, int stride_y, int e
 }
 
 // w x h elements of `es` bytes at hp (byte strides) -> device image dp with `pitch`
-int host_upload(const void *hp, int stride_x, int stride_y, int es, int w, int h, void *dp, long pitch)
+static int host_upload(const void *hp, int stride_x, int stride_y, int es, int w, int h, void *dp, long pitch)
 {
 	if (host_pitch_is_fast(hp, stride_x, stride_y, es)) {
 		HIP_TRY(hipMemcpy2DAsync(dp, pitch, hp, stride_x, (size_t)w * es, h, hipMemcpyHostToDevice, g.stream));
@@ -98,7 +101,7 @@ int host_upload(const void *hp, int stride_x, int stride_y, int es, int w, int h
 	return 0;
 }
 
-int host_download(void *hp, int stride_x, int stride_y, int es, int w, int h, const void *dp, long pitch)
+static int host_download(void *hp, int stride_x, int stride_y, int es, int w, int h, const void *dp, long pitch)
 {
 	if (host_pitch_is_fast(hp, stride_x, stride_y, es)) {
 		HIP_TRY(hipMemcpy2DAsync(hp, stride_x, dp, pitch, (size_t)w * es, h, hipMemcpyDeviceToHost, g.stream));
@@ -140,6 +143,33 @@ int host_download(void *hp, int stride_x, int stride_y, int es, int w, int h, co
 		});
 	}
 	return 0;
+}
+
+// ---- the staging detour (dwt_backend.h) ----
+int frame_check(const Frame &f)
+{
+	if (!f.dev && (f.sx > INT_MAX || f.sy > INT_MAX))
+		return fail("host frames take strides below 2 GiB (%ld, %ld bytes)", f.sx, f.sy);
+	return 0;
+}
+
+static int strided_launched(hipError_t e, const char *what)
+{
+	return e == hipSuccess ? 0 : fail("strided %s launch failed: %s", what, hipGetErrorString(e));
+}
+
+int frame_pack(const Frame &f, void *dense, long pitch)
+{
+	if (f.dev)
+		return strided_launched(launch_strided_pack(dense, pitch, f.p, f.sx, f.sy, f.es, f.w, f.h, g.stream), "pack");
+	return frame_check(f) || host_upload(f.p, (int)f.sx, (int)f.sy, f.es, f.w, f.h, dense, pitch);
+}
+
+int frame_unpack(const Frame &f, const void *dense, long pitch)
+{
+	if (f.dev)
+		return strided_launched(launch_strided_unpack(f.p, f.sx, f.sy, dense, pitch, f.es, f.w, f.h, g.stream), "unpack");
+	return frame_check(f) || host_download(f.p, (int)f.sx, (int)f.sy, f.es, f.w, f.h, dense, pitch);
 }
 
 // A host volume with awkward strides (libdwt's own "optimal" strides are odd numbers of bytes: a 2-D copy with such a
@@ -268,16 +298,16 @@ int host_forward_pipelined(Wavelet w, const void *src, void *dst, int stride_x, 
 	if (two && !pin_dst.ok())
 		return -1;
 	auto body = [&]() -> int {
-		if (grow(&g.host_a, &g.host_a_bytes, (size_t)pitch * H) || grow(&g.host_b, &g.host_b_bytes, (size_t)pitch * H))
+		if (grow(g.frame_a, (size_t)pitch * H) || grow(g.frame_b, (size_t)pitch * H))
 			return 1;
 		// level 1 follows level 0 band by band too (its details are three quarters of the low-pass quadrant): scratch
 		// for both low-pass bands
 		const int Wd1 = (Wd + 1) / 2, Hd1 = (Hd + 1) / 2, Hh1 = Hd / 2;
 		const long llp = align_up((long)Wd, 64), llp1 = align_up((long)Wd1, 64);
 		const bool lvl1 = J > 1 && Wd >= 2 && Hd >= 2;
-		if (J > 1 && grow(&g.stage_img, &g.stage_bytes, ((size_t)llp * Hd + (size_t)llp1 * Hd1) * 4))
+		if (J > 1 && grow(g.stage_img, ((size_t)llp * Hd + (size_t)llp1 * Hd1) * 4))
 			return 1;
-		float *const ll0 = (float *)g.stage_img, *const ll1 = ll0 + (size_t)llp * Hd;
+		float *const ll0 = (float *)g.stage_img.p, *const ll1 = ll0 + (size_t)llp * Hd;
 		int done1 = 0; // level 1: row pairs computed so far
 		if (!g.up) {
 			HIP_TRY(hipStreamCreateWithFlags(&g.up, hipStreamNonBlocking));
@@ -287,7 +317,7 @@ int host_forward_pipelined(Wavelet w, const void *src, void *dst, int stride_x, 
 			for (int k = 0; k < 16; k++)
 				if (!row[k])
 					HIP_TRY(hipEventCreateWithFlags(&row[k], hipEventDisableTiming));
-		char *A = (char *)g.host_a, *B = (char *)g.host_b;
+		char *A = (char *)g.frame_a.p, *B = (char *)g.frame_b.p;
 		// everything queued on the caller's stream so far comes first
 		HIP_TRY(hipEventRecord(g.pipe_ev[0][15], g.stream));
 		HIP_TRY(hipStreamWaitEvent(g.up, g.pipe_ev[0][15], 0));
@@ -492,10 +522,10 @@ int host_inverse_pipelined(Wavelet w, const void *src, void *dst, int stride_x, 
 	if (two && !pin_dst.ok())
 		return -1;
 	auto body = [&]() -> int {
-		if (grow(&g.host_a, &g.host_a_bytes, (size_t)pitch * H) || grow(&g.host_b, &g.host_b_bytes, (size_t)pitch * H))
+		if (grow(g.frame_a, (size_t)pitch * H) || grow(g.frame_b, (size_t)pitch * H))
 			return 1;
 		const long llp = align_up((long)Wd, 64);
-		if (J > 1 && grow(&g.stage_img, &g.stage_bytes, (size_t)llp * Hd * 4))
+		if (J > 1 && grow(g.stage_img, (size_t)llp * Hd * 4))
 			return 1;
 		if (!g.up) {
 			HIP_TRY(hipStreamCreateWithFlags(&g.up, hipStreamNonBlocking));
@@ -505,7 +535,7 @@ int host_inverse_pipelined(Wavelet w, const void *src, void *dst, int stride_x, 
 			for (int k = 0; k < 16; k++)
 				if (!row[k])
 					HIP_TRY(hipEventCreateWithFlags(&row[k], hipEventDisableTiming));
-		char *A = (char *)g.host_a, *B = (char *)g.host_b;
+		char *A = (char *)g.frame_a.p, *B = (char *)g.frame_b.p;
 		HIP_TRY(hipEventRecord(g.pipe_ev[0][15], g.stream));
 		HIP_TRY(hipStreamWaitEvent(g.up, g.pipe_ev[0][15], 0));
 		HIP_TRY(hipStreamWaitEvent(g.down, g.pipe_ev[0][15], 0));
@@ -524,9 +554,9 @@ int host_inverse_pipelined(Wavelet w, const void *src, void *dst, int stride_x, 
 		long ll_pitch = pitch / 4;
 		if (J > 1) {
 			const Geom gl{Wd, Hd, Wd, Hd};
-			if (inverse2d(w, Img{A, pitch, 4}, Img{(char *)g.stage_img, llp * 4, 4}, gl, J - 1, decompose_one, 0, 1, 0, 0))
+			if (inverse2d(w, Img{A, pitch, 4}, Img{(char *)g.stage_img.p, llp * 4, 4}, gl, J - 1, decompose_one, 0, 1, 0, 0))
 				return 1;
-			ll = g.stage_img;
+			ll = g.stage_img.p;
 			ll_pitch = llp;
 		}
 		int top_done = 0, bot_done = Hd; // HL rows [0, top_done) and image rows [Hd, bot_done) are on their way up

@@ -28,8 +28,7 @@ namespace dwtb {
 struct SlotWorker : SlotThread {
 	SlotWorker() : SlotThread(dwt_hip_last_error) {}
 	// staging of this slot (owned by the worker thread's device): two source and two result pieces
-	void *stage[4] = {nullptr, nullptr, nullptr, nullptr};
-	size_t stage_bytes[4] = {0, 0, 0, 0};
+	Buf stage[4];
 	hipStream_t cin = nullptr, cout = nullptr;
 	hipEvent_t ev_in[2] = {}, ev_done[2] = {}, ev_out[2] = {};
 	int device = -1;
@@ -81,12 +80,8 @@ static int slot_job(SlotWorker *wk, const SlotOpts &opts, int device, int root_d
 		return 1;
 	opts.apply();
 	if (wk->device != device) { // the slot moved to another device: its staging, streams and events are on the old one
-		for (int k = 0; k < 4; k++) {
-			if (wk->stage[k])
-				dev_free(wk->stage[k]);
-			wk->stage[k] = nullptr;
-			wk->stage_bytes[k] = 0;
-		}
+		for (Buf &b : wk->stage)
+			drop(b);
 		if (wk->cin) {
 			hipStreamDestroy(wk->cin);
 			hipStreamDestroy(wk->cout);
@@ -139,7 +134,7 @@ static int slot_job(SlotWorker *wk, const SlotOpts &opts, int device, int root_d
 	const int n_pieces = n < 4 ? n : 4;
 	const int m = (n + n_pieces - 1) / n_pieces;
 	for (int k = 0; k < 4; k++)
-		if (grow(&wk->stage[k], &wk->stage_bytes[k], (size_t)m * batch_stride))
+		if (grow(wk->stage[k], (size_t)m * batch_stride))
 			return 1;
 	hipStream_t st = g.stream;
 	int j = j_in;
@@ -161,7 +156,7 @@ static int slot_job(SlotWorker *wk, const SlotOpts &opts, int device, int root_d
 	for (int c = 0; c < n_pieces; c++) {
 		const int a = shard_lo(c, n, n_pieces), cnt = shard_lo(c + 1, n, n_pieces) - a, s = c & 1;
 		const size_t off = (size_t)a * batch_stride, bytes = (size_t)cnt * batch_stride;
-		char *in = (char *)wk->stage[s], *out = (char *)wk->stage[2 + s];
+		char *in = (char *)wk->stage[s].p, *out = (char *)wk->stage[2 + s].p;
 		if (c >= 2) {
 			HIP_TRY(hipStreamWaitEvent(wk->cin, wk->ev_done[s], 0)); // piece c-2 has been read
 			HIP_TRY(hipStreamWaitEvent(wk->cin, wk->ev_out[s], 0));  // ... and its result has left

@@ -415,17 +415,14 @@ static int arena_place(const ArenaJob &job, void **out)
 struct TrialLL {
 	TrialLL(char *b0, size_t n0, char *b1, size_t n1)
 	{
-		g.ll[0] = b0;
-		g.ll[1] = b1;
-		g.ll_bytes[0] = n0;
-		g.ll_bytes[1] = n1;
+		g.ll[0] = Buf{b0, n0};
+		g.ll[1] = Buf{b1, n1};
 		g.ll_external = true;
 	}
 	~TrialLL()
 	{
 		g.ll_external = false;
-		g.ll[0] = g.ll[1] = nullptr;
-		g.ll_bytes[0] = g.ll_bytes[1] = 0;
+		g.ll[0] = g.ll[1] = Buf{};
 	}
 };
 
@@ -441,12 +438,8 @@ static int alloc_batch_arena(Wavelet w, int n_images, int size_x, int size_y, in
 	const size_t cap0 = (job.ws_bytes[0] + C - 1) / C * C, cap1 = (job.ws_bytes[1] + C - 1) / C * C;
 	// the context's own scratch makes room for the arena's candidates
 	hipStreamSynchronize(g.stream);
-	for (int b = 0; b < 2; b++) {
-		if (g.ll[b])
-			dev_free(g.ll[b]);
-		g.ll[b] = nullptr;
-		g.ll_bytes[b] = 0;
-	}
+	drop(g.ll[0]);
+	drop(g.ll[1]);
 	job.quick = [&](char *s, char *d, double *ms) {
 		// (a one-level call never touches the scratch; the context is pointed at the source region so that
 		// it does not allocate one of its own meanwhile)
@@ -461,10 +454,8 @@ static int alloc_batch_arena(Wavelet w, int n_images, int size_x, int size_y, in
 	const int rc = arena_place(job, out);
 	if (rc)
 		return rc;
-	g.ll[0] = out[2];
-	g.ll[1] = out[3];
-	g.ll_bytes[0] = cap0;
-	g.ll_bytes[1] = cap1;
+	g.ll[0] = Buf{out[2], cap0};
+	g.ll[1] = Buf{out[3], cap1};
 	*src_out = out[0];
 	*dst_out = out[1];
 	return 0;
@@ -512,18 +503,11 @@ static int alloc_volumes_arena(int nx, int ny, int nz, int levels, void **src_ou
 	if (pool)
 		job.ws_bytes = {pool, pool};
 	hipStreamSynchronize(g.stream);
-	void **own[2] = {&g.host_a, &g.host_b};
-	size_t *own_bytes[2] = {&g.host_a_bytes, &g.host_b_bytes};
-	for (int b = 0; b < 2; b++) {
-		if (*own[b])
-			dev_free(*own[b]);
-		*own[b] = nullptr;
-		*own_bytes[b] = 0;
-	}
+	drop(g.frame_a);
+	drop(g.frame_b);
 	auto point = [&](char *a, char *b, size_t n) {
-		g.host_a = a;
-		g.host_b = b;
-		g.host_a_bytes = g.host_b_bytes = n;
+		g.frame_a = Buf{a, n};
+		g.frame_b = Buf{b, n};
 	};
 	if (pool) // (a one-level call has no workspace: the quick measurement of the destinations)
 		job.quick = [&](char *s, char *d, double *ms) { return timed_volume_op(s, d, sy, sz, nx, ny, nz, 1, ms); };

@@ -188,7 +188,7 @@ int place_ll_scratch(Wavelet w, Img s, Img d, const Geom &ge, int levels, int ba
 	const size_t need[2] = {ll_band_bytes(ge, 0, batch, es), ll_band_bytes(ge, 1, batch, es)};
 	g.place_n = 0;
 	g.place_best = -1;
-	if (!may_measure() || g.placing || g.ll_external || g.place_tries < 2 || s.p == d.p || (g.ll_bytes[0] >= need[0] && g.ll_bytes[1] >= need[1]) ||
+	if (!may_measure() || g.placing || g.ll_external || g.place_tries < 2 || s.p == d.p || (g.ll[0].bytes >= need[0] && g.ll[1].bytes >= need[1]) ||
 		need[0] + need[1] < ((size_t)g.place_min_mib << 20) || !ge.dense() || ge.Wo(2) < 2 || ge.Ho(2) < 2 || g.force_generic ||
 		stream_is_capturing())
 		return 0;
@@ -223,17 +223,15 @@ int place_ll_scratch(Wavelet w, Img s, Img d, const Geom &ge, int levels, int ba
 		g.stat_allocs += 2 + (k ? 1 : 0);
 		// the context works on this candidate for the trial; the too-small scratch of earlier calls goes first
 		if (!own_released) {
-			if (g.ll[0] || g.ll[1])
+			if (g.ll[0].p || g.ll[1].p)
 				(void)hipStreamSynchronize(g.stream);
 			for (int b = 0; b < 2; b++)
-				if (g.ll[b])
-					dev_free(g.ll[b]);
+				if (g.ll[b].p)
+					dev_free(g.ll[b].p);
 			own_released = true;
 		}
-		for (int b = 0; b < 2; b++) {
-			g.ll[b] = c.ll[b];
-			g.ll_bytes[b] = need[b];
-		}
+		for (int b = 0; b < 2; b++)
+			g.ll[b] = Buf{c.ll[b], need[b]};
 		rc = timed_forward(w, s, d, ge, levels, batch, sb, db, &c.ms);
 		c.ok = rc == 0; // (a trial that failed has no time: never the best)
 		cands.push_back(c);
@@ -257,10 +255,8 @@ int place_ll_scratch(Wavelet w, Img s, Img d, const Geom &ge, int levels, int ba
 			hipFree(cands[k].ll[1]);
 		}
 	}
-	for (int b = 0; b < 2; b++) {
-		g.ll[b] = cands[best].ll[b];
-		g.ll_bytes[b] = need[b];
-	}
+	for (int b = 0; b < 2; b++)
+		g.ll[b] = Buf{cands[best].ll[b], need[b]};
 	return rc;
 }
 

@@ -528,7 +528,7 @@ for i, t in enumerate(dev):   # and back, alternating the other way round
 torch.cuda.synchronize()
 for i, t in enumerate(dev):
     assert np.abs(t.cpu().numpy() - imgs[i]).max() < 1e-5, f"inverse call {i}"
-# host-pointer calls (pinned staging, host_a / host_b) between two streams as well
+# host-pointer calls (pinned staging, frame_a / frame_b) between two streams as well
 h = [rng.random((700, 900), dtype=np.float32) for _ in range(4)]
 for i, a in enumerate(h):
     w_ = a.copy(); orc.fwd("cdf97_2f_s", w_, 3)
