@@ -378,6 +378,69 @@ int dwt_hip_swt1d_level(int wavelet, const void *src, void *dst_l, void *dst_h, 
 int dwt_hip_swt_features1d_batch(int wavelet, unsigned feature_mask, const void *src, size_t line_stride, size_t elem_stride,
 	int n_lines, int N, int levels, int band, float p, float *fv, int fv_line_stride);
 
+/* Time-frequency planes of line batches: the Gaussian-window STFT, the complex Morlet CWT and the S transform of
+ * src/gabor.c (gabor_ft_s, gabor_wt_s, gabor_st_s and their _arg_ twins; include/gabor.h), DESIGN.md s14.
+ *
+ * A BANK is `bins` complex kernels, each with its number of taps and its centre (0 <= centre < taps).  _bank_create
+ * generates the kernels of one transform exactly as the reference does, in float with the host's libm: kind FT reads
+ * sigma, WT reads sigma and freq, ST neither.  _bank_from_kernels takes them from the caller: sizes[bins],
+ * centers[bins], and the taps of all kernels one after the other as (re, im) pairs.  Both return NULL on error
+ * (dwt_hip_last_error) and need no device.  _bank_query copies sizes, centres and taps back (any pointer may be NULL;
+ * the tap array holds 2 * dwt_hip_timefreq_bank_taps floats).  A bank is used by one thread at a time.
+ *
+ * dwt_hip_timefreq_batch correlates every line with every kernel: with x the line's N samples, k the kernel of bin y,
+ *     c(t) = sum over i = -min(t, centre) .. min(N-1-t, taps-centre-1), ascending, of x[t+i] * conj(k[centre+i])
+ * summed from +0 in float, every product and sum rounded on its own: bit-identical to dwt_util_cdot1_s.  Bin y writes
+ * plane row bins-1-y, as the reference does.  out_kind DWT_HIP_TIMEFREQ_COMPLEX stores c as (re, im) pairs, _ABS the
+ * magnitude (bit-identical to cabsf over the whole float range), _ARG the argument (atan2 in double, rounded once).
+ * Output (line, row, t) goes to dst + line*plane_stride + row*row_stride + t*(8 for complex, else 4) bytes;
+ * _batch_strided takes the distance of the row's elements as well.  Lines are line_stride bytes apart, their samples
+ * elem_stride.  Both pointers are host memory or both device memory; they must not overlap (an error); n_lines, N and
+ * bins are at least 1.  A call on device memory takes ONE kernel launch, whatever n_lines, bins and the kernel sizes;
+ * kernels of any size are taken.  Option "timefreq_tiled" = 0 selects the plain kernel (one thread per output). */
+typedef struct dwt_hip_timefreq_bank dwt_hip_timefreq_bank;
+enum dwt_hip_timefreq_kind { DWT_HIP_TIMEFREQ_FT = 0, DWT_HIP_TIMEFREQ_WT = 1, DWT_HIP_TIMEFREQ_ST = 2 };
+enum dwt_hip_timefreq_out { DWT_HIP_TIMEFREQ_COMPLEX = 0, DWT_HIP_TIMEFREQ_ABS = 1, DWT_HIP_TIMEFREQ_ARG = 2 };
+dwt_hip_timefreq_bank *dwt_hip_timefreq_bank_create(int kind, int bins, float sigma, float freq);
+dwt_hip_timefreq_bank *dwt_hip_timefreq_bank_from_kernels(int bins, const int *sizes, const int *centers, const float *taps);
+void dwt_hip_timefreq_bank_free(dwt_hip_timefreq_bank *bank);
+int dwt_hip_timefreq_bank_bins(const dwt_hip_timefreq_bank *bank);
+long dwt_hip_timefreq_bank_taps(const dwt_hip_timefreq_bank *bank); /* of all kernels together */
+int dwt_hip_timefreq_bank_query(const dwt_hip_timefreq_bank *bank, int *sizes, int *centers, float *taps);
+int dwt_hip_timefreq_batch(dwt_hip_timefreq_bank *bank, const void *src, size_t line_stride, size_t elem_stride, int n_lines, int N,
+	int out_kind, void *dst, size_t plane_stride, size_t row_stride);
+int dwt_hip_timefreq_batch_strided(dwt_hip_timefreq_bank *bank, const void *src, size_t line_stride, size_t elem_stride, int n_lines,
+	int N, int out_kind, void *dst, size_t plane_stride, size_t row_stride, size_t dst_elem_stride);
+/* dwt_util_cdot1_s: the one sum c(func_center) of a signal (host or device) with one kernel of (re, im) pairs kern_stride
+ * bytes apart (host); re_im[2] is host memory */
+int dwt_hip_cdot1(const float *func, int func_size, int func_stride, int func_center, const float *kern, int kern_size,
+	int kern_stride, int kern_center, float *re_im);
+/* What include/gabor.h's entries stand on.  dwt_hip_gabor_transform: one plane of one signal as gabor_{ft,wt,st}[_arg]_s
+ * takes it (`kind` as above, arg != 0 for the argument; plane element (row, t) at plane + row*stride_x + t*stride_y);
+ * dwt_hip_timefreq_line: one line against one kernel of (re, im) pairs kern_stride bytes apart in host memory
+ * (timefreq_line / timefreq_arg_line).  The generators run on the host: dwt_hip_gaussian_size = (int)ceilf(1 + 2 * 4 *
+ * sigma * a), the centre is half of it; dwt_hip_gabor_wavelet stores gabor_wavelet(t, sigma, f, a) -- gabor_function
+ * for a = 1 -- as re_im[2]; dwt_hip_gabor_gen_kernel writes the dwt_hip_gaussian_size(sigma, a) taps of
+ * gabor_gen_kernel, `stride` bytes apart, into memory the caller holds. */
+int dwt_hip_gabor_transform(int kind, int arg, const float *sig, int sig_stride, int sig_size, void *plane, int stride_x, int stride_y,
+	int bins, float sigma, float freq);
+int dwt_hip_timefreq_line(int arg, float *dst, int dst_stride, const float *src, int src_stride, int size, const void *kern,
+	int kern_stride, int kern_size, int kern_center);
+int dwt_hip_gaussian_size(float sigma, float a);
+void dwt_hip_gabor_wavelet(float t, float sigma, float f, float a, float *re_im);
+void dwt_hip_gabor_gen_kernel(void *kern, int stride, float sigma, float freq, float a);
+/* The operators of src/gabor.c over a batch of planes: element (y, x) of plane p at base + p*plane_stride + y*stride_x +
+ * x*stride_y bytes in the source and in the destination, which must not overlap; host or device memory alike.
+ * dwt_hip_phase_derivative: phase_derivative_s, the difference of neighbouring angles along x wrapped by 2 pi into
+ * [-limit, +limit], limit > 0 (a value the wrap step does not move -- the reference would not return -- is left).
+ * dwt_hip_detect_ridges: detect_ridges1_s / 2_s / 3_s by `kind` 1 / 2 / 3.  Bit-identical to the reference, except that
+ * kind 3 quantises the gradient direction with cos and sin taken in double (the reference: cosf, sinf): a point may
+ * differ only where the cosine or sine of its gradient angle lies within a rounding error of +-1/2. */
+int dwt_hip_phase_derivative(const void *angle, void *derivative, int stride_x, int stride_y, int size_x, int size_y, int n_planes,
+	size_t plane_stride, float limit);
+int dwt_hip_detect_ridges(int kind, const void *src, void *ridges, int stride_x, int stride_y, int size_x, int size_y, int n_planes,
+	size_t plane_stride, float threshold);
+
 /* dwt_util_perf_cdf97_2_s's protocol (src/libdwt.c:21444-21476) with the M images
  * resident in HBM: seconds per transform, minimum over N loops. */
 void dwt_hip_perf_cdf97_2_s(int stride_x, int stride_y, int size_o_big_x, int size_o_big_y,

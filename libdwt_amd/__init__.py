@@ -864,6 +864,130 @@ swt_cdf97_f_ex_stride_s = _swt_entry("swt_cdf97_f_ex_stride_s", CDF97_S)
 swt_cdf53_f_ex_stride_s = _swt_entry("swt_cdf53_f_ex_stride_s", CDF53_S)
 
 
+# ---- time-frequency planes (include/libdwt_hip.h, include/gabor.h) -------------------------------------
+TIMEFREQ_KINDS = {"ft": 0, "wt": 1, "st": 2}
+TIMEFREQ_OUT = {"complex": 0, "abs": 1, "arg": 2}
+lib.dwt_hip_timefreq_bank_create.argtypes = [_I, _I, _F, _F]
+lib.dwt_hip_timefreq_bank_create.restype = _P
+lib.dwt_hip_timefreq_bank_from_kernels.argtypes = [_I, _P, _P, _P]
+lib.dwt_hip_timefreq_bank_from_kernels.restype = _P
+lib.dwt_hip_timefreq_bank_free.argtypes = [_P]
+lib.dwt_hip_timefreq_bank_free.restype = None
+lib.dwt_hip_timefreq_bank_bins.argtypes = [_P]
+lib.dwt_hip_timefreq_bank_bins.restype = _I
+lib.dwt_hip_timefreq_bank_taps.argtypes = [_P]
+lib.dwt_hip_timefreq_bank_taps.restype = C.c_long
+lib.dwt_hip_timefreq_bank_query.argtypes = [_P, _P, _P, _P]
+lib.dwt_hip_timefreq_bank_query.restype = _I
+lib.dwt_hip_timefreq_batch.argtypes = [_P, _P, _S, _S, _I, _I, _I, _P, _S, _S]
+lib.dwt_hip_timefreq_batch.restype = _I
+lib.dwt_hip_timefreq_batch_strided.argtypes = [_P, _P, _S, _S, _I, _I, _I, _P, _S, _S, _S]
+lib.dwt_hip_timefreq_batch_strided.restype = _I
+lib.dwt_hip_gabor_transform.argtypes = [_I, _I, _P, _I, _I, _P, _I, _I, _I, _F, _F]
+lib.dwt_hip_gabor_transform.restype = _I
+lib.dwt_hip_timefreq_line.argtypes = [_I, _P, _I, _P, _I, _I, _P, _I, _I, _I]
+lib.dwt_hip_timefreq_line.restype = _I
+lib.dwt_hip_cdot1.argtypes = [_P, _I, _I, _I, _P, _I, _I, _I, _P]
+lib.dwt_hip_cdot1.restype = _I
+lib.dwt_hip_phase_derivative.argtypes = [_P, _P, _I, _I, _I, _I, _I, _S, _F]
+lib.dwt_hip_phase_derivative.restype = _I
+lib.dwt_hip_detect_ridges.argtypes = [_I, _P, _P, _I, _I, _I, _I, _I, _S, _F]
+lib.dwt_hip_detect_ridges.restype = _I
+lib.dwt_hip_gaussian_size.argtypes = [_F, _F]
+lib.dwt_hip_gaussian_size.restype = _I
+
+
+class TimefreqBank:
+    """A bank of complex kernels (dwt_hip_timefreq_bank): `sizes`, `centers` and `taps` (one complex64 array per bin) read
+    back from the library.  Freed by free() or with the object."""
+
+    def __init__(self, handle):
+        self.handle = handle
+        if not handle:
+            raise DwtError(lib.dwt_hip_last_error().decode())
+        self.bins = lib.dwt_hip_timefreq_bank_bins(handle)
+
+    def query(self):
+        import numpy as np
+
+        sizes, centers = np.zeros(self.bins, np.int32), np.zeros(self.bins, np.int32)
+        taps = np.zeros(2 * lib.dwt_hip_timefreq_bank_taps(self.handle), np.float32)
+        _check(lib.dwt_hip_timefreq_bank_query(self.handle, sizes.ctypes.data, centers.ctypes.data, taps.ctypes.data), "dwt_hip_timefreq_bank_query")
+        return sizes, centers, np.split(taps.view(np.complex64), np.cumsum(sizes)[:-1])
+
+    def free(self):
+        if self.handle:
+            lib.dwt_hip_timefreq_bank_free(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        self.free()
+
+
+def timefreq_bank(kind=None, bins=0, sigma=0.0, freq=0.0, kernels=None, centers=None):
+    """A bank of one transform -- kind "ft" (reads sigma), "wt" (sigma, freq) or "st" with `bins` bins, generated as the
+    reference generates its kernels -- or of the caller's `kernels` (complex64 arrays) with their `centers`."""
+    if kernels is not None:
+        import numpy as np
+
+        sizes = np.array([len(k) for k in kernels], np.int32)
+        cs = np.array(centers, np.int32)
+        if len(kernels) < 1 or len(cs) != len(kernels):
+            raise DwtError("timefreq_bank: one centre per kernel, at least one kernel")
+        taps = np.ascontiguousarray(np.concatenate([np.asarray(k, np.complex64) for k in kernels])).view(np.float32)
+        return TimefreqBank(lib.dwt_hip_timefreq_bank_from_kernels(len(kernels), sizes.ctypes.data, cs.ctypes.data, taps.ctypes.data))
+    k = TIMEFREQ_KINDS.get(kind, kind) if isinstance(kind, str) else kind
+    if k not in (0, 1, 2):
+        raise DwtError("timefreq_bank: kind %r (ft, wt or st)" % (kind,))
+    return TimefreqBank(lib.dwt_hip_timefreq_bank_create(k, bins, float(sigma), float(freq)))
+
+
+def timefreq_batch(bank, src, line_stride, elem_stride, n_lines, size, out_kind, dst, plane_stride, row_stride, dst_elem_stride=None):
+    """dwt_hip_timefreq_batch: every line against every kernel of the bank; out_kind "complex", "abs" or "arg".  Output
+    (line, row, t) at dst + line*plane_stride + row*row_stride + t*dst_elem_stride bytes (dense by default), bin y in
+    row bins-1-y.  One launch for device memory."""
+    o = TIMEFREQ_OUT.get(out_kind, out_kind) if isinstance(out_kind, str) else out_kind
+    if o not in (0, 1, 2):
+        raise DwtError("timefreq_batch: out_kind %r (complex, abs or arg)" % (out_kind,))
+    if not isinstance(bank, TimefreqBank) or not bank.handle:
+        raise DwtError("timefreq_batch: the bank is freed or no TimefreqBank")
+    if dst_elem_stride is None:
+        _check(lib.dwt_hip_timefreq_batch(bank.handle, _addr(src), line_stride, elem_stride, n_lines, size, o, _addr(dst), plane_stride,
+                                          row_stride), "dwt_hip_timefreq_batch")
+    else:
+        _check(lib.dwt_hip_timefreq_batch_strided(bank.handle, _addr(src), line_stride, elem_stride, n_lines, size, o, _addr(dst),
+                                                  plane_stride, row_stride, dst_elem_stride), "dwt_hip_timefreq_batch_strided")
+
+
+def _gabor_entry(name, kind, arg):
+    def entry(sig, sig_stride, sig_size, plane, stride_x, stride_y, bins, sigma=0.0, freq=0.0):
+        """libdwt's prototype (include/gabor.h): one plane of one signal, host or device memory."""
+        if min(sig_stride, stride_x, stride_y) < 0:
+            raise DwtError("%s: negative stride" % name)
+        _check(lib.dwt_hip_gabor_transform(kind, arg, _addr(sig), sig_stride, sig_size, _addr(plane), stride_x, stride_y, bins, float(sigma),
+                                           float(freq)), name)
+
+    entry.__name__ = name
+    return entry
+
+
+gabor_ft_s, gabor_ft_arg_s = _gabor_entry("gabor_ft_s", 0, 0), _gabor_entry("gabor_ft_arg_s", 0, 1)
+gabor_wt_s, gabor_wt_arg_s = _gabor_entry("gabor_wt_s", 1, 0), _gabor_entry("gabor_wt_arg_s", 1, 1)
+gabor_st_s, gabor_st_arg_s = _gabor_entry("gabor_st_s", 2, 0), _gabor_entry("gabor_st_arg_s", 2, 1)
+
+
+def phase_derivative(angle, derivative, stride_x, stride_y, size_x, size_y, limit, n_planes=1, plane_stride=0):
+    """dwt_hip_phase_derivative (phase_derivative_s over n_planes planes)."""
+    _check(lib.dwt_hip_phase_derivative(_addr(angle), _addr(derivative), stride_x, stride_y, size_x, size_y, n_planes, plane_stride,
+                                        float(limit)), "dwt_hip_phase_derivative")
+
+
+def detect_ridges(kind, src, ridges, stride_x, stride_y, size_x, size_y, threshold, n_planes=1, plane_stride=0):
+    """dwt_hip_detect_ridges (detect_ridges1_s / 2_s / 3_s by kind, over n_planes planes)."""
+    _check(lib.dwt_hip_detect_ridges(kind, _addr(src), _addr(ridges), stride_x, stride_y, size_x, size_y, n_planes, plane_stride,
+                                     float(threshold)), "dwt_hip_detect_ridges")
+
+
 # ---- batches resident in HBM -----------------------------------------------------------
 def transform2d_batch(wavelet, inverse, src, dst, batch_stride, batch, stride_x, size_x, size_y, j_max=-1):
     j = _I(j_max)

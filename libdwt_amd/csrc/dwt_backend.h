@@ -65,6 +65,7 @@ struct Ctx {
 	void *pin = nullptr; // pinned host staging for host-pointer calls with awkward strides (hipHostFree: not a Buf)
 	size_t pin_bytes = 0;
 	int feat_groups = 0; // workgroups of the feature slab passes (0: the launcher's rule); results do not depend on it
+	int tf_tiled = 1;  // time-frequency planes of dense lines through the LDS-tiled kernel (0: one thread per output, the cross-check)
 	int swt_fused = 1; // SWT lines of up to N1D_MAX samples in one launch (0: one launch per level, the cross-check)
 	// options
 	SweepTuning tune;

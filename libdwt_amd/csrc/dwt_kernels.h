@@ -379,6 +379,43 @@ struct SwtLevelArgs {
 };
 hipError_t launch_swt_level(Wavelet w, const SwtLevelArgs &a, hipStream_t s);
 
+// Time-frequency planes (dwt_timefreq.hip): every line of a batch correlated with a bank of complex kernels,
+//   out(line, bin, t) = sum over the kernel's taps i, ascending, of x[t - center + i] * conj(k[i])   (taps inside [0, N) only),
+// from +0, product and sum rounded separately.  The device bank holds the taps already conjugated.
+struct TfBin {
+	long off;         // first tap of the bin in the bank's tap array
+	int size, center; // 0 <= center < size
+	int row, pad;     // plane row the bin writes
+};
+enum TfOut { kTfComplex = 0, kTfAbs = 1, kTfArg = 2 };
+struct TfArgs {
+	const char *src;     // element t of line y at src + y*src_ls + t*src_es (bytes)
+	long src_ls, src_es;
+	int n_lines, N;
+	int t0, nt;          // the outputs t0 .. t0+nt-1 of every line are computed
+	const float2 *taps;  // (re, -im)
+	const TfBin *bins;
+	const int *order;    // the bins by falling size: the order workgroups take them in
+	int n_bins;
+	int out;             // TfOut
+	char *dst;           // output (y, row, t) at dst + y*plane_stride + row*row_stride + t*dst_es: a float, or (re, im)
+	long plane_stride, row_stride, dst_es;
+};
+// one thread per output, signal and taps read from global memory; any strides that are multiples of 4
+hipError_t launch_tf_plain(const TfArgs &a, hipStream_t s);
+// dense lines (src_es == 4), finite taps: the signal window in LDS, the taps wave-uniform, 8 outputs per lane
+hipError_t launch_tf_tiled(const TfArgs &a, hipStream_t s);
+// the plane operators (phase_derivative_s, detect_ridges{1,2,3}_s of src/gabor.c) over n_planes planes: element (y, x) of
+// plane p at base + p*ps + y*sx + x*sy (bytes) on both sides.  op 0: phase derivative (param = limit), 1..3: ridges
+struct TfPlaneArgs {
+	const char *src;
+	char *dst;
+	long ps, sx, sy;
+	int size_x, size_y, n_planes, op;
+	float param;
+};
+hipError_t launch_tf_plane_op(const TfPlaneArgs &a, hipStream_t s);
+
 // the strided gather / scatter (dwt_util_memcpy_stride_s / _i, src/system.c:102-164) on the device: w x h elements of
 // `es` bytes between a dense image (row pitch `pitch`) and one whose element (y, x) lies at y*sx + x*sy; all in BYTES
 hipError_t launch_strided_pack(void *dense, long pitch, const void *strided, long sx, long sy, int es, int w, int h, hipStream_t st);
