@@ -384,15 +384,13 @@ int dwt_hip_transform2d(int wavelet, int inverse, const void *src, void *dst, in
 		if (rc >= 0)
 			return rc;
 	}
-	const long pitch = align_up((long)sox * es, 256);
-	const size_t bytes = (size_t)pitch * soy;
-	if (grow(g.frame_a, bytes) || grow(g.frame_b, bytes))
-		return 1;
 	const bool s2 = (src != dst);
 	const Frame fs{(void *)src, stride_x, stride_y, es, sox, soy, dev_dst}, fd{dst, stride_x, stride_y, es, sox, soy, dev_dst};
-	Img A{(char *)g.frame_a.p, pitch, es}, B{(char *)g.frame_b.p, pitch, es};
-	if (frame_pack(fs, A.p, pitch))
+	Img A;
+	if (frame_stage(fs, g.frame_a, &A) || grow(g.frame_b, (size_t)A.sx * soy))
 		return 1;
+	const long pitch = A.sx;
+	const Img B{(char *)g.frame_b.p, pitch, es};
 	// B receives the result.  It starts as a copy of what the destination holds so
 	// that every element the reference leaves untouched keeps its value -- unless the call
 	// writes every element of the frame anyway (a dense frame, at least one level: no second

@@ -13,6 +13,7 @@
 #include <array>
 #include <condition_variable>
 #include <functional>
+#include <initializer_list>
 #include <map>
 #include <mutex>
 #include <thread>
@@ -42,9 +43,8 @@ struct Ctx {
 	// Two general dense device frames.  frame_a holds the staged frame of a host-pointer or strided call (frame_pack /
 	// frame_unpack) for the length of that call.  frame_b is the callee's temporary: the staged destination of the 2-D
 	// Mallat calls, the line-pass temporaries of the EAW and interleaved levels, the image copy of the fused EAW levels, the
-	// plane stacks of the SWT.  The exceptions: dwt_hip_features1d_batch packs strided lines into frame_b, because
-	// features() may stage into frame_a; the 3-D drivers take both as their level pools (dwt_hip_alloc_volumes points
-	// them into its arena during a trial).
+	// plane stacks of the SWT.  The exception: the 3-D drivers take both as their level pools (dwt_hip_alloc_volumes
+	// points them into its arena during a trial).
 	Buf frame_a, frame_b;
 	Buf vol_out;     // dense result volume of an in-place 3-D forward call (fused levels, then copied back)
 	Buf vol_host[2]; // device staging of host volumes (struct volume_t entries)
@@ -118,6 +118,16 @@ extern thread_local char g_err[512];
 extern thread_local bool g_elems_are_32bit; // set per call: the fused sweeps exist for 4-byte elements only
 
 int fail(const char *fmt, ...);
+// the tail of a kernel launch that this context counts (stat_launches): 0, or fail("<family> <what> launch failed: ...")
+int launched(hipError_t e, const char *family, const char *what);
+// device memory is read and written as 4-byte words: every address and stride of a device call is a multiple of 4 bytes
+int check_dev_align(std::initializer_list<const void *> ptrs, std::initializer_list<long> strides);
+// do na bytes at a and nb bytes at b share a byte?
+inline bool overlap(const void *a, size_t na, const void *b, size_t nb)
+{
+	const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+	return na && nb && pa < pb + nb && pb < pa + na;
+}
 
 // The public wavelet id of a C-ABI call (enum dwt_hip_wavelet) as the internal enum Wavelet: ids 0..5 are the same
 // numbers, DWT_HIP_INTERP53_S (6) is kInterp53S -- internal 6 is the contracted float 9/7.  false: no such public id.
@@ -191,6 +201,13 @@ struct Frame {
 int frame_check(const Frame &f);
 int frame_pack(const Frame &f, void *dense, long pitch);         // -> dense device image
 int frame_unpack(const Frame &f, const void *dense, long pitch); // dense device image -> the frame's own elements
+// the pitch every staged frame takes, and the whole first half of the detour: `buf` grown to f.h rows of that pitch, the
+// frame packed into it, *dense describing it
+inline long frame_pitch(long es, long w) { return align_up(es * w, 256); }
+int frame_stage(const Frame &f, Buf &buf, Img *dense);
+// n frames like f, plane_stride bytes apart from f.p on <-> a dense stack of images of `pitch`, pitch * f.h bytes apart
+int frame_pack_stack(Frame f, int n, long plane_stride, void *stack, long pitch);
+int frame_unpack_stack(Frame f, int n, long plane_stride, const void *stack, long pitch);
 int host_volume_xfer(bool to_device, void *dev, size_t d_sy, size_t d_sz, void *host, size_t h_sy, size_t h_sz, int nx, int ny, int nz);
 // one exact out-of-place 1-D pass over the lines of a frame (in == out is staged)
 int generic_pass(Wavelet w, bool inverse, bool rows, Img in, Img out, int frame_w, int frame_h, int n_lines, int N, int hoff);

@@ -36,6 +36,22 @@ int fail(const char *fmt, ...)
 	return 1;
 }
 
+int launched(hipError_t e, const char *family, const char *what)
+{
+	g.stat_launches++;
+	return e == hipSuccess ? 0 : fail("%s %s launch failed: %s", family, what, hipGetErrorString(e));
+}
+
+int check_dev_align(std::initializer_list<const void *> ptrs, std::initializer_list<long> strides)
+{
+	bool ok = true;
+	for (const void *p : ptrs)
+		ok = ok && (uintptr_t)p % 4 == 0;
+	for (long s : strides)
+		ok = ok && s % 4 == 0;
+	return ok ? 0 : fail("device memory takes strides and addresses that are multiples of 4 bytes");
+}
+
 int grow(Buf &b, size_t need)
 {
 	if (b.bytes >= need)
@@ -85,11 +101,7 @@ static CopyRects make_copy_rects(Img dst, Img src, const Rect *rc, int n, int po
 
 int copy_rects_on(hipStream_t st, Img dst, Img src, const Rect *rc, int n, int policy = 3)
 {
-	hipError_t e = launch_copy_rects(make_copy_rects(dst, src, rc, n, policy), st);
-	g.stat_launches++;
-	if (e != hipSuccess)
-		return fail("rectangle copy launch failed: %s", hipGetErrorString(e));
-	return 0;
+	return launched(launch_copy_rects(make_copy_rects(dst, src, rc, n, policy), st), "rectangle", "copy");
 }
 
 // A rectangle copy that RIDES ALONG with the levels it does not depend on (one image, in place: the staged subbands of
@@ -116,12 +128,9 @@ struct RideCopy {
 	{
 		if (!on || next >= total)
 			return 0;
-		hipError_t e = launch_copy_rects_range(r, next, total, g.stream);
-		g.stat_launches++;
+		const int from = next;
 		next = total;
-		if (e != hipSuccess)
-			return fail("rectangle copy launch failed: %s", hipGetErrorString(e));
-		return 0;
+		return launched(launch_copy_rects_range(r, from, total, g.stream), "rectangle", "copy");
 	}
 };
 
@@ -172,10 +181,8 @@ int generic_pass(Wavelet w, bool inverse, bool rows, Img in, Img out, int frame_
 	} else if (in.sx != out.sx) {
 		return fail("generic pass: source and destination pitches differ (%ld vs %ld)", in.sx, out.sx);
 	}
-	hipError_t e = launch_line_pass(w, inverse, in.p, dst.p, rows ? in.sx : in.es, rows ? in.es : in.sx, n_lines, N, hoff, !rows, g.stream);
-	g.stat_launches++;
-	if (e != hipSuccess)
-		return fail("line pass launch failed: %s", hipGetErrorString(e));
+	if (launched(launch_line_pass(w, inverse, in.p, dst.p, rows ? in.sx : in.es, rows ? in.es : in.sx, n_lines, N, hoff, !rows, g.stream), "line", "pass"))
+		return 1;
 	if (alias && copy_rect(out, 0, 0, dst, 0, 0, frame_w, frame_h))
 		return 1;
 	return 0;

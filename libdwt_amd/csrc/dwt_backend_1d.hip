@@ -20,11 +20,7 @@ static int long_levels(int so, int J)
 
 static int fused_launch(Wavelet w, bool inverse, const char *s, char *d, long ls, long es, int n_lines, int N, int levels)
 {
-	const hipError_t e = launch_line_levels(w, inverse, s, d, ls, es, n_lines, N, levels, g.stream);
-	g.stat_launches++;
-	if (e != hipSuccess)
-		return fail("1-D level launch failed: %s", hipGetErrorString(e));
-	return 0;
+	return launched(launch_line_levels(w, inverse, s, d, ls, es, n_lines, N, levels, g.stream), "1-D", "level");
 }
 
 // Forward, in place on `d` (lines of dense 4-byte elements, row pitch d.sx), J levels already clamped.
@@ -112,12 +108,10 @@ int transform1d(Wavelet w, bool inverse, const void *src, void *dst, long line_s
 	const Frame fs{(void *)src, line_stride, elem_stride, 4, so, n_lines, dev};
 	if (frame_check(fs))
 		return 1;
-	const long pitch = align_up(4l * so, 256);
-	if (grow(g.frame_a, (size_t)pitch * n_lines))
+	Img A;
+	if (frame_stage(fs, g.frame_a, &A))
 		return 1;
-	const Img A{(char *)g.frame_a.p, pitch, 4};
-	if (frame_pack(fs, A.p, pitch))
-		return 1;
+	const long pitch = A.sx;
 	int rc = 0;
 	if (J >= 1 && so == si && so <= N1D_MAX && !g.force_generic)
 		rc = fused_launch(w, inverse, A.p, A.p, pitch, 4, n_lines, so, J);

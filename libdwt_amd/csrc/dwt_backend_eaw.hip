@@ -62,13 +62,8 @@ int line_pass(bool inverse, char *base, long ls, long es, int n_lines, int N, in
 		return 1;
 	float *tmp = (float *)g.frame_b.p;
 	const bool lanes_along_lines = ls < es; // columns of a row-major image
-	hipError_t e = launch_eaw_line(inverse, base, ls, es, n_lines, N, hoff, tmp, w, lanes_along_lines, alpha, g.stream);
-	g.stat_launches++;
-	if (e == hipSuccess) {
-		e = launch_eaw_place(base, ls, es, n_lines, N, inverse ? -1 : hoff, tmp, lanes_along_lines, g.stream);
-		g.stat_launches++;
-	}
-	return e == hipSuccess ? 0 : fail("EAW line pass launch failed: %s", hipGetErrorString(e));
+	return launched(launch_eaw_line(inverse, base, ls, es, n_lines, N, hoff, tmp, w, lanes_along_lines, alpha, g.stream), "EAW", "line pass") ||
+	       launched(launch_eaw_place(base, ls, es, n_lines, N, inverse ? -1 : hoff, tmp, lanes_along_lines, g.stream), "EAW", "line pass");
 }
 
 // Level j of the reference's loop on the dense device image d (4-byte elements, pitch d.sx).
@@ -125,9 +120,7 @@ int fused_levels(const EawFrame &f)
 
 int level_launch(bool inverse, const EawLevelArgs &a, float alpha)
 {
-	const hipError_t e = launch_eaw_level(inverse, a, alpha, g.stream);
-	g.stat_launches++;
-	return e == hipSuccess ? 0 : fail("EAW level launch failed: %s", hipGetErrorString(e));
+	return launched(launch_eaw_level(inverse, a, alpha, g.stream), "EAW", "level");
 }
 
 // scratch of the fused levels: the image copy (frame_b) and the LL ping-pong, for `batch` images
@@ -256,13 +249,10 @@ int eaw2d(bool inverse, int layout, void *ptr, int stride_x, int stride_y, const
 		return run_device(inverse, f, Img{(char *)ptr, fh == 1 ? align_up(4l * fw, 4) : (long)stride_x, 4}, 1, 0, weights, f.total,
 			zero_padding, alpha);
 	// host memory, strided or unaligned device images: the staging detour (dwt_backend.h)
-	const long pitch = align_up(4l * fw, 256);
-	if (grow(g.frame_a, (size_t)pitch * fh))
-		return 1;
-	const Img A{(char *)g.frame_a.p, pitch, 4};
 	const Frame fr{ptr, stride_x, stride_y, 4, fw, fh, dev};
+	Img A;
 	float *wd = weights;
-	if (frame_pack(fr, A.p, pitch))
+	if (frame_stage(fr, g.frame_a, &A))
 		return 1;
 	if (!dev) {
 		if (grow(g.eaw_w, std::max<size_t>((size_t)f.total * 4, 4)))
@@ -275,7 +265,7 @@ int eaw2d(bool inverse, int layout, void *ptr, int stride_x, int stride_y, const
 		return 1;
 	if (!dev && !inverse)
 		HIP_TRY(hipMemcpyAsync(weights, wd, (size_t)f.total * 4, hipMemcpyDeviceToHost, g.stream));
-	return frame_unpack(fr, A.p, pitch);
+	return frame_unpack(fr, A.p, A.sx);
 }
 
 } // namespace

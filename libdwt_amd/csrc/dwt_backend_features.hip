@@ -131,12 +131,6 @@ int carve(long nrec, long npart, int nb, bool select, Ws *w)
 	return 0;
 }
 
-int launched(hipError_t e, const char *what)
-{
-	g.stat_launches++;
-	return e == hipSuccess ? 0 : fail("feature %s launch failed: %s", what, hipGetErrorString(e));
-}
-
 // this driver counts the pack launch of a device frame among its own
 int pack(const Frame &f, void *dense, long pitch)
 {
@@ -183,7 +177,7 @@ int run_device(Img d, long bstride, int batch, const Band *bands, int nb, bool l
 		a.work = (pass2 ? kFeatPass2 : 0) | (select ? kFeatSelect : 0);
 		a.pmode = pmode;
 		a.p = p;
-		if (launched(launch_feat_lines(a, g.stream), "line"))
+		if (launched(launch_feat_lines(a, g.stream), "feature", "line"))
 			return 1;
 	} else {
 		static thread_local FeatBand tab[FEAT_MAX_BANDS]; // (outlives the asynchronous copy below; the call ends synchronised)
@@ -224,14 +218,14 @@ int run_device(Img d, long bstride, int batch, const Band *bands, int nb, bool l
 		a.mn = mom.n;
 		a.c = mom.c;
 		a.groups = g.feat_groups;
-		if (launched(launch_feat_pass1(a, g.stream), "pass 1") || launched(launch_feat_fold(a, 0, g.stream), "fold"))
+		if (launched(launch_feat_pass1(a, g.stream), "feature", "pass 1") || launched(launch_feat_fold(a, 0, g.stream), "feature", "fold"))
 			return 1;
-		if (pass2 && (launched(launch_feat_pass2(a, g.stream), "pass 2") || launched(launch_feat_fold(a, 1, g.stream), "fold")))
+		if (pass2 && (launched(launch_feat_pass2(a, g.stream), "feature", "pass 2") || launched(launch_feat_fold(a, 1, g.stream), "feature", "fold")))
 			return 1;
 		if (select) {
 			HIP_TRY(hipMemsetAsync(ws.hist, 0, ws.hist_bytes, g.stream));
 			for (int pass = 0; pass < 4; pass++)
-				if (launched(launch_feat_hist(a, pass, g.stream), "histogram") || launched(launch_feat_pick(a, pass, g.stream), "pick"))
+				if (launched(launch_feat_hist(a, pass, g.stream), "feature", "histogram") || launched(launch_feat_pick(a, pass, g.stream), "feature", "pick"))
 					return 1;
 		}
 	}
@@ -298,7 +292,7 @@ int stage(const void *ptr, bool dev, long bstride, int batch, long stride_x, lon
 		*dbs = bstride;
 		return 0;
 	}
-	const long pitch = align_up(4l * fw, 256);
+	const long pitch = frame_pitch(4, fw);
 	if (grow(g.frame_a, (size_t)pitch * fh * batch))
 		return 1;
 	// the whole batch as ONE image of fh * batch rows where its rows are evenly apart: rows of one-row frames, or
@@ -340,8 +334,8 @@ int features(unsigned mask, const void *ptr, long bstride, int batch, long strid
 	const bool fv_dev = dwt_hip_is_device_pointer(fv);
 	if (fv_follows_ptr ? dev != fv_dev : fv_dev)
 		return fail(fv_follows_ptr ? "the image and the feature vector must both be host or both be device memory" : "the feature vector must be host memory");
-	if (dev && (stride_y % 4 || stride_x % 4 || (uintptr_t)ptr % 4 || bstride % 4))
-		return fail("device images take strides and addresses that are multiples of 4 bytes (stride_x %ld, stride_y %ld)", stride_x, stride_y);
+	if (dev && check_dev_align({ptr}, {stride_x, stride_y, bstride}))
+		return 1;
 	if (stride_y < 4 || (ge.soy > 1 && stride_x < 4))
 		return fail("bad strides: %ld, %ld bytes", stride_x, stride_y);
 	if (nb == 0 || batch == 0)
@@ -364,6 +358,20 @@ int features(unsigned mask, const void *ptr, long bstride, int batch, long strid
 }
 
 bool bad_sizes(int sox, int soy, int six, int siy) { return sox < 0 || soy < 0 || six < 0 || siy < 0 || six > sox || siy > soy; }
+
+// the two entries that take one image with its frame sizes: the bands of dwt_util_subband, every feature of the mask
+int features2d(unsigned mask, const void *ptr, int stride_x, int stride_y, int sox, int soy, int six, int siy, int j_max, float p, float *fv,
+	bool fv_follows_ptr)
+{
+	if (check_inited() || check_request(mask, ptr, fv, p))
+		return 1;
+	if (bad_sizes(sox, soy, six, siy))
+		return fail("bad sizes: outer %d x %d, inner %d x %d", sox, soy, six, siy);
+	const Geom ge{sox, soy, six, siy};
+	Band bands[FEAT_MAX_BANDS];
+	const int nb = enum_bands(ge, j_max, bands);
+	return features(mask, ptr, 0, 1, stride_x, stride_y, ge, bands, nb, p, Moment{}, fv, 0, fv_follows_ptr);
+}
 
 // The features of every level's H (band 0) or L (band 1) plane of the stationary transform of `n_lines` dense device
 // lines -> fv (HOST memory), feature k of level l of line y at fv[y*fv_stride + k*levels + l].  Lines the fused kernel
@@ -394,7 +402,7 @@ int swt_features_device(Wavelet w, unsigned mask, const char *src, long ls, int 
 		a.work = ((mask & kMomentFeatures) ? kFeatPass2 : 0) | ((mask & DWT_HIP_FEATURE_BIT(DWT_HIP_FEATURE_MED)) ? kFeatSelect : 0);
 		a.pmode = pmode_of(mask, p);
 		a.p = p;
-		if (launched(launch_swt_lines(w, true, a, g.stream), "SWT line"))
+		if (launched(launch_swt_lines(w, true, a, g.stream), "feature", "SWT line"))
 			return 1;
 		return finish_records(ws.rec, nrec, n_lines, bands, levels, mask, a.pmode, p, Moment{}, fv, fv_stride);
 	}
@@ -437,27 +445,13 @@ int dwt_hip_count_subbands(int size_o_x, int size_o_y, int size_i_x, int size_i_
 int dwt_hip_features2d(unsigned feature_mask, const void *ptr, int stride_x, int stride_y, int size_o_x, int size_o_y, int size_i_x,
 	int size_i_y, int j_max, float p, float *fv)
 {
-	if (check_inited() || check_request(feature_mask, ptr, fv, p))
-		return 1;
-	if (bad_sizes(size_o_x, size_o_y, size_i_x, size_i_y))
-		return fail("bad sizes: outer %d x %d, inner %d x %d", size_o_x, size_o_y, size_i_x, size_i_y);
-	const Geom ge{size_o_x, size_o_y, size_i_x, size_i_y};
-	Band bands[FEAT_MAX_BANDS];
-	const int nb = enum_bands(ge, j_max, bands);
-	return features(feature_mask, ptr, 0, 1, stride_x, stride_y, ge, bands, nb, p, Moment{}, fv, 0, true);
+	return features2d(feature_mask, ptr, stride_x, stride_y, size_o_x, size_o_y, size_i_x, size_i_y, j_max, p, fv, true);
 }
 
 int dwt_hip_features2d_hostfv(unsigned feature_mask, const void *ptr, int stride_x, int stride_y, int size_o_x, int size_o_y, int size_i_x,
 	int size_i_y, int j_max, float p, float *fv)
 {
-	if (check_inited() || check_request(feature_mask, ptr, fv, p))
-		return 1;
-	if (bad_sizes(size_o_x, size_o_y, size_i_x, size_i_y))
-		return fail("bad sizes: outer %d x %d, inner %d x %d", size_o_x, size_o_y, size_i_x, size_i_y);
-	const Geom ge{size_o_x, size_o_y, size_i_x, size_i_y};
-	Band bands[FEAT_MAX_BANDS];
-	const int nb = enum_bands(ge, j_max, bands);
-	return features(feature_mask, ptr, 0, 1, stride_x, stride_y, ge, bands, nb, p, Moment{}, fv, 0, false);
+	return features2d(feature_mask, ptr, stride_x, stride_y, size_o_x, size_o_y, size_i_x, size_i_y, j_max, p, fv, false);
 }
 
 long dwt_hip_features_raw_sums(int plane, double *out, long n)
@@ -496,28 +490,9 @@ int dwt_hip_features1d_batch(unsigned feature_mask, const void *ptr, size_t line
 	const Geom ge{size, 1, size, 1};
 	Band bands[FEAT_MAX_BANDS];
 	const int nb = enum_bands(ge, j_max, bands);
-	if (elem_stride == 4) // n_lines frames of one row each
-		return features(feature_mask, ptr, (long)line_stride, n_lines, 4l * size, 4, ge, bands, nb, p, Moment{}, fv, (long)fv_stride, true);
-	// strided elements: the lines packed as the rows of one dense image, then taken as n_lines frames of one row
-	const bool dev = dwt_hip_is_device_pointer(ptr);
-	if (dev != (bool)dwt_hip_is_device_pointer(fv))
-		return fail("the image and the feature vector must both be host or both be device memory");
-	if (dev && (elem_stride % 4 || line_stride % 4 || (uintptr_t)ptr % 4))
-		return fail("device lines take strides and addresses that are multiples of 4 bytes");
-	if (nb == 0 || n_lines == 0)
-		return 0;
-	const long pitch = align_up(4l * size, 256);
-	if (grow(g.frame_b, (size_t)pitch * n_lines))
-		return 1;
-	if (pack(Frame{(void *)ptr, (long)line_stride, (long)elem_stride, 4, size, n_lines, dev}, g.frame_b.p, pitch))
-		return 1;
-	if (!dev) { // the packed lines are device memory, the vector is not: finish into it directly
-		const bool lines = size <= N1D_MAX && nb <= 32;
-		if (n_lines > 1 && fv_stride < (size_t)popcount(feature_mask) * nb)
-			return fail("feature stride %zu floats, one line takes %d", fv_stride, popcount(feature_mask) * nb);
-		return run_device(Img{(char *)g.frame_b.p, pitch, 4}, pitch, n_lines, bands, nb, lines, size, feature_mask, p, Moment{}, fv, (long)fv_stride);
-	}
-	return features(feature_mask, g.frame_b.p, pitch, n_lines, 4l * size, 4, ge, bands, nb, p, Moment{}, fv, (long)fv_stride, true);
+	// n_lines frames of one row each; strided elements: stage() packs the lines as the rows of one dense image
+	return features(feature_mask, ptr, (long)line_stride, n_lines, (long)elem_stride * size, (long)elem_stride, ge, bands, nb, p, Moment{}, fv,
+		(long)fv_stride, true);
 }
 
 int dwt_hip_swt_features1d_batch(int wavelet, unsigned feature_mask, const void *src, size_t line_stride, size_t elem_stride, int n_lines, int N,
@@ -542,22 +517,16 @@ int dwt_hip_swt_features1d_batch(int wavelet, unsigned feature_mask, const void 
 	const bool dev = dwt_hip_is_device_pointer(src);
 	if (dev != (bool)dwt_hip_is_device_pointer(fv))
 		return fail("the lines and the feature vector must both be host or both be device memory");
-	if (dev && (elem_stride % 4 || line_stride % 4 || (uintptr_t)src % 4))
-		return fail("device lines take strides and addresses that are multiples of 4 bytes");
+	if (dev && check_dev_align({src}, {(long)elem_stride, (long)line_stride}))
+		return 1;
 	if (n_lines == 0 || N == 0 || levels == 0)
 		return 0;
 	// dense device lines run where they lie; everything else is packed into the context's dense device image
-	const char *d = (const char *)src;
-	long ls = (long)line_stride;
-	if (!dev || elem_stride != 4) {
-		const long pitch = align_up(4l * N, 256);
-		if (grow(g.frame_a, (size_t)pitch * n_lines))
-			return 1;
-		if (pack(Frame{(void *)src, (long)line_stride, (long)elem_stride, 4, N, n_lines, dev}, g.frame_a.p, pitch))
-			return 1;
-		d = (const char *)g.frame_a.p;
-		ls = pitch;
-	}
+	Img A;
+	long ls = 0;
+	if (stage(src, dev, (long)line_stride, n_lines, (long)elem_stride * N, (long)elem_stride, N, 1, &A, &ls))
+		return 1;
+	const char *d = A.p;
 	if (!dev)
 		return swt_features_device(w, feature_mask, d, ls, n_lines, N, levels, band, p, fv, fv_line_stride);
 	const long block = (long)nf * levels;
@@ -612,19 +581,15 @@ int dwt_hip_abs(void *ptr, int stride_x, int stride_y, int size_x, int size_y)
 		return fail("bad sizes: %d x %d", size_x, size_y);
 	if (size_x == 0 || size_y == 0)
 		return 0;
-	if (dwt_hip_is_device_pointer(ptr)) {
-		if (stride_y % 4 || stride_x % 4 || (uintptr_t)ptr % 4 || stride_y < 4)
-			return fail("device images take strides and addresses that are multiples of 4 bytes (stride_x %d, stride_y %d)", stride_x, stride_y);
-		return launched(launch_feat_abs(ptr, stride_x, stride_y, size_x, size_y, g.stream), "abs");
-	}
 	if (stride_y < 4)
 		return fail("bad strides: %d, %d bytes", stride_x, stride_y);
-	const long pitch = align_up(4l * size_x, 256);
+	if (dwt_hip_is_device_pointer(ptr))
+		return check_dev_align({ptr}, {stride_x, stride_y}) || launched(launch_feat_abs(ptr, stride_x, stride_y, size_x, size_y, g.stream), "feature", "abs");
 	const Frame fr{ptr, stride_x, stride_y, 4, size_x, size_y, false};
-	if (grow(g.frame_a, (size_t)pitch * size_y) || frame_pack(fr, g.frame_a.p, pitch) ||
-		launched(launch_feat_abs(g.frame_a.p, pitch, 4, size_x, size_y, g.stream), "abs"))
+	Img A;
+	if (frame_stage(fr, g.frame_a, &A) || launched(launch_feat_abs(A.p, A.sx, 4, size_x, size_y, g.stream), "feature", "abs"))
 		return 1;
-	return frame_unpack(fr, g.frame_a.p, pitch);
+	return frame_unpack(fr, A.p, A.sx);
 }
 
 } // extern "C"

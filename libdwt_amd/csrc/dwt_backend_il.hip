@@ -458,16 +458,13 @@ int dwt_hip_transform2d_interleaved(int wavelet, int inverse, int flavour, const
 		return fail("device image: stride_y %d must be >= 4 and stride_x %d >= (width-1)*stride_y + 4", stride_y, stride_x);
 	// host pointers (any byte strides), device images whose elements are not adjacent or not aligned: the outer frame
 	// takes the staging detour (dwt_backend.h)
-	const long pitch = align_up((long)sox * 4, 256);
-	if (grow(g.frame_a, (size_t)pitch * soy))
-		return 1;
-	Img A{(char *)g.frame_a.p, pitch, 4};
-	if (frame_pack(Frame{(void *)src, stride_x, stride_y, 4, sox, soy, dev_dst}, A.p, pitch))
+	Img A;
+	if (frame_stage(Frame{(void *)src, stride_x, stride_y, 4, sox, soy, dev_dst}, g.frame_a, &A))
 		return 1;
 	if (fixed ? inplace_int2d(inverse != 0, A, A, sox, soy, six, siy, j, decompose_one)
 	          : interleaved2d(w, inverse != 0, scale_single, A, A, sox, soy, six, siy, j, decompose_one, dirs))
 		return 1;
-	return frame_unpack(Frame{dst, stride_x, stride_y, 4, sox, soy, dev_dst}, A.p, pitch);
+	return frame_unpack(Frame{dst, stride_x, stride_y, 4, sox, soy, dev_dst}, A.p, A.sx);
 }
 
 } // extern "C"

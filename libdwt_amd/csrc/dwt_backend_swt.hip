@@ -11,22 +11,6 @@
 
 namespace dwtb {
 
-namespace {
-
-int launched(hipError_t e, const char *what)
-{
-	g.stat_launches++;
-	return e == hipSuccess ? 0 : fail("SWT %s launch failed: %s", what, hipGetErrorString(e));
-}
-
-bool overlap(const void *a, size_t na, const void *b, size_t nb)
-{
-	const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-	return na && nb && pa < pb + nb && pb < pa + na;
-}
-
-} // namespace
-
 bool swt_fused_ok(const void *src, long ls, long es, int N)
 {
 	return g.swt_fused && N <= N1D_MAX && es == 4 && ls % 4 == 0 && (uintptr_t)src % 4 == 0;
@@ -39,9 +23,8 @@ int swt_device(Wavelet w, const char *src, long ls, long es, int n_lines, int N,
 {
 	if (n_lines <= 0 || levels <= 0 || N <= 0)
 		return 0;
-	if (es % 4 || ls % 4 || (uintptr_t)src % 4 || h_es % 4 || (uintptr_t)dst_h % 4 || plane_stride % 4 || dls % 4 ||
-		(l_mode && (l_es % 4 || (uintptr_t)dst_l % 4)))
-		return fail("device lines take strides and addresses that are multiples of 4 bytes");
+	if (check_dev_align({src, dst_h, l_mode ? dst_l : nullptr}, {es, ls, h_es, plane_stride, dls, l_mode ? l_es : 0}))
+		return 1;
 	if (dst_h && swt_fused_ok(src, ls, es, N) && h_es == 4 && (!l_mode || l_es == 4)) {
 		SwtLineArgs a{};
 		a.src = src;
@@ -56,7 +39,7 @@ int swt_device(Wavelet w, const char *src, long ls, long es, int n_lines, int N,
 		a.plane_stride = plane_stride;
 		a.dst_line_stride = dls;
 		a.l_mode = l_mode;
-		return launched(launch_swt_lines(w, false, a, g.stream), "line");
+		return launched(launch_swt_lines(w, false, a, g.stream), "SWT", "line");
 	}
 	// level by level: the L chain through two dense scratch images
 	const long pitch = 4l * N;
@@ -85,7 +68,7 @@ int swt_device(Wavelet w, const char *src, long ls, long es, int n_lines, int N,
 		a.out_h = dst_h ? dst_h + (long)l * plane_stride : nullptr; // (null: the level passes of an L-only caller)
 		a.h_ls = dls;
 		a.h_es = h_es;
-		if (launched(launch_swt_level(w, a, g.stream), "level"))
+		if (launched(launch_swt_level(w, a, g.stream), "SWT", "level"))
 			return 1;
 	}
 	return 0;
@@ -133,25 +116,15 @@ int swt1d(int wavelet, const void *src, long ls, long es, int n_lines, int N, in
 	const Frame fs{(void *)src, ls, es, 4, N, n_lines, false}, fh{dst_h, dls, h_es, 4, N, n_lines, false}, fl{dst_l, dls, l_es, 4, N, n_lines, false};
 	if (frame_check(fs) || frame_check(fh) || frame_check(fl))
 		return 1;
-	const long pitch = align_up(4l * N, 256), plane = pitch * n_lines;
+	const long pitch = frame_pitch(4, N), plane = pitch * n_lines;
 	const int l_planes = l_mode == 2 ? levels : l_mode;
-	if (grow(g.frame_a, (size_t)plane) || grow(g.frame_b, (size_t)plane * (levels + l_planes)))
+	Img A;
+	if (grow(g.frame_b, (size_t)plane * (levels + l_planes)) || frame_stage(fs, g.frame_a, &A))
 		return 1;
 	char *dh = (char *)g.frame_b.p, *dl = dh + (size_t)plane * levels;
-	if (frame_pack(fs, g.frame_a.p, pitch) ||
-		swt_device(w, (const char *)g.frame_a.p, pitch, 4, n_lines, N, level0, levels, dh, 4, dl, 4, l_mode, plane, pitch))
+	if (swt_device(w, A.p, pitch, 4, n_lines, N, level0, levels, dh, 4, dl, 4, l_mode, plane, pitch))
 		return 1;
-	auto plane_of = [&](Frame f, int l) {
-		f.p = (char *)f.p + (long)l * plane_stride;
-		return f;
-	};
-	for (int l = 0; l < levels; l++)
-		if (frame_unpack(plane_of(fh, l), dh + (size_t)plane * l, pitch))
-			return 1;
-	for (int l = 0; l < l_planes; l++)
-		if (frame_unpack(plane_of(fl, l), dl + (size_t)plane * l, pitch))
-			return 1;
-	return 0;
+	return frame_unpack_stack(fh, levels, plane_stride, dh, pitch) || frame_unpack_stack(fl, l_planes, plane_stride, dl, pitch);
 }
 
 } // namespace dwtb

@@ -30,18 +30,6 @@ namespace dwtb {
 
 namespace {
 
-int launched(hipError_t e, const char *what)
-{
-	g.stat_launches++;
-	return e == hipSuccess ? 0 : fail("timefreq %s launch failed: %s", what, hipGetErrorString(e));
-}
-
-bool overlap(const void *a, size_t na, const void *b, size_t nb)
-{
-	const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-	return na && nb && pa < pb + nb && pb < pa + na;
-}
-
 void bank_drop_device(dwt_hip_timefreq_bank *b)
 {
 	for (void **p : {&b->d_taps, &b->d_bins, &b->d_order})
@@ -81,9 +69,7 @@ int bank_upload(dwt_hip_timefreq_bank *b)
 int tf_device(dwt_hip_timefreq_bank *b, const char *src, long ls, long es, int n_lines, int N, int t0, int nt, int out, char *dst,
 	long plane_stride, long row_stride, long dst_es)
 {
-	if (es % 4 || ls % 4 || (uintptr_t)src % 4 || plane_stride % 4 || row_stride % 4 || dst_es % 4 || (uintptr_t)dst % 4)
-		return fail("device lines and planes take strides and addresses that are multiples of 4 bytes");
-	if (bank_upload(b))
+	if (check_dev_align({src, dst}, {es, ls, plane_stride, row_stride, dst_es}) || bank_upload(b))
 		return 1;
 	TfArgs a{};
 	a.src = src;
@@ -103,8 +89,8 @@ int tf_device(dwt_hip_timefreq_bank *b, const char *src, long ls, long es, int n
 	a.row_stride = row_stride;
 	a.dst_es = dst_es;
 	if (g.tf_tiled && b->finite && es == 4)
-		return launched(launch_tf_tiled(a, g.stream), "tiled");
-	return launched(launch_tf_plain(a, g.stream), "plain");
+		return launched(launch_tf_tiled(a, g.stream), "timefreq", "tiled");
+	return launched(launch_tf_plain(a, g.stream), "timefreq", "plain");
 }
 
 // host or device memory (both sides alike): the checks of the C-ABI entries.  Outputs t0 .. t0+nt-1 of every line.
@@ -142,21 +128,15 @@ int timefreq(dwt_hip_timefreq_bank *b, const void *src, long ls, long es, int n_
 
 	// host memory: a dense device image of the lines, dense device planes, each plane spread back
 	const Frame fs{(void *)src, ls, es, 4, N, n_lines, false};
-	Frame fd{dst, row_stride, dst_es, osz, nt, b->bins, false};
+	const Frame fd{dst, row_stride, dst_es, osz, nt, b->bins, false};
 	if (frame_check(fs) || frame_check(fd))
 		return 1;
-	const long spitch = align_up(4l * N, 256), dpitch = align_up((long)osz * nt, 256), plane = dpitch * b->bins;
-	if (grow(g.frame_a, (size_t)spitch * n_lines) || grow(g.frame_b, (size_t)plane * n_lines))
+	const long dpitch = frame_pitch(osz, nt), plane = dpitch * b->bins;
+	Img A;
+	if (grow(g.frame_b, (size_t)plane * n_lines) || frame_stage(fs, g.frame_a, &A) ||
+		tf_device(b, A.p, A.sx, 4, n_lines, N, t0, nt, out, (char *)g.frame_b.p, plane, dpitch, osz))
 		return 1;
-	if (frame_pack(fs, g.frame_a.p, spitch) ||
-		tf_device(b, (const char *)g.frame_a.p, spitch, 4, n_lines, N, t0, nt, out, (char *)g.frame_b.p, plane, dpitch, osz))
-		return 1;
-	for (int y = 0; y < n_lines; y++) {
-		fd.p = (char *)dst + (long)y * plane_stride;
-		if (frame_unpack(fd, (char *)g.frame_b.p + (size_t)plane * y, dpitch))
-			return 1;
-	}
-	return 0;
+	return frame_unpack_stack(fd, n_lines, plane_stride, g.frame_b.p, dpitch);
 }
 
 // op 0: phase derivative, 1 .. 3: the ridge detectors; element (y, x) of plane p at base + p*ps + y*sx + x*sy on both sides
@@ -183,34 +163,21 @@ int plane_op(int op, const void *src, void *dst, long sx, long sy, int size_x, i
 		return fail("source and destination must both be host or both be device pointers");
 	TfPlaneArgs a{(const char *)src, (char *)dst, ps, sx, sy, size_x, size_y, n_planes, op, param};
 	if (dev) {
-		if (sx % 4 || sy % 4 || ps % 4 || (uintptr_t)src % 4 || (uintptr_t)dst % 4)
-			return fail("device planes take strides and addresses that are multiples of 4 bytes");
-		return launched(launch_tf_plane_op(a, g.stream), who);
+		return check_dev_align({src, dst}, {sx, sy, ps}) || launched(launch_tf_plane_op(a, g.stream), "timefreq", who);
 	}
-	Frame fs{(void *)src, sx, sy, 4, size_x, size_y, false}, fd{dst, sx, sy, 4, size_x, size_y, false};
+	const Frame fs{(void *)src, sx, sy, 4, size_x, size_y, false}, fd{dst, sx, sy, 4, size_x, size_y, false};
 	if (frame_check(fs) || frame_check(fd))
 		return 1;
-	const long pitch = align_up(4l * size_x, 256), plane = pitch * size_y;
-	if (grow(g.frame_a, (size_t)plane * n_planes) || grow(g.frame_b, (size_t)plane * n_planes))
+	const long pitch = frame_pitch(4, size_x), plane = pitch * size_y;
+	if (grow(g.frame_a, (size_t)plane * n_planes) || grow(g.frame_b, (size_t)plane * n_planes) ||
+		frame_pack_stack(fs, n_planes, ps, g.frame_a.p, pitch))
 		return 1;
-	for (int p = 0; p < n_planes; p++) {
-		fs.p = (char *)src + (long)p * ps;
-		if (frame_pack(fs, (char *)g.frame_a.p + (size_t)plane * p, pitch))
-			return 1;
-	}
 	a.src = (const char *)g.frame_a.p;
 	a.dst = (char *)g.frame_b.p;
 	a.ps = plane;
 	a.sx = pitch;
 	a.sy = 4;
-	if (launched(launch_tf_plane_op(a, g.stream), who))
-		return 1;
-	for (int p = 0; p < n_planes; p++) {
-		fd.p = (char *)dst + (long)p * ps;
-		if (frame_unpack(fd, (char *)g.frame_b.p + (size_t)plane * p, pitch))
-			return 1;
-	}
-	return 0;
+	return launched(launch_tf_plane_op(a, g.stream), "timefreq", who) || frame_unpack_stack(fd, n_planes, ps, g.frame_b.p, pitch);
 }
 
 bool strides_ok(size_t a, size_t b, size_t c, size_t d)

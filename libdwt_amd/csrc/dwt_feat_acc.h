@@ -1,6 +1,7 @@
-// dwt_feat_acc.h -- the accumulators and workgroup folds of the feature statistics, shared by the kernels that reduce
-// stored coefficients (dwt_features.hip) and the one that reduces coefficients as it computes them (dwt_swt1d.hip): the
-// same code, so the same order and the same bits.  Included inside namespace dwt { namespace {.
+// dwt_feat_acc.h -- the accumulators and workgroup folds of the feature statistics and the reduction of one record over
+// them (reduce_record), shared by the kernel that reduces stored lines (k_feat_lines, dwt_features.hip) and the one that
+// reduces coefficients as it computes them (k_swt_lines, dwt_swt1d.hip): the same code, so the same order and the same
+// bits.  Included inside namespace dwt { namespace {.
 #pragma once
 
 typedef unsigned long long u64;
@@ -134,4 +135,70 @@ static __device__ __forceinline__ unsigned pick_bin(const unsigned *h, unsigned 
 	const int src = m ? __ffsll((long long)m) - 1 : 0;
 	*k = __shfl(rank, src);
 	return __shfl(bin, src);
+}
+
+// The `n` values of one record -> its raw planes rec[plane * nrec + r], by the NT threads of one line (this one is t;
+// NT = 64: one wave of a shared workgroup, else the whole workgroup).  first(i) gives value i in the pass every call
+// makes (k_swt_lines computes the sample there and keeps its low-pass part), again(i) gives it to the passes that read
+// the values once more: the central moments about the float mean (work & kFeatPass2) and the four rounds of the median's
+// radix select (work & kFeatSelect).  Thread t takes values t, t + NT, ...; every thread of the workgroup meets every
+// barrier, a thread that is not `active` stores nothing.  shd, shk: 4 entries each; hist: 256; sel: 2.
+template <int NT, class First, class Again>
+static __device__ __forceinline__ void reduce_record(int t, int n, First first, Again again, long r, u64 *rec, long nrec, int work,
+	int pmode, float p, bool active, double *shd, u64 *shk, unsigned *hist, unsigned *sel)
+{
+	constexpr int NW = NT / 64;
+	Acc1 acc;
+	for (int i = t; i < n; i += NT)
+		acc.add(first(i), (unsigned)i, pmode, p);
+	const double s1 = wg_sum<NW>(acc.s1, shd), s2 = wg_sum<NW>(acc.s2, shd);
+	const double sp = pmode != kFeatPNone ? wg_sum<NW>(acc.sp, shd) : 0.0;
+	const u64 key = wg_max<NW>(acc.key, shk);
+	if (t == 0 && active) {
+		rec[kFeatS1 * nrec + r] = dbits(s1);
+		rec[kFeatS2 * nrec + r] = dbits(s2);
+		rec[kFeatSp * nrec + r] = dbits(sp);
+		rec[kFeatKey * nrec + r] = key;
+	}
+	if (work & kFeatPass2) {
+		const float c = mean_of(s1, n);
+		Acc2 m;
+		for (int i = t; i < n; i += NT)
+			m.add(again(i), c, 2);
+		const double m2 = wg_sum<NW>(m.m2, shd), m3 = wg_sum<NW>(m.m3, shd), m4 = wg_sum<NW>(m.m4, shd);
+		if (t == 0 && active) {
+			rec[kFeatM2 * nrec + r] = dbits(m2);
+			rec[kFeatM3 * nrec + r] = dbits(m3);
+			rec[kFeatM4 * nrec + r] = dbits(m4);
+		}
+	}
+	if (work & kFeatSelect) {
+		unsigned prefix = 0, rank = (unsigned)n / 2;
+		for (int pass = 0; pass < 4; pass++) {
+			const int shift = 24 - 8 * pass;
+			for (int i = t; i < 256; i += NT)
+				hist[i] = 0;
+			__syncthreads();
+			for (int i = t; i < n; i += NT) {
+				const unsigned q = okey(again(i));
+				if (pass == 0 || (q >> (shift + 8)) == prefix)
+					atomicAdd(&hist[(q >> shift) & 255], 1u);
+			}
+			__syncthreads();
+			if (t < 64) {
+				unsigned kk = rank;
+				const unsigned bin = pick_bin(hist, &kk);
+				if (t == 0) {
+					sel[0] = bin;
+					sel[1] = kk;
+				}
+			}
+			__syncthreads();
+			prefix = (prefix << 8) | sel[0];
+			rank = sel[1];
+			__syncthreads();
+		}
+		if (t == 0 && active)
+			rec[kFeatMed * nrec + r] = to_bits(okey_inv(prefix));
+	}
 }

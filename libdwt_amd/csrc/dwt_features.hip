@@ -30,7 +30,6 @@ namespace {
 template <int NT, int CAP>
 __global__ __launch_bounds__(NT) void k_feat_lines(FeatLineArgs a)
 {
-	constexpr int NW = NT / 64;
 	__shared__ float line[CAP];
 	__shared__ double shd[4];
 	__shared__ u64 shk[4];
@@ -56,59 +55,8 @@ __global__ __launch_bounds__(NT) void k_feat_lines(FeatLineArgs a)
 		const float *b = line + a.off[k];
 		const int n = a.len[k];
 		const long r = li * a.nb + k;
-		Acc1 acc;
-		for (int i = t; i < n; i += NT)
-			acc.add(b[i], (unsigned)i, a.pmode, a.p);
-		const double s1 = wg_sum<NW>(acc.s1, shd), s2 = wg_sum<NW>(acc.s2, shd);
-		const double sp = a.pmode != kFeatPNone ? wg_sum<NW>(acc.sp, shd) : 0.0;
-		const u64 key = wg_max<NW>(acc.key, shk);
-		if (t == 0) {
-			a.rec[kFeatS1 * a.nrec + r] = dbits(s1);
-			a.rec[kFeatS2 * a.nrec + r] = dbits(s2);
-			a.rec[kFeatSp * a.nrec + r] = dbits(sp);
-			a.rec[kFeatKey * a.nrec + r] = key;
-		}
-		if (a.work & kFeatPass2) {
-			const float c = mean_of(s1, n);
-			Acc2 m;
-			for (int i = t; i < n; i += NT)
-				m.add(b[i], c, 2);
-			const double m2 = wg_sum<NW>(m.m2, shd), m3 = wg_sum<NW>(m.m3, shd), m4 = wg_sum<NW>(m.m4, shd);
-			if (t == 0) {
-				a.rec[kFeatM2 * a.nrec + r] = dbits(m2);
-				a.rec[kFeatM3 * a.nrec + r] = dbits(m3);
-				a.rec[kFeatM4 * a.nrec + r] = dbits(m4);
-			}
-		}
-		if (a.work & kFeatSelect) {
-			unsigned prefix = 0, rank = (unsigned)n / 2;
-			for (int pass = 0; pass < 4; pass++) {
-				const int shift = 24 - 8 * pass;
-				for (int i = t; i < 256; i += NT)
-					hist[i] = 0;
-				__syncthreads();
-				for (int i = t; i < n; i += NT) {
-					const unsigned q = okey(b[i]);
-					if (pass == 0 || (q >> (shift + 8)) == prefix)
-						atomicAdd(&hist[(q >> shift) & 255], 1u);
-				}
-				__syncthreads();
-				if (t < 64) {
-					unsigned kk = rank;
-					const unsigned bin = pick_bin(hist, &kk);
-					if (t == 0) {
-						sel[0] = bin;
-						sel[1] = kk;
-					}
-				}
-				__syncthreads();
-				prefix = (prefix << 8) | sel[0];
-				rank = sel[1];
-				__syncthreads();
-			}
-			if (t == 0)
-				a.rec[kFeatMed * a.nrec + r] = to_bits(okey_inv(prefix));
-		}
+		auto x = [&](int i) { return b[i]; };
+		reduce_record<NT>(t, n, x, x, r, a.rec, a.nrec, a.work, a.pmode, a.p, true, shd, shk, hist, sel);
 	}
 }
 

@@ -172,6 +172,31 @@ int frame_unpack(const Frame &f, const void *dense, long pitch)
 	return frame_check(f) || host_download(f.p, (int)f.sx, (int)f.sy, f.es, f.w, f.h, dense, pitch);
 }
 
+int frame_stage(const Frame &f, Buf &buf, Img *dense)
+{
+	const long pitch = frame_pitch(f.es, f.w);
+	if (grow(buf, (size_t)pitch * f.h))
+		return 1;
+	*dense = Img{(char *)buf.p, pitch, f.es};
+	return frame_pack(f, buf.p, pitch);
+}
+
+int frame_pack_stack(Frame f, int n, long plane_stride, void *stack, long pitch)
+{
+	for (int k = 0; k < n; k++, f.p = (char *)f.p + plane_stride)
+		if (frame_pack(f, (char *)stack + (size_t)pitch * f.h * k, pitch))
+			return 1;
+	return 0;
+}
+
+int frame_unpack_stack(Frame f, int n, long plane_stride, const void *stack, long pitch)
+{
+	for (int k = 0; k < n; k++, f.p = (char *)f.p + plane_stride)
+		if (frame_unpack(f, (const char *)stack + (size_t)pitch * f.h * k, pitch))
+			return 1;
+	return 0;
+}
+
 // A host volume with awkward strides (libdwt's own "optimal" strides are odd numbers of bytes: a 2-D copy with such a
 // pitch runs at 1 GB/s, scripts/archive/probes/r04_oddpitch_probe.py) <-> a device volume: batches of slices of about 32 MiB
 // are repacked by the row pool into / out of the halves of a pinned buffer laid out like the device volume, one copy

@@ -21,6 +21,7 @@
 // At N1D_MAX = 8192 the inverse takes 56 KiB: two workgroups per CU (160 KiB).
 #include "dwt_kernels.h"
 #include "dwt_lift.h"
+#include "dwt_line_lds.h"
 
 namespace dwt {
 
@@ -51,19 +52,8 @@ __global__ __launch_bounds__(256) void k_line_levels(const char *__restrict__ sr
 	char *d = dst + (long)line * line_stride;
 	auto st = [&](int i, T v) { *(T *)(d + (long)i * elem_stride) = v; };
 
-	// the whole line into A: 16 B per lane where the line is dense and aligned, one element per lane otherwise
-	if (active) {
-		if (vec) {
-			const int n4 = N >> 2;
-			for (int i = t; i < n4; i += tpl)
-				*(float4 *)(A + 4 * i) = *(const float4 *)(s + 16l * i);
-			for (int i = 4 * n4 + t; i < N; i += tpl)
-				A[i] = *(const T *)(s + 4l * i);
-		} else {
-			for (int i = t; i < N; i += tpl)
-				A[i] = *(const T *)(s + (long)i * elem_stride);
-		}
-	}
+	if (active)
+		line_to_lds(A, s, N, elem_stride, t, tpl, vec);
 
 	if (!INV) {
 		T *cur = A, *nxt = B;

@@ -24,6 +24,7 @@
 // strided elements, and the cross-check of the fused kernel (option "swt_fused" = 0).
 #include "dwt_device.h"
 #include "dwt_kernels.h"
+#include "dwt_line_lds.h"
 
 namespace dwt {
 
@@ -92,7 +93,7 @@ static __device__ __forceinline__ void swt_point(X x, I p, I u, I n, float *lo, 
 template <class F, bool FEAT, int NT, int CAP>
 __global__ __launch_bounds__(256) void k_swt_lines(SwtLineArgs a)
 {
-	constexpr int LPW = 256 / NT, NW = NT / 64;
+	constexpr int LPW = 256 / NT;
 	__shared__ float buf[LPW][2][CAP];
 	__shared__ double shd[4];
 	__shared__ u64 shk[4];
@@ -106,16 +107,7 @@ __global__ __launch_bounds__(256) void k_swt_lines(SwtLineArgs a)
 	const char *s = a.src + line * a.line_stride;
 	float *cur = buf[sub][0], *nxt = buf[sub][1];
 
-	if (a.vec) {
-		const int n4 = N >> 2;
-		for (int i = t; i < n4; i += NT)
-			*(float4 *)(cur + 4 * i) = *(const float4 *)(s + 16l * i);
-		for (int i = 4 * n4 + t; i < N; i += NT)
-			cur[i] = *(const float *)(s + 4l * i);
-	} else {
-		for (int i = t; i < N; i += NT)
-			cur[i] = *(const float *)(s + 4l * i);
-	}
+	line_to_lds(cur, s, N, 4, t, NT, a.vec);
 
 	for (int l = 0; l < a.levels; l++) {
 		__syncthreads();
@@ -148,64 +140,13 @@ __global__ __launch_bounds__(256) void k_swt_lines(SwtLineArgs a)
 				swt_point<F, int>(x, p, u, N, &lo, &hi);
 				return hi;
 			};
-			const long r = line * a.levels + l;
-			Acc1 acc;
-			for (int p = t; p < N; p += NT) {
+			auto first = [&](int p) {
 				float lo, hi;
 				swt_point<F, int>(x, p, u, N, &lo, &hi);
-				nxt[p] = lo;
-				acc.add(band ? lo : hi, (unsigned)p, a.pmode, a.p);
-			}
-			const double s1 = wg_sum<NW>(acc.s1, shd), s2 = wg_sum<NW>(acc.s2, shd);
-			const double sp = a.pmode != kFeatPNone ? wg_sum<NW>(acc.sp, shd) : 0.0;
-			const u64 key = wg_max<NW>(acc.key, shk);
-			if (t == 0 && active) {
-				a.rec[kFeatS1 * a.nrec + r] = dbits(s1);
-				a.rec[kFeatS2 * a.nrec + r] = dbits(s2);
-				a.rec[kFeatSp * a.nrec + r] = dbits(sp);
-				a.rec[kFeatKey * a.nrec + r] = key;
-			}
-			if (a.work & kFeatPass2) {
-				const float c = mean_of(s1, N);
-				Acc2 m;
-				for (int p = t; p < N; p += NT)
-					m.add(val(p), c, 2);
-				const double m2 = wg_sum<NW>(m.m2, shd), m3 = wg_sum<NW>(m.m3, shd), m4 = wg_sum<NW>(m.m4, shd);
-				if (t == 0 && active) {
-					a.rec[kFeatM2 * a.nrec + r] = dbits(m2);
-					a.rec[kFeatM3 * a.nrec + r] = dbits(m3);
-					a.rec[kFeatM4 * a.nrec + r] = dbits(m4);
-				}
-			}
-			if (a.work & kFeatSelect) {
-				unsigned prefix = 0, rank = (unsigned)N / 2;
-				for (int pass = 0; pass < 4; pass++) {
-					const int shift = 24 - 8 * pass;
-					for (int i = t; i < 256; i += NT)
-						hist[sub][i] = 0;
-					__syncthreads();
-					for (int p = t; p < N; p += NT) {
-						const unsigned q = okey(val(p));
-						if (pass == 0 || (q >> (shift + 8)) == prefix)
-							atomicAdd(&hist[sub][(q >> shift) & 255], 1u);
-					}
-					__syncthreads();
-					if (t < 64) {
-						unsigned kk = rank;
-						const unsigned bin = pick_bin(hist[sub], &kk);
-						if (t == 0) {
-							sel[sub][0] = bin;
-							sel[sub][1] = kk;
-						}
-					}
-					__syncthreads();
-					prefix = (prefix << 8) | sel[sub][0];
-					rank = sel[sub][1];
-					__syncthreads();
-				}
-				if (t == 0 && active)
-					a.rec[kFeatMed * a.nrec + r] = to_bits(okey_inv(prefix));
-			}
+				out[p] = lo;
+				return band ? lo : hi;
+			};
+			reduce_record<NT>(t, N, first, val, line * a.levels + l, a.rec, a.nrec, a.work, a.pmode, a.p, active, shd, shk, hist[sub], sel[sub]);
 		}
 		float *const q = cur;
 		cur = nxt;

@@ -11,6 +11,7 @@ import pytest
 
 import eaw_model as M
 from conftest import full_range_floats, same_floats
+from hipdev import Dev
 
 pytestmark = pytest.mark.gpu
 warnings.filterwarnings("ignore", category=RuntimeWarning)
@@ -66,30 +67,10 @@ def weights_ok(got, want):
     return len(got) == len(want) and all(M.same_weights(g, w) for g, w in zip(got, want))
 
 
-class DevArr:
-    """A numpy array's copy in device memory (dwt_hip_malloc): data_ptr() and numpy() as a tensor would give them."""
-
-    def __init__(self, arr):
-        import libdwt_amd as d
-
-        self.lib, self.a = d.lib, np.ascontiguousarray(arr)
-        self.p = self.lib.dwt_hip_malloc(max(self.a.nbytes, 1))
-        assert self.p and self.lib.dwt_hip_memcpy_h2d(self.p, self.a.ctypes.data, self.a.nbytes) == 0
-
-    def data_ptr(self):
-        return self.p
-
-    def numpy(self):
-        out = np.empty_like(self.a)
-        assert self.lib.dwt_hip_memcpy_d2h(out.ctypes.data, self.p, out.nbytes) == 0
-        return out
-
-    def __del__(self):
-        self.lib.dwt_hip_free(self.p)
-
-
 def to_device(arr):
-    return DevArr(arr)
+    import libdwt_amd as d
+
+    return Dev(d, arr)
 
 
 @pytest.mark.parametrize("interleaved", [False, True], ids=["mallat", "interleaved"])
@@ -115,11 +96,11 @@ def test_device_bit_exact(dwt, ref, shape, interleaved):
     img = np.random.default_rng(w).random((h, w), dtype=np.float32)
     want, jw, wHw, wVw = expect_fwd(ref, img, interleaved, j_max=5)
     d = to_device(img)
-    jg, wH, wV = fwd_fn(dwt, interleaved)(d.data_ptr(), w * 4, 4, w, h, w, h, 5, 0, 0)
-    assert jg == jw and same_floats(d.numpy(), want)
+    jg, wH, wV = fwd_fn(dwt, interleaved)(d.ptr, w * 4, 4, w, h, w, h, 5, 0, 0)
+    assert jg == jw and same_floats(d.get(), want)
     assert weights_ok(wH, wHw) and weights_ok(wV, wVw)
-    inv_fn(dwt, interleaved)(d.data_ptr(), w * 4, 4, w, h, w, h, jg, 0, 0, wH, wV)
-    assert same_floats(d.numpy(), expect_inv(ref, want, wHw, wVw, interleaved, j_max=jw))
+    inv_fn(dwt, interleaved)(d.ptr, w * 4, 4, w, h, w, h, jg, 0, 0, wH, wV)
+    assert same_floats(d.get(), expect_inv(ref, want, wHw, wVw, interleaved, j_max=jw))
 
 
 @pytest.mark.parametrize("where", ["host", "device"])
@@ -134,8 +115,8 @@ def test_prime_pitch(dwt, ref, where, interleaved):
     want, jw, wHw, wVw = expect_fwd(ref, img, interleaved, j_max=3)
     if where == "device":
         d = to_device(buf)
-        jg, wH, wV = fwd_fn(dwt, interleaved)(d.data_ptr(), pitch, 4, w, h, w, h, 3, 0, 0)
-        out = d.numpy()
+        jg, wH, wV = fwd_fn(dwt, interleaved)(d.ptr, pitch, 4, w, h, w, h, 3, 0, 0)
+        out = d.get()
     else:
         out = buf.copy()
         jg, wH, wV = fwd_fn(dwt, interleaved)(out.ctypes.data, pitch, 4, w, h, w, h, 3, 0, 0)
@@ -152,8 +133,8 @@ def test_one_channel_of_three(dwt, ref, where):
     want, jw, wHw, wVw = expect_fwd(ref, rgb[:, :, 1], j_max=-1)
     if where == "device":
         d = to_device(rgb)
-        jg, wH, wV = dwt.dwt_eaw53_2f_s(d.data_ptr() + 4, w * 12, 12, w, h, w, h, -1, 0, 0)
-        out = d.numpy()
+        jg, wH, wV = dwt.dwt_eaw53_2f_s(d.ptr + 4, w * 12, 12, w, h, w, h, -1, 0, 0)
+        out = d.get()
     else:
         out = rgb.copy()
         jg, wH, wV = dwt.dwt_eaw53_2f_s(out.ctypes.data + 4, w * 12, 12, w, h, w, h, -1, 0, 0)
@@ -170,11 +151,11 @@ def test_full_float_range(dwt, ref, klass, two_pass):
     d = to_device(img)
     dwt.set_option("eaw_two_pass", two_pass)
     try:
-        jg, wH, wV = dwt.dwt_eaw53_2f_s(d.data_ptr(), w * 4, 4, w, h, w, h, 3, 0, 0)
-        assert jg == jw and same_floats(d.numpy(), want)
+        jg, wH, wV = dwt.dwt_eaw53_2f_s(d.ptr, w * 4, 4, w, h, w, h, 3, 0, 0)
+        assert jg == jw and same_floats(d.get(), want)
         assert all(same_floats(np.where(np.isnan(b), 0, a), np.nan_to_num(b, nan=0.0)) for a, b in zip(wH + wV, wHw + wVw))
-        dwt.dwt_eaw53_2i_s(d.data_ptr(), w * 4, 4, w, h, w, h, jg, 0, 0, wH, wV)
-        assert same_floats(d.numpy(), expect_inv(ref, want, wHw, wVw, j_max=jw))
+        dwt.dwt_eaw53_2i_s(d.ptr, w * 4, 4, w, h, w, h, jg, 0, 0, wH, wV)
+        assert same_floats(d.get(), expect_inv(ref, want, wHw, wVw, j_max=jw))
     finally:
         dwt.set_option("eaw_two_pass", 0)
 
@@ -202,10 +183,10 @@ def test_fused_equals_two_pass(dwt, shape, decompose_one):
         dwt.set_option("eaw_two_pass", two)
         try:
             d = to_device(img)
-            j, wH, wV = dwt.dwt_eaw53_2f_s(d.data_ptr(), w * 4, 4, w, h, w, h, -1, decompose_one, 0, alpha=0.8)
-            f = d.numpy()
-            dwt.dwt_eaw53_2i_s(d.data_ptr(), w * 4, 4, w, h, w, h, j, decompose_one, 0, wH, wV)
-            res.append((j, f, wH, wV, d.numpy()))
+            j, wH, wV = dwt.dwt_eaw53_2f_s(d.ptr, w * 4, 4, w, h, w, h, -1, decompose_one, 0, alpha=0.8)
+            f = d.get()
+            dwt.dwt_eaw53_2i_s(d.ptr, w * 4, 4, w, h, w, h, j, decompose_one, 0, wH, wV)
+            res.append((j, f, wH, wV, d.get()))
         finally:
             dwt.set_option("eaw_two_pass", 0)
     (j0, f0, h0, v0, i0), (j1, f1, h1, v1, i1) = res
@@ -220,10 +201,10 @@ def test_dense_device_call_makes_one_launch_per_level(dwt):
     wb = to_device(np.zeros(total, dtype=np.float32))
     j = C.c_int(J)
     n0 = dwt.get_option("stat_launches")
-    assert dwt.lib.dwt_hip_eaw53_2d(0, 0, d.data_ptr(), w * 4, 4, w, h, w, h, C.byref(j), 0, 0, wb.data_ptr(), 1.0) == 0
+    assert dwt.lib.dwt_hip_eaw53_2d(0, 0, d.ptr, w * 4, 4, w, h, w, h, C.byref(j), 0, 0, wb.ptr, 1.0) == 0
     assert dwt.get_option("stat_launches") - n0 == J
     n0 = dwt.get_option("stat_launches")
-    assert dwt.lib.dwt_hip_eaw53_2d(1, 0, d.data_ptr(), w * 4, 4, w, h, w, h, C.byref(j), 0, 0, wb.data_ptr(), 1.0) == 0
+    assert dwt.lib.dwt_hip_eaw53_2d(1, 0, d.ptr, w * 4, 4, w, h, w, h, C.byref(j), 0, 0, wb.ptr, 1.0) == 0
     assert dwt.get_option("stat_launches") - n0 == J
 
 
@@ -238,8 +219,8 @@ def test_batch_equals_single(dwt, where):
     else:
         d, wb = imgs.copy(), np.zeros(B * ws, dtype=np.float32)
     assert dwt.eaw53_2d_batch(0, d, h * w * 4, B, w * 4, w, h, wb, ws, J, alpha=0.8) == J
-    got = d.numpy() if where == "device" else d
-    gw = wb.numpy() if where == "device" else wb
+    got = d.get() if where == "device" else d
+    gw = wb.get() if where == "device" else wb
     for b in range(B):
         one = imgs[b].copy()
         j, wH, wV = dwt.dwt_eaw53_2f_s(one, w * 4, 4, w, h, w, h, J, 0, 0, alpha=0.8)
@@ -247,7 +228,7 @@ def test_batch_equals_single(dwt, where):
         flat = np.concatenate([a.reshape(-1) for k in range(J) for a in (wH[k], wV[k])])
         assert same_floats(gw[b * ws:b * ws + total], flat)
     dwt.eaw53_2d_batch(1, d, h * w * 4, B, w * 4, w, h, wb, ws, J)
-    back = d.numpy() if where == "device" else d
+    back = d.get() if where == "device" else d
     assert np.abs(back - imgs).max() <= 1e-5 * np.abs(imgs).max()
 
 
@@ -260,9 +241,9 @@ def test_inverse_exact_for_any_alpha(dwt, ref, alpha):
     want = expect_inv(ref, coef, wH, wV, j_max=j)
     for where in ("host", "device"):
         d = coef.copy() if where == "host" else to_device(coef)
-        dwt.dwt_eaw53_2i_s(d if where == "host" else d.data_ptr(), w * 4, 4, w, h, w, h, j, 0, 0,
+        dwt.dwt_eaw53_2i_s(d if where == "host" else d.ptr, w * 4, 4, w, h, w, h, j, 0, 0,
                            [np.nan_to_num(a) for a in wH], [np.nan_to_num(a) for a in wV])
-        assert same_floats(d if where == "host" else d.numpy(), want), where
+        assert same_floats(d if where == "host" else d.get(), want), where
 
 
 def test_alpha_08_forward_within_tolerance(dwt, ref):
@@ -275,7 +256,7 @@ def test_alpha_08_forward_within_tolerance(dwt, ref):
     img = np.random.default_rng(8).random((h, w), dtype=np.float32) * 100
     want, jw, wHw, wVw = expect_fwd(ref, img, j_max=5, alpha=0.8)
     d = to_device(img)
-    jg, wH, wV = dwt.dwt_eaw53_2f_s(d.data_ptr(), w * 4, 4, w, h, w, h, 5, 0, 0, alpha=0.8)
+    jg, wH, wV = dwt.dwt_eaw53_2f_s(d.ptr, w * 4, 4, w, h, w, h, 5, 0, 0, alpha=0.8)
     assert jg == jw
     ulp = np.abs(wH[0].view(np.int32).astype(np.int64) - wHw[0].view(np.int32).astype(np.int64))
     assert ulp.max() <= 2
@@ -283,7 +264,7 @@ def test_alpha_08_forward_within_tolerance(dwt, ref):
         m = ~np.isnan(r) & (r != 0)  # (each line's last weight is 0)
         rel = np.abs(g[m] - r[m]) / r[m]
         assert np.median(rel) <= 1e-6 and np.mean(rel > 1e-3) <= 1e-3, (np.median(rel), np.mean(rel > 1e-3), rel.max())
-    got = d.numpy()
+    got = d.get()
     assert np.abs(got - want).max() <= 1e-5 * np.abs(want).max()
 
 
@@ -302,14 +283,14 @@ def test_hdr_detail_edit(dwt, ref, where):
         return a
     want = expect_inv(ref, halve(coef), wHw, wVw, j_max=jw)
     d = img.copy() if where == "host" else to_device(img)
-    p = d.ctypes.data if where == "host" else d.data_ptr()
+    p = d.ctypes.data if where == "host" else d.ptr
     j, wH, wV = dwt.dwt_eaw53_2f_s(p, w * 4, 4, w, h, w, h, J, 0, 0)
-    c = d if where == "host" else d.numpy()
+    c = d if where == "host" else d.get()
     c = halve(c)
     d = c if where == "host" else to_device(c)
-    p = d.ctypes.data if where == "host" else d.data_ptr()
+    p = d.ctypes.data if where == "host" else d.ptr
     dwt.dwt_eaw53_2i_s(p, w * 4, 4, w, h, w, h, j, 0, 0, wH, wV)
-    assert same_floats(d if where == "host" else d.numpy(), want)
+    assert same_floats(d if where == "host" else d.get(), want)
 
 
 @pytest.mark.parametrize("alpha", [1.0, 0.8])
@@ -317,6 +298,6 @@ def test_round_trip(dwt, alpha):
     h, w = 777, 1025
     img = np.random.default_rng(13).random((h, w), dtype=np.float32) + 0.5
     d = to_device(img)
-    j, wH, wV = dwt.dwt_eaw53_2f_s(d.data_ptr(), w * 4, 4, w, h, w, h, -1, 1, 0, alpha=alpha)
-    dwt.dwt_eaw53_2i_s(d.data_ptr(), w * 4, 4, w, h, w, h, j, 1, 0, wH, wV)
-    assert np.abs(d.numpy() - img).max() <= 1e-5 * np.abs(img).max()
+    j, wH, wV = dwt.dwt_eaw53_2f_s(d.ptr, w * 4, 4, w, h, w, h, -1, 1, 0, alpha=alpha)
+    dwt.dwt_eaw53_2i_s(d.ptr, w * 4, 4, w, h, w, h, j, 1, 0, wH, wV)
+    assert np.abs(d.get() - img).max() <= 1e-5 * np.abs(img).max()

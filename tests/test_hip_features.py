@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import features_model as fm
+from hipdev import Dev, launches
 
 pytestmark = pytest.mark.gpu
 F32 = np.float32
@@ -27,25 +28,6 @@ def reference(img, sox, soy, six, siy, j_max, p):
     if fm.RefFeatures.available():
         return fm.RefFeatures().features(img, sox, soy, six, siy, j_max, p)
     return fm.seq32(img, sox, soy, six, siy, j_max, p)
-
-
-class Dev:
-    """a host array copied to device memory"""
-
-    def __init__(self, dwt, a):
-        self.dwt, self.n = dwt, max(a.nbytes, 4)
-        self.ptr = dwt.lib.dwt_hip_malloc(self.n)
-        assert self.ptr
-        if a.nbytes:
-            assert dwt.lib.dwt_hip_memcpy_h2d(self.ptr, a.ctypes.data, a.nbytes) == 0
-
-    def get(self, shape, dtype=F32):
-        out = np.empty(shape, dtype)
-        assert self.dwt.lib.dwt_hip_memcpy_d2h(out.ctypes.data, self.ptr, out.nbytes) == 0
-        return out
-
-    def free(self):
-        self.dwt.lib.dwt_hip_free(self.ptr)
 
 
 def run(dwt, names, imgs, six, siy, j_max, p, how, device):
@@ -229,12 +211,6 @@ def test_reproducible_across_runs_and_geometries(dwt):
     a = run(dwt, ALL, row, 4096, 1, 12, 1.7, "lines", True)[0]
     assert equal_bits(a, run(dwt, ALL, row, 4096, 1, 12, 1.7, "lines", True)[0])
     assert equal_bits(a, run(dwt, ALL, row, 4096, 1, 12, 1.7, "single", True)[0])  # dwt_util_*_s on a row == the batch call
-
-
-def launches(dwt, f):
-    n0 = dwt.get_option("stat_launches")
-    f()
-    return dwt.get_option("stat_launches") - n0
 
 
 def test_launch_counts(dwt):

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from conftest import full_range_floats, same_floats
+from hipdev import Dev
 from oraclelib import Oracle, Reference, have_reference
 from test_oned import J_CASES, ceil_log2, ref_call, ref_lib, restated
 
@@ -49,25 +50,6 @@ def expect():
             b = np.ascontiguousarray(a, np.float32).copy()
             return b, restated(orc, wv, inverse, b, so, si, j_max, zp)
     return f
-
-
-class Dev:
-    """A device buffer holding a copy of a numpy array."""
-
-    def __init__(self, dwt, arr):
-        self.dwt, self.nbytes, self.shape, self.dtype = dwt, arr.nbytes, arr.shape, arr.dtype
-        self.ptr = dwt.lib.dwt_hip_malloc(arr.nbytes)
-        assert self.ptr
-        assert dwt.lib.dwt_hip_memcpy_h2d(self.ptr, np.ascontiguousarray(arr).ctypes.data, arr.nbytes) == 0
-
-    def get(self):
-        self.dwt.sync()
-        out = np.empty(self.shape, self.dtype)
-        assert self.dwt.lib.dwt_hip_memcpy_d2h(out.ctypes.data, self.ptr, self.nbytes) == 0
-        return out
-
-    def free(self):
-        self.dwt.lib.dwt_hip_free(self.ptr)
 
 
 def t1d(dwt, wv, inverse, ptr, stride, so, si, j, zp=0):

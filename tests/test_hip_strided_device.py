@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from conftest import bits, full_range_ints, multichannel_cases
+from hipdev import Dev
 
 pytestmark = pytest.mark.gpu
 
@@ -22,23 +23,6 @@ def dwt():
     d.dwt_util_finish()
 
 
-class DevBuf:
-    def __init__(self, dwt, arr):
-        self.dwt, self.shape, self.dtype = dwt, arr.shape, arr.dtype
-        a = np.ascontiguousarray(arr)
-        self.nbytes = a.nbytes
-        self.ptr = dwt.lib.dwt_hip_malloc(max(16, a.nbytes))
-        assert self.ptr and dwt.lib.dwt_hip_memcpy_h2d(self.ptr, a.ctypes.data, a.nbytes) == 0
-
-    def get(self):
-        out = np.empty(self.shape, self.dtype)
-        assert self.dwt.lib.dwt_hip_memcpy_d2h(out.ctypes.data, self.ptr, self.nbytes) == 0
-        return out
-
-    def free(self):
-        self.dwt.lib.dwt_hip_free(self.ptr)
-
-
 @pytest.mark.parametrize("case", multichannel_cases(), ids=lambda c: c[0]["name"])
 def test_golden_multichannel_device_resident(dwt, case):
     """The 21 reference-generated multichannel fixtures with the matrix in HBM."""
@@ -46,7 +30,7 @@ def test_golden_multichannel_device_resident(dwt, case):
     wname = meta["wavelet"]
     es = src.dtype.itemsize
     (sox, soy), (six, siy) = meta["size_o"], meta["size_i"]
-    d = DevBuf(dwt, src)
+    d = Dev(dwt, src)
     ptr = d.ptr + es * meta["channel"]
     j = dwt.FORWARD[wname](ptr, src.strides[0], src.strides[1], sox, soy, six, siy, meta["j_in"],
                            meta["decompose_one"], meta["zero_padding"])
@@ -65,7 +49,7 @@ def test_multichannel_all_channels_like_cv_dwt_transform_device_resident(dwt, or
     h, w, c = 1080, 1920, 3
     img = rng.random((h, w, c), dtype=np.float32)
     want = img.copy()
-    d = DevBuf(dwt, img)
+    d = Dev(dwt, img)
     for ch in range(c):
         jw = oracle.call_channel("cdf97_2f_s", want, ch, 4)
         jg = dwt.dwt_cdf97_2f_s(d.ptr + 4 * ch, img.strides[0], img.strides[1], w, h, w, h, 4)
@@ -96,7 +80,7 @@ def test_s2_sparse_and_unaligned_strides_device_resident(dwt, oracle, wname, dt)
     want = img.copy()
     kw = dict(size_i=(120, 50), zero_padding=1)
     jw = oracle.call_channel(ff, want, 1, 3, **kw)
-    d = DevBuf(dwt, img)
+    d = Dev(dwt, img)
     jg = dwt.FORWARD[wname](d.ptr + es, img.strides[0], img.strides[1], w, h, 120, 50, 3, 0, 1)
     assert jg == jw and np.array_equal(bits(d.get()), bits(want))
     oracle.call_channel(fi, want, 1, jw, **kw)
@@ -110,7 +94,7 @@ def test_s2_sparse_and_unaligned_strides_device_resident(dwt, oracle, wname, dt)
     dense = img[:hh, :ww, 0].copy()
     view = np.lib.stride_tricks.as_strided(raw[off:].view(np.uint8), shape=(hh, ww, es), strides=(sx, sy, 1))
     view[:] = dense.view(np.uint8).reshape(hh, ww, es)
-    d = DevBuf(dwt, raw)
+    d = Dev(dwt, raw)
     want2 = dense.copy()
     jw = oracle.fwd(ff, want2, -1)
     assert dwt.FORWARD[wname](d.ptr + off, sx, sy, ww, hh, ww, hh, -1) == jw
@@ -137,7 +121,7 @@ def test_interleaved_layout_entries_on_a_strided_device_image(dwt, oracle):
     rng = np.random.default_rng(12)
     h, w, c = 130, 200, 2
     img = rng.random((h, w, c), dtype=np.float32)
-    d = DevBuf(dwt, img)
+    d = Dev(dwt, img)
     want = np.ascontiguousarray(img[:, :, 1])
     jw = oracle.fwd("cdf97_2f_inplace_s", want, 3)
     assert dwt.dwt_cdf97_2f_inplace_s(d.ptr + 4, img.strides[0], img.strides[1], w, h, w, h, 3) == jw

@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 import timefreq_model as tm
+from hipdev import Dev, launches
 
 pytestmark = pytest.mark.gpu
 F32 = np.float32
@@ -34,32 +35,6 @@ def dwt():
     d.dwt_util_init()
     yield d
     d.set_option("timefreq_tiled", 1)
-
-
-class Dev:
-    """a host array copied to device memory"""
-
-    def __init__(self, dwt, a):
-        self.dwt, self.n = dwt, max(a.nbytes, 4)
-        self.ptr = dwt.lib.dwt_hip_malloc(self.n)
-        assert self.ptr
-        if a.nbytes:
-            assert dwt.lib.dwt_hip_memcpy_h2d(self.ptr, a.ctypes.data, a.nbytes) == 0
-
-    def get(self, shape, dtype=F32):
-        out = np.empty(shape, dtype)
-        if out.nbytes:
-            assert self.dwt.lib.dwt_hip_memcpy_d2h(out.ctypes.data, self.ptr, out.nbytes) == 0
-        return out
-
-    def free(self):
-        self.dwt.lib.dwt_hip_free(self.ptr)
-
-
-def launches(dwt, f):
-    n0 = dwt.get_option("stat_launches")
-    f()
-    return dwt.get_option("stat_launches") - n0
 
 
 def bank_of(dwt, i):
