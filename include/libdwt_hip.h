@@ -203,8 +203,20 @@ int dwt_hip_eaw53_2d(int inverse, int layout, void *ptr, int stride_x, int strid
 int dwt_hip_eaw53_2d_batch(int inverse, void *ptr, size_t batch_stride, int batch, int stride_x, int size_x, int size_y,
 	int *j, int decompose_one, float *weights, size_t weights_stride, float alpha);
 
-/* Floats of the weight buffer of a `j`-level EAW call (-1: bad arguments); off_h[k] / off_v[k] (k < j; either may be
- * NULL) receive where level k's wH / wV start.  Mallat: wH[k] is size_o_src_y x size_i_src_x row-major, wV[k]
+/* Edge-avoiding CDF 9/7 wavelet (libdwt's dwt_eaw97_2f_s / _2i_s, "WCDF 9/7": src/eaw-experimental.h), float, Mallat
+ * layout only (the reference has no interleaved twin).  Four lifting steps per pass, all with the weights computed once
+ * from the pass's input.  The contracts are those of dwt_hip_eaw53_2d / _batch above: host or device memory, any byte
+ * strides, one caller-owned weight buffer in the memory space of `ptr`, alpha 1 and 0 exact, any other alpha through
+ * pow in double, the inverse exact for every alpha, one launch per level of a dense Mallat frame in HBM.  The weight
+ * arrays have the shapes of the 5/3 wavelet's, so dwt_hip_eaw53_weights_layout(DWT_HIP_EAW_MALLAT, ...) lays out the
+ * buffer of both wavelets. */
+int dwt_hip_eaw97_2d(int inverse, void *ptr, int stride_x, int stride_y, int size_o_x, int size_o_y, int size_i_x,
+	int size_i_y, int *j, int decompose_one, int zero_padding, float *weights, float alpha);
+int dwt_hip_eaw97_2d_batch(int inverse, void *ptr, size_t batch_stride, int batch, int stride_x, int size_x, int size_y,
+	int *j, int decompose_one, float *weights, size_t weights_stride, float alpha);
+
+/* Floats of the weight buffer of a `j`-level EAW call, 5/3 or 9/7 (-1: bad arguments); off_h[k] / off_v[k] (k < j; either
+ * may be NULL) receive where level k's wH / wV start.  Mallat: wH[k] is size_o_src_y x size_i_src_x row-major, wV[k]
  * size_o_src_x x size_i_src_y column-major (wV[k][x * size_i_src_y + y]); interleaved: both size_i_src_y x size_i_src_x
  * (wV column-major too). */
 long dwt_hip_eaw53_weights_layout(int layout, int size_o_x, int size_o_y, int size_i_x, int size_i_y, int j,

@@ -500,8 +500,13 @@ def transform1d_batch(wavelet, inverse, src, dst, line_stride, n_lines, size, j_
     return j.value
 
 
-# ---- edge-avoiding 5/3 (EAW) entry points ---------------------------------------------
+# ---- edge-avoiding 5/3 and 9/7 (EAW) entry points -------------------------------------
 EAW_MALLAT, EAW_INTERLEAVED = 0, 1
+EAW53, EAW97 = "eaw53", "eaw97"  # the wavelet argument of _eaw_call / _eaw_forward / _eaw_inverse
+lib.dwt_hip_eaw97_2d.argtypes = [_I, _P, _I, _I, _I, _I, _I, _I, C.POINTER(_I), _I, _I, _P, C.c_float]
+lib.dwt_hip_eaw97_2d.restype = _I
+lib.dwt_hip_eaw97_2d_batch.argtypes = [_I, _P, _S, _I, _I, _I, _I, C.POINTER(_I), _I, _P, _S, C.c_float]
+lib.dwt_hip_eaw97_2d_batch.restype = _I
 lib.dwt_hip_eaw53_2d.argtypes = [_I, _I, _P, _I, _I, _I, _I, _I, _I, C.POINTER(_I), _I, _I, _P, C.c_float]
 lib.dwt_hip_eaw53_2d.restype = _I
 lib.dwt_hip_eaw53_2d_batch.argtypes = [_I, _P, _S, _I, _I, _I, _I, C.POINTER(_I), _I, _P, _S, C.c_float]
@@ -550,14 +555,20 @@ def _eaw_levels(inverse, size_o_x, size_o_y, j_max, decompose_one):
     return j_max if 0 <= j_max < lim else lim
 
 
-def _eaw_call(inverse, layout, ptr, stride_x, stride_y, sox, soy, six, siy, j_max, decompose_one, zero_padding, wbuf, alpha, who):
+def _eaw_call(inverse, layout, ptr, stride_x, stride_y, sox, soy, six, siy, j_max, decompose_one, zero_padding, wbuf, alpha, who,
+              wavelet=EAW53):
     j = _I(j_max)
-    _check(lib.dwt_hip_eaw53_2d(int(inverse), layout, _addr(ptr), stride_x, stride_y, sox, soy, six, siy, C.byref(j),
-                                decompose_one, zero_padding, wbuf, float(alpha)), who)
+    if wavelet == EAW97:  # Mallat only
+        _check(lib.dwt_hip_eaw97_2d(int(inverse), _addr(ptr), stride_x, stride_y, sox, soy, six, siy, C.byref(j),
+                                    decompose_one, zero_padding, wbuf, float(alpha)), who)
+    else:
+        _check(lib.dwt_hip_eaw53_2d(int(inverse), layout, _addr(ptr), stride_x, stride_y, sox, soy, six, siy, C.byref(j),
+                                    decompose_one, zero_padding, wbuf, float(alpha)), who)
     return j.value
 
 
-def _eaw_forward(layout, ptr, stride_x, stride_y, sox, soy, six, siy, j_max, decompose_one, zero_padding, alpha, who):
+def _eaw_forward(layout, ptr, stride_x, stride_y, sox, soy, six, siy, j_max, decompose_one, zero_padding, alpha, who,
+                 wavelet=EAW53):
     import numpy as np
 
     J = _eaw_levels(False, sox, soy, j_max, decompose_one)
@@ -570,19 +581,21 @@ def _eaw_forward(layout, ptr, stride_x, stride_y, sox, soy, six, siy, j_max, dec
             raise DwtError("dwt_hip_malloc: " + last_error())
         try:
             _check(lib.dwt_hip_memcpy_h2d(d, w.ctypes.data, w.nbytes), who)
-            j = _eaw_call(0, layout, p, stride_x, stride_y, sox, soy, six, siy, j_max, decompose_one, zero_padding, d, alpha, who)
+            j = _eaw_call(0, layout, p, stride_x, stride_y, sox, soy, six, siy, j_max, decompose_one, zero_padding, d, alpha, who,
+                          wavelet)
             _check(lib.dwt_hip_memcpy_d2h(w.ctypes.data, d, w.nbytes), who)
         finally:
             lib.dwt_hip_free(d)
     else:
         j = _eaw_call(0, layout, p, stride_x, stride_y, sox, soy, six, siy, j_max, decompose_one, zero_padding, w.ctypes.data,
-                      alpha, who)
+                      alpha, who, wavelet)
     wH = [w[o:o + a * b].reshape(a, b).copy() for o, (a, b) in hs]
     wV = [w[o:o + a * b].reshape(a, b).copy() for o, (a, b) in vs]
     return j, wH, wV
 
 
-def _eaw_inverse(layout, ptr, stride_x, stride_y, sox, soy, six, siy, j_max, decompose_one, zero_padding, wH, wV, who):
+def _eaw_inverse(layout, ptr, stride_x, stride_y, sox, soy, six, siy, j_max, decompose_one, zero_padding, wH, wV, who,
+                 wavelet=EAW53):
     import numpy as np
 
     J = _eaw_levels(True, sox, soy, j_max, decompose_one)
@@ -598,11 +611,12 @@ def _eaw_inverse(layout, ptr, stride_x, stride_y, sox, soy, six, siy, j_max, dec
             raise DwtError("dwt_hip_malloc: " + last_error())
         try:
             _check(lib.dwt_hip_memcpy_h2d(d, w.ctypes.data, w.nbytes), who)
-            _eaw_call(1, layout, p, stride_x, stride_y, sox, soy, six, siy, j_max, decompose_one, zero_padding, d, 1.0, who)
+            _eaw_call(1, layout, p, stride_x, stride_y, sox, soy, six, siy, j_max, decompose_one, zero_padding, d, 1.0, who, wavelet)
         finally:
             lib.dwt_hip_free(d)
     else:
-        _eaw_call(1, layout, p, stride_x, stride_y, sox, soy, six, siy, j_max, decompose_one, zero_padding, w.ctypes.data, 1.0, who)
+        _eaw_call(1, layout, p, stride_x, stride_y, sox, soy, six, siy, j_max, decompose_one, zero_padding, w.ctypes.data, 1.0, who,
+                  wavelet)
     return j_max
 
 
@@ -634,23 +648,50 @@ def dwt_eaw53_2i_inplace_s(ptr, stride_x, stride_y, size_o_x, size_o_y, size_i_x
                         zero_padding, wH, wV, "dwt_eaw53_2i_inplace_s")
 
 
+def dwt_eaw97_2f_s(ptr, stride_x, stride_y, size_o_x, size_o_y, size_i_x, size_i_y, j_max=-1, decompose_one=0,
+                   zero_padding=0, alpha=1.0):
+    """src/eaw-experimental.c:300 (edge-avoiding CDF 9/7, Mallat layout).  Returns (levels done, wH, wV), shaped as
+    dwt_eaw53_2f_s's."""
+    return _eaw_forward(EAW_MALLAT, ptr, stride_x, stride_y, size_o_x, size_o_y, size_i_x, size_i_y, j_max, decompose_one,
+                        zero_padding, alpha, "dwt_eaw97_2f_s", EAW97)
+
+
+def dwt_eaw97_2i_s(ptr, stride_x, stride_y, size_o_x, size_o_y, size_i_x, size_i_y, j_max, decompose_one, zero_padding, wH, wV):
+    """src/eaw-experimental.c:398, with the forward's weight arrays."""
+    return _eaw_inverse(EAW_MALLAT, ptr, stride_x, stride_y, size_o_x, size_o_y, size_i_x, size_i_y, j_max, decompose_one,
+                        zero_padding, wH, wV, "dwt_eaw97_2i_s", EAW97)
+
+
 def eaw53_2d_batch(inverse, ptr, batch_stride, batch, stride_x, size_x, size_y, weights, weights_stride, j_max=-1,
                    decompose_one=0, alpha=1.0):
     """EAW 5/3 of `batch` dense float images (Mallat layout, in place) `batch_stride` bytes apart, image b's weights
     (one buffer laid out as eaw53_weights_layout says) at `weights` + b * weights_stride floats.  numpy arrays, torch
     tensors or raw pointers: device memory runs one launch per level for the whole batch, host memory image by image.
     Returns the level count (forward: clamped)."""
+    return _eaw_batch(EAW53, inverse, ptr, batch_stride, batch, stride_x, size_x, size_y, weights, weights_stride, j_max,
+                      decompose_one, alpha)
+
+
+def eaw97_2d_batch(inverse, ptr, batch_stride, batch, stride_x, size_x, size_y, weights, weights_stride, j_max=-1,
+                   decompose_one=0, alpha=1.0):
+    """EAW 9/7 of a batch: eaw53_2d_batch's arguments, layout (eaw53_weights_layout(EAW_MALLAT, ...)) and return."""
+    return _eaw_batch(EAW97, inverse, ptr, batch_stride, batch, stride_x, size_x, size_y, weights, weights_stride, j_max,
+                      decompose_one, alpha)
+
+
+def _eaw_batch(wavelet, inverse, ptr, batch_stride, batch, stride_x, size_x, size_y, weights, weights_stride, j_max, decompose_one,
+               alpha):
     p, w = _addr(ptr), _addr(weights)
     j = _I(j_max)
     if lib.dwt_hip_is_device_pointer(p):
-        _check(lib.dwt_hip_eaw53_2d_batch(int(inverse), p, batch_stride, batch, stride_x, size_x, size_y, C.byref(j),
-                                          decompose_one, w, weights_stride, float(alpha)), "dwt_hip_eaw53_2d_batch")
+        fn = lib.dwt_hip_eaw97_2d_batch if wavelet == EAW97 else lib.dwt_hip_eaw53_2d_batch
+        _check(fn(int(inverse), p, batch_stride, batch, stride_x, size_x, size_y, C.byref(j), decompose_one, w, weights_stride,
+                  float(alpha)), "dwt_hip_%s_2d_batch" % wavelet)
         return j.value
     for b in range(batch):
         j = _I(j_max)
-        _check(lib.dwt_hip_eaw53_2d(int(inverse), EAW_MALLAT, p + b * batch_stride, stride_x, 4, size_x, size_y, size_x, size_y,
-                                    C.byref(j), decompose_one, 0, w + 4 * b * weights_stride, float(alpha)),
-               "dwt_hip_eaw53_2d")
+        j.value = _eaw_call(inverse, EAW_MALLAT, p + b * batch_stride, stride_x, 4, size_x, size_y, size_x, size_y, j_max,
+                            decompose_one, 0, w + 4 * b * weights_stride, alpha, "dwt_hip_%s_2d" % wavelet, wavelet)
     return _eaw_levels(bool(inverse), size_x, size_y, j_max, decompose_one) if batch == 0 else j.value
 
 

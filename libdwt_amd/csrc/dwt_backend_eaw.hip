@@ -1,13 +1,15 @@
-// dwt_backend_eaw.hip -- the edge-avoiding 5/3 drivers (dwt_eaw53_2f_s / _2i_s, src/libdwt.c:16663, 18373; the
-// interleaved dwt_eaw53_2f_inplace_s / _2i_inplace_s, :16602, :17932) on the device, and their C-ABI
-// (include/libdwt_hip.h).
+// dwt_backend_eaw.hip -- the edge-avoiding drivers on the device and their C-ABI (include/libdwt_hip.h): 5/3
+// (dwt_eaw53_2f_s / _2i_s, src/libdwt.c:16663, 18373; the interleaved dwt_eaw53_2f_inplace_s / _2i_inplace_s, :16602,
+// :17932) and 9/7 (dwt_eaw97_2f_s / _2i_s, src/eaw-experimental.c:300, 398, Mallat only).  The two wavelets' drivers are
+// the same loop over different line functions, so one set of functions here takes the wavelet in its frame.
 //
-// A dense Mallat frame in HBM runs one launch of k_eaw_fwd_tile / k_eaw_inv_tile per level (dwt_eaw.hip), for a whole
-// batch at once: the level reads a copy of the image (forward level 0, every inverse level's detail bands) or the LL
-// ping-pong, so no tile reads what another one writes.  Levels whose LL side has shrunk to 1 (decompose_one), sparse
-// frames, the interleaved layout and option "eaw_two_pass" run the reference's loop: per level an exact row pass and an
-// exact column pass (each one line kernel into a dense scratch and one placing kernel), then its zero fills.  Host
-// memory and strided device images are packed into a dense device image first, as the other drivers do.
+// A dense Mallat frame in HBM runs one launch of the wavelet's forward / inverse tile kernel per level (dwt_eaw.hip,
+// dwt_eaw97.hip), for a whole batch at once: the level reads a copy of the image (forward level 0, every inverse
+// level's detail bands) or the LL ping-pong, so no tile reads what another one writes.  Levels whose LL side has shrunk
+// to 1 (decompose_one), sparse frames, the interleaved layout and option "eaw_two_pass" run the reference's loop: per
+// level an exact row pass and an exact column pass (each one line kernel into a dense scratch and one placing kernel),
+// then its zero fills.  Host memory and strided device images are packed into a dense device image first, as the other
+// drivers do.
 #include "dwt_backend.h"
 
 #include <climits>
@@ -16,7 +18,10 @@ namespace dwtb {
 
 namespace {
 
+enum EawWavelet { kEaw53, kEaw97 };
+
 struct EawFrame {
+	EawWavelet wavelet;
 	int layout; // DWT_HIP_EAW_MALLAT / DWT_HIP_EAW_INTERLEAVED
 	Geom ge;
 	int J;
@@ -52,9 +57,9 @@ int eaw_levels(bool inverse, const Geom &ge, int decompose_one, int *jp)
 	return (*jp >= 0 && *jp < lim) ? *jp : lim;
 }
 
-// One exact pass over n_lines lines of N samples (dwt_eaw53_{f,i}_ex_stride_s on each): line kernel into the dense
-// scratch, then the placing kernel.  hoff: Mallat H offset, or -1 for the interleaved layout.
-int line_pass(bool inverse, char *base, long ls, long es, int n_lines, int N, int hoff, float *w, float alpha)
+// One exact pass over n_lines lines of N samples (dwt_eaw53_{f,i}_ex_stride_s / dwt_eaw97_{f,i}_ex_stride_s on each):
+// line kernel into the dense scratch, then the placing kernel.  hoff: Mallat H offset, or -1 for the interleaved layout.
+int line_pass(EawWavelet wv, bool inverse, char *base, long ls, long es, int n_lines, int N, int hoff, float *w, float alpha)
 {
 	if (n_lines <= 0 || N <= 0)
 		return 0;
@@ -62,7 +67,9 @@ int line_pass(bool inverse, char *base, long ls, long es, int n_lines, int N, in
 		return 1;
 	float *tmp = (float *)g.frame_b.p;
 	const bool lanes_along_lines = ls < es; // columns of a row-major image
-	return launched(launch_eaw_line(inverse, base, ls, es, n_lines, N, hoff, tmp, w, lanes_along_lines, alpha, g.stream), "EAW", "line pass") ||
+	const hipError_t e = wv == kEaw97 ? launch_eaw97_line(inverse, base, ls, es, n_lines, N, hoff, tmp, w, lanes_along_lines, alpha, g.stream)
+	                                  : launch_eaw_line(inverse, base, ls, es, n_lines, N, hoff, tmp, w, lanes_along_lines, alpha, g.stream);
+	return launched(e, "EAW", "line pass") ||
 	       launched(launch_eaw_place(base, ls, es, n_lines, N, inverse ? -1 : hoff, tmp, lanes_along_lines, g.stream), "EAW", "line pass");
 }
 
@@ -76,13 +83,13 @@ int level_two_pass(bool inverse, const EawFrame &f, Img d, int j, int zero_paddi
 		const int k = inverse ? j - 1 : j, Wk = ge.Wi(k), Hk = ge.Hi(k);
 		const long rs = P << k, cs = 4l << k;
 		if (!inverse)
-			return line_pass(false, p, rs, cs, Hk, Wk, -1, wb + f.offH[k], alpha) || line_pass(false, p, cs, rs, Wk, Hk, -1, wb + f.offV[k], alpha);
-		return line_pass(true, p, cs, rs, Wk, Hk, -1, wb + f.offV[k], alpha) || line_pass(true, p, rs, cs, Hk, Wk, -1, wb + f.offH[k], alpha);
+			return line_pass(f.wavelet, false, p, rs, cs, Hk, Wk, -1, wb + f.offH[k], alpha) || line_pass(f.wavelet, false, p, cs, rs, Wk, Hk, -1, wb + f.offV[k], alpha);
+		return line_pass(f.wavelet, true, p, cs, rs, Wk, Hk, -1, wb + f.offV[k], alpha) || line_pass(f.wavelet, true, p, rs, cs, Hk, Wk, -1, wb + f.offH[k], alpha);
 	}
 	if (!inverse) {
 		// rows y < size_o_src_y over size_i_src_x samples, then columns x < size_o_src_x over size_i_src_y
-		if (line_pass(false, p, P, 4, ge.Ho(j), ge.Wi(j), ge.Wo(j + 1), wb + f.offH[j], alpha) ||
-			line_pass(false, p, 4, P, ge.Wo(j), ge.Hi(j), ge.Ho(j + 1), wb + f.offV[j], alpha))
+		if (line_pass(f.wavelet, false, p, P, 4, ge.Ho(j), ge.Wi(j), ge.Wo(j + 1), wb + f.offH[j], alpha) ||
+			line_pass(f.wavelet, false, p, 4, P, ge.Wo(j), ge.Hi(j), ge.Ho(j + 1), wb + f.offV[j], alpha))
 			return 1;
 		if (zero_padding) { // dwt_zero_padding_f_stride_s (src/libdwt.c:12118), rows then columns
 			const int nlx = (ge.Wi(j) + 1) >> 1, nhx = ge.Wi(j) >> 1, nly = (ge.Hi(j) + 1) >> 1, nhy = ge.Hi(j) >> 1;
@@ -95,8 +102,8 @@ int level_two_pass(bool inverse, const EawFrame &f, Img d, int j, int zero_paddi
 		return 0;
 	}
 	// level j back to j-1: columns x < size_o_dst_x over size_i_dst_y samples, then rows y < size_o_dst_y
-	if (line_pass(true, p, 4, P, ge.Wo(j - 1), ge.Hi(j - 1), ge.Ho(j), wb + f.offV[j - 1], alpha) ||
-		line_pass(true, p, P, 4, ge.Ho(j - 1), ge.Wi(j - 1), ge.Wo(j), wb + f.offH[j - 1], alpha))
+	if (line_pass(f.wavelet, true, p, 4, P, ge.Wo(j - 1), ge.Hi(j - 1), ge.Ho(j), wb + f.offV[j - 1], alpha) ||
+		line_pass(f.wavelet, true, p, P, 4, ge.Ho(j - 1), ge.Wi(j - 1), ge.Wo(j), wb + f.offH[j - 1], alpha))
 		return 1;
 	if (zero_padding) // dwt_zero_padding_i_stride_s (src/libdwt.c:12199), rows then columns
 		return zero_rect(d, ge.Wi(j - 1), 0, ge.Wo(j - 1) - ge.Wi(j - 1), ge.Ho(j - 1)) ||
@@ -118,9 +125,9 @@ int fused_levels(const EawFrame &f)
 	return n;
 }
 
-int level_launch(bool inverse, const EawLevelArgs &a, float alpha)
+int level_launch(EawWavelet wv, bool inverse, const EawLevelArgs &a, float alpha)
 {
-	return launched(launch_eaw_level(inverse, a, alpha, g.stream), "EAW", "level");
+	return launched(wv == kEaw97 ? launch_eaw97_level(inverse, a, alpha, g.stream) : launch_eaw_level(inverse, a, alpha, g.stream), "EAW", "level");
 }
 
 // scratch of the fused levels: the image copy (frame_b) and the LL ping-pong, for `batch` images
@@ -180,7 +187,7 @@ int run_device(bool inverse, const EawFrame &f, Img d, int batch, long bs, float
 				a.wH_out = wb + f.offH[j];
 				a.wV_out = wb + f.offV[j];
 				a.bi_w = ws;
-				if (level_launch(false, a, alpha))
+				if (level_launch(f.wavelet, false, a, alpha))
 					return 1;
 			}
 		}
@@ -223,17 +230,18 @@ int run_device(bool inverse, const EawFrame &f, Img d, int batch, long bs, float
 			a.wH = wb + f.offH[j - 1];
 			a.wV = wb + f.offV[j - 1];
 			a.bi_w = ws;
-			if (level_launch(true, a, alpha))
+			if (level_launch(f.wavelet, true, a, alpha))
 				return 1;
 		}
 	}
 	return 0;
 }
 
-int eaw2d(bool inverse, int layout, void *ptr, int stride_x, int stride_y, const Geom &ge, int *jp, int decompose_one, int zero_padding,
-	float *weights, float alpha)
+int eaw2d(EawWavelet wv, bool inverse, int layout, void *ptr, int stride_x, int stride_y, const Geom &ge, int *jp, int decompose_one,
+	int zero_padding, float *weights, float alpha)
 {
 	EawFrame f;
+	f.wavelet = wv;
 	f.layout = layout;
 	f.ge = ge;
 	f.J = eaw_levels(inverse, ge, decompose_one, jp);
@@ -268,35 +276,8 @@ int eaw2d(bool inverse, int layout, void *ptr, int stride_x, int stride_y, const
 	return frame_unpack(fr, A.p, A.sx);
 }
 
-} // namespace
-
-} // namespace dwtb
-
-using namespace dwtb;
-
-#pragma GCC visibility push(default)
-extern "C" {
-
-long dwt_hip_eaw53_weights_layout(int layout, int size_o_x, int size_o_y, int size_i_x, int size_i_y, int j, long *off_h, long *off_v)
-{
-	if ((layout != DWT_HIP_EAW_MALLAT && layout != DWT_HIP_EAW_INTERLEAVED) || j < 0 || j > 32 || size_i_x < 0 || size_i_y < 0 ||
-		size_i_x > size_o_x || size_i_y > size_o_y)
-		return -1;
-	EawFrame f;
-	f.layout = layout;
-	f.ge = Geom{size_o_x, size_o_y, size_i_x, size_i_y};
-	f.J = j;
-	eaw_layout(&f);
-	for (int k = 0; k < j; k++) {
-		if (off_h)
-			off_h[k] = f.offH[k];
-		if (off_v)
-			off_v[k] = f.offV[k];
-	}
-	return f.total;
-}
-
-int dwt_hip_eaw53_2d(int inverse, int layout, void *ptr, int stride_x, int stride_y, int size_o_x, int size_o_y, int size_i_x,
+// the argument checks of dwt_hip_eaw53_2d / dwt_hip_eaw97_2d, then the call
+int eaw2d_checked(EawWavelet wv, int inverse, int layout, void *ptr, int stride_x, int stride_y, int size_o_x, int size_o_y, int size_i_x,
 	int size_i_y, int *j, int decompose_one, int zero_padding, float *weights, float alpha)
 {
 	if (check_inited())
@@ -314,10 +295,11 @@ int dwt_hip_eaw53_2d(int inverse, int layout, void *ptr, int stride_x, int strid
 	if (eaw_levels(inverse != 0, ge, decompose_one, &jj) > 0 && !weights && size_o_x > 0 && size_o_y > 0)
 		return fail("null weights");
 	g_elems_are_32bit = true;
-	return eaw2d(inverse != 0, layout, ptr, stride_x, stride_y, ge, j, decompose_one, zero_padding, weights, alpha);
+	return eaw2d(wv, inverse != 0, layout, ptr, stride_x, stride_y, ge, j, decompose_one, zero_padding, weights, alpha);
 }
 
-int dwt_hip_eaw53_2d_batch(int inverse, void *ptr, size_t batch_stride, int batch, int stride_x, int size_x, int size_y, int *j,
+// the same of the batch entries
+int eaw2d_batch_checked(EawWavelet wv, int inverse, void *ptr, size_t batch_stride, int batch, int stride_x, int size_x, int size_y, int *j,
 	int decompose_one, float *weights, size_t weights_stride, float alpha)
 {
 	if (check_inited())
@@ -330,6 +312,7 @@ int dwt_hip_eaw53_2d_batch(int inverse, void *ptr, size_t batch_stride, int batc
 		batch_stride > (size_t)LONG_MAX / 2)
 		return fail("EAW batch: images must be dense, aligned and apart (stride %d, batch stride %zu)", stride_x, batch_stride);
 	EawFrame f;
+	f.wavelet = wv;
 	f.layout = DWT_HIP_EAW_MALLAT;
 	f.ge = Geom{size_x, size_y, size_x, size_y};
 	f.J = eaw_levels(inverse != 0, f.ge, decompose_one, j);
@@ -340,6 +323,63 @@ int dwt_hip_eaw53_2d_batch(int inverse, void *ptr, size_t batch_stride, int batc
 		return 0;
 	g_elems_are_32bit = true;
 	return run_device(inverse != 0, f, Img{(char *)ptr, stride_x, 4}, batch, (long)batch_stride, weights, (long)weights_stride, 0, alpha);
+}
+
+} // namespace
+
+} // namespace dwtb
+
+using namespace dwtb;
+
+#pragma GCC visibility push(default)
+extern "C" {
+
+long dwt_hip_eaw53_weights_layout(int layout, int size_o_x, int size_o_y, int size_i_x, int size_i_y, int j, long *off_h, long *off_v)
+{
+	if ((layout != DWT_HIP_EAW_MALLAT && layout != DWT_HIP_EAW_INTERLEAVED) || j < 0 || j > 32 || size_i_x < 0 || size_i_y < 0 ||
+		size_i_x > size_o_x || size_i_y > size_o_y)
+		return -1;
+	EawFrame f;
+	f.wavelet = kEaw53; // the layout does not depend on the wavelet
+	f.layout = layout;
+	f.ge = Geom{size_o_x, size_o_y, size_i_x, size_i_y};
+	f.J = j;
+	eaw_layout(&f);
+	for (int k = 0; k < j; k++) {
+		if (off_h)
+			off_h[k] = f.offH[k];
+		if (off_v)
+			off_v[k] = f.offV[k];
+	}
+	return f.total;
+}
+
+int dwt_hip_eaw53_2d(int inverse, int layout, void *ptr, int stride_x, int stride_y, int size_o_x, int size_o_y, int size_i_x,
+	int size_i_y, int *j, int decompose_one, int zero_padding, float *weights, float alpha)
+{
+	return eaw2d_checked(kEaw53, inverse, layout, ptr, stride_x, stride_y, size_o_x, size_o_y, size_i_x, size_i_y, j, decompose_one,
+		zero_padding, weights, alpha);
+}
+
+int dwt_hip_eaw53_2d_batch(int inverse, void *ptr, size_t batch_stride, int batch, int stride_x, int size_x, int size_y, int *j,
+	int decompose_one, float *weights, size_t weights_stride, float alpha)
+{
+	return eaw2d_batch_checked(kEaw53, inverse, ptr, batch_stride, batch, stride_x, size_x, size_y, j, decompose_one, weights,
+		weights_stride, alpha);
+}
+
+int dwt_hip_eaw97_2d(int inverse, void *ptr, int stride_x, int stride_y, int size_o_x, int size_o_y, int size_i_x, int size_i_y, int *j,
+	int decompose_one, int zero_padding, float *weights, float alpha)
+{
+	return eaw2d_checked(kEaw97, inverse, DWT_HIP_EAW_MALLAT, ptr, stride_x, stride_y, size_o_x, size_o_y, size_i_x, size_i_y, j,
+		decompose_one, zero_padding, weights, alpha);
+}
+
+int dwt_hip_eaw97_2d_batch(int inverse, void *ptr, size_t batch_stride, int batch, int stride_x, int size_x, int size_y, int *j,
+	int decompose_one, float *weights, size_t weights_stride, float alpha)
+{
+	return eaw2d_batch_checked(kEaw97, inverse, ptr, batch_stride, batch, stride_x, size_x, size_y, j, decompose_one, weights,
+		weights_stride, alpha);
 }
 
 } // extern "C"

@@ -14,6 +14,7 @@
 //  * k_eaw_fwd_tile / k_eaw_inv_tile: one launch per level of a dense Mallat frame.  A workgroup owns a 64 x 64 tile,
 //    reads it with its halo into LDS once, lifts the rows it needs (halo rows recomputed, never exchanged), then the
 //    columns, and writes the subbands and both weight arrays of its own samples.
+#include "dwt_eaw_steps.h"
 #include "dwt_kernels.h"
 
 #include <math.h>
@@ -26,22 +27,6 @@ struct Eaw53 {
 	static __device__ __forceinline__ float s1() { return 1.41421356237309504880f; } // dwt_cdf53_s1_s (src/inline.h:334)
 	static __device__ __forceinline__ float s2() { return 0.70710678118654752440f; } // dwt_cdf53_s2_s
 };
-
-// dwt_eaw_w (src/libdwt.c:11070).  mode 0: alpha == 0 (powf(x, 0) == 1 for every x); mode 1: alpha == 1 (powf(x, 1)
-// == x for every float); mode 2: any other alpha, pow in double rounded once to float (within 1 ulp of glibc's powf).
-static __device__ __forceinline__ float eaw_weight(float n, float m, float alpha, int mode)
-{
-	const float eps = 1.0e-5f;
-	const float d = fabsf(n - m);
-	float p;
-	if (mode == 0)
-		p = 1.f;
-	else if (mode == 1)
-		p = d;
-	else
-		p = (float)pow((double)d, (double)alpha);
-	return 1.f / (p + eps);
-}
 
 // forward predict of an odd sample with both neighbours / at the end of an even line (wL = wR = w[N-2])
 static __device__ __forceinline__ float f_pred(float x, float xl, float xr, float wl, float wr) { return x - (wl * xl + wr * xr) / (wl + wr); }
@@ -113,9 +98,6 @@ static __device__ __forceinline__ void inv_pair(const T &t, const Wt &W, int N, 
 
 // ---- the exact line pass ---------------------------------------------------------------------------------------------
 
-// Where sample i of a line sits: Mallat (L at i/2, H at hoff + i/2) or interleaved (at i).
-static __device__ __forceinline__ long eaw_pos(int i, int hoff) { return hoff < 0 ? i : (i & 1) ? hoff + (i >> 1) : (i >> 1); }
-
 // n_lines lines, line l at src + l*ls, its elements es bytes apart.  Forward: reads samples 0..N-1 in order, writes the
 // pass's result in sample order to tmp[l*N ..] and the weights to w[l*N ..].  Inverse: reads sample i at eaw_pos(i),
 // weights from w, writes the line in order to tmp.  lanes_along_lines: neighbouring lanes take neighbouring lines
@@ -168,14 +150,6 @@ __global__ __launch_bounds__(256) void k_eaw_place(char *__restrict__ dst, long 
 		const int i = lanes_along_lines ? (int)(t / n_lines) : (int)(t % N);
 		*(float *)(dst + (long)l * ls + eaw_pos(i, hoff) * es) = tmp[(long)l * N + i];
 	}
-}
-
-static int eaw_mode(float alpha) { return alpha == 0.f ? 0 : alpha == 1.f ? 1 : 2; }
-
-static dim3 eaw_grid(long threads)
-{
-	long b = (threads + 255) / 256;
-	return dim3((unsigned)(b < 65536 ? (b > 0 ? b : 1) : 65536));
 }
 
 hipError_t launch_eaw_line(bool inverse, const void *src, long ls, long es, int n_lines, int N, int hoff, float *tmp, float *w,

@@ -1,9 +1,11 @@
 /*
- * dwt_entry_eaw.c -- libdwt's edge-avoiding 5/3 entry points (src/libdwt.h:742-796, 1073-1100) as thin C wrappers
- * over dwt_hip_eaw53_2d (include/libdwt_hip.h), and dwt_util_alloc.  The weights cross as one buffer in the image's
- * memory space; the forward hands them out as the reference does, one dwt_util_alloc'd host array per level and
- * direction.  A call that cannot run on the device logs the reason and aborts through dwt_util_error.
+ * dwt_entry_eaw.c -- libdwt's edge-avoiding entry points, 5/3 (src/libdwt.h:742-796, 1073-1100) and 9/7
+ * (src/eaw-experimental.h), as thin C wrappers over dwt_hip_eaw53_2d / dwt_hip_eaw97_2d (include/libdwt_hip.h), and
+ * dwt_util_alloc.  The weights cross as one buffer in the image's memory space; the forward hands them out as the
+ * reference does, one dwt_util_alloc'd host array per level and direction.  A call that cannot run on the device logs
+ * the reason and aborts through dwt_util_error.
  */
+#include "../../include/eaw-experimental.h"
 #include "../../include/libdwt.h"
 #include "../../include/libdwt_hip.h"
 
@@ -59,7 +61,18 @@ static void wcopy(int dev, int to_buf, float *buf, float *host, long n, const ch
 		dwt_util_error("%s: %s\n", who, dwt_hip_last_error());
 }
 
-static void eaw_forward(int layout, void *ptr, int stride_x, int stride_y, int sox, int soy, int six, int siy, int *j_max_ptr,
+enum eaw_wavelet { EAW53, EAW97 };
+
+/* the wavelet's device call; 9/7 has the Mallat layout only */
+static int eaw_call(enum eaw_wavelet wv, int inverse, int layout, void *ptr, int stride_x, int stride_y, int sox, int soy, int six, int siy,
+	int *j, int decompose_one, int zero_padding, float *buf, float alpha)
+{
+	if (wv == EAW97)
+		return dwt_hip_eaw97_2d(inverse, ptr, stride_x, stride_y, sox, soy, six, siy, j, decompose_one, zero_padding, buf, alpha);
+	return dwt_hip_eaw53_2d(inverse, layout, ptr, stride_x, stride_y, sox, soy, six, siy, j, decompose_one, zero_padding, buf, alpha);
+}
+
+static void eaw_forward(enum eaw_wavelet wv, int layout, void *ptr, int stride_x, int stride_y, int sox, int soy, int six, int siy, int *j_max_ptr,
 	int decompose_one, int zero_padding, float *wH[], float *wV[], float alpha, const char *who)
 {
 	const int lim = level_limit(sox, soy, decompose_one);
@@ -70,7 +83,7 @@ static void eaw_forward(int layout, void *ptr, int stride_x, int stride_y, int s
 		dwt_util_error("%s: bad sizes\n", who);
 	const int dev = dwt_hip_is_device_pointer(ptr);
 	float *buf = wbuf_alloc(dev, total, who);
-	if (dwt_hip_eaw53_2d(0, layout, ptr, stride_x, stride_y, sox, soy, six, siy, j_max_ptr, decompose_one, zero_padding, buf, alpha))
+	if (eaw_call(wv, 0, layout, ptr, stride_x, stride_y, sox, soy, six, siy, j_max_ptr, decompose_one, zero_padding, buf, alpha))
 		dwt_util_error("%s: %s\n", who, dwt_hip_last_error());
 	for (int k = 0; k < J; k++) {
 		const long nh = off_v[k] - off_h[k], nv = (k + 1 < J ? off_h[k + 1] : total) - off_v[k];
@@ -82,7 +95,7 @@ static void eaw_forward(int layout, void *ptr, int stride_x, int stride_y, int s
 	wbuf_free(dev, buf);
 }
 
-static void eaw_inverse(int layout, void *ptr, int stride_x, int stride_y, int sox, int soy, int six, int siy, int j_max,
+static void eaw_inverse(enum eaw_wavelet wv, int layout, void *ptr, int stride_x, int stride_y, int sox, int soy, int six, int siy, int j_max,
 	int decompose_one, int zero_padding, float *wH[], float *wV[], const char *who)
 {
 	const int lim = level_limit(sox, soy, decompose_one);
@@ -98,7 +111,7 @@ static void eaw_inverse(int layout, void *ptr, int stride_x, int stride_y, int s
 		wcopy(dev, 1, buf + off_v[k], wV[k], (k + 1 < J ? off_h[k + 1] : total) - off_v[k], who);
 	}
 	int j = J;
-	if (dwt_hip_eaw53_2d(1, layout, ptr, stride_x, stride_y, sox, soy, six, siy, &j, decompose_one, zero_padding, buf, 1.f))
+	if (eaw_call(wv, 1, layout, ptr, stride_x, stride_y, sox, soy, six, siy, &j, decompose_one, zero_padding, buf, 1.f))
 		dwt_util_error("%s: %s\n", who, dwt_hip_last_error());
 	wbuf_free(dev, buf);
 }
@@ -107,7 +120,7 @@ static void eaw_inverse(int layout, void *ptr, int stride_x, int stride_y, int s
 void dwt_eaw53_2f_s(void *ptr, int stride_x, int stride_y, int size_o_big_x, int size_o_big_y, int size_i_big_x, int size_i_big_y,
 	int *j_max_ptr, int decompose_one, int zero_padding, float *wH[], float *wV[], float alpha)
 {
-	eaw_forward(DWT_HIP_EAW_MALLAT, ptr, stride_x, stride_y, size_o_big_x, size_o_big_y, size_i_big_x, size_i_big_y, j_max_ptr,
+	eaw_forward(EAW53, DWT_HIP_EAW_MALLAT, ptr, stride_x, stride_y, size_o_big_x, size_o_big_y, size_i_big_x, size_i_big_y, j_max_ptr,
 		decompose_one, zero_padding, wH, wV, alpha, __func__);
 }
 
@@ -115,7 +128,23 @@ void dwt_eaw53_2f_s(void *ptr, int stride_x, int stride_y, int size_o_big_x, int
 void dwt_eaw53_2i_s(void *ptr, int stride_x, int stride_y, int size_o_big_x, int size_o_big_y, int size_i_big_x, int size_i_big_y,
 	int j_max, int decompose_one, int zero_padding, float *wH[], float *wV[])
 {
-	eaw_inverse(DWT_HIP_EAW_MALLAT, ptr, stride_x, stride_y, size_o_big_x, size_o_big_y, size_i_big_x, size_i_big_y, j_max,
+	eaw_inverse(EAW53, DWT_HIP_EAW_MALLAT, ptr, stride_x, stride_y, size_o_big_x, size_o_big_y, size_i_big_x, size_i_big_y, j_max,
+		decompose_one, zero_padding, wH, wV, __func__);
+}
+
+/* src/eaw-experimental.c:300 */
+void dwt_eaw97_2f_s(void *ptr, int stride_x, int stride_y, int size_o_big_x, int size_o_big_y, int size_i_big_x, int size_i_big_y,
+	int *j_max_ptr, int decompose_one, int zero_padding, float *wH[], float *wV[], float alpha)
+{
+	eaw_forward(EAW97, DWT_HIP_EAW_MALLAT, ptr, stride_x, stride_y, size_o_big_x, size_o_big_y, size_i_big_x, size_i_big_y, j_max_ptr,
+		decompose_one, zero_padding, wH, wV, alpha, __func__);
+}
+
+/* src/eaw-experimental.c:398 */
+void dwt_eaw97_2i_s(void *ptr, int stride_x, int stride_y, int size_o_big_x, int size_o_big_y, int size_i_big_x, int size_i_big_y,
+	int j_max, int decompose_one, int zero_padding, float *wH[], float *wV[])
+{
+	eaw_inverse(EAW97, DWT_HIP_EAW_MALLAT, ptr, stride_x, stride_y, size_o_big_x, size_o_big_y, size_i_big_x, size_i_big_y, j_max,
 		decompose_one, zero_padding, wH, wV, __func__);
 }
 
@@ -123,7 +152,7 @@ void dwt_eaw53_2i_s(void *ptr, int stride_x, int stride_y, int size_o_big_x, int
 void dwt_eaw53_2f_inplace_s(void *ptr, int stride_x, int stride_y, int size_o_big_x, int size_o_big_y, int size_i_big_x,
 	int size_i_big_y, int *j_max_ptr, int decompose_one, int zero_padding, float *wH[], float *wV[], float alpha)
 {
-	eaw_forward(DWT_HIP_EAW_INTERLEAVED, ptr, stride_x, stride_y, size_o_big_x, size_o_big_y, size_i_big_x, size_i_big_y, j_max_ptr,
+	eaw_forward(EAW53, DWT_HIP_EAW_INTERLEAVED, ptr, stride_x, stride_y, size_o_big_x, size_o_big_y, size_i_big_x, size_i_big_y, j_max_ptr,
 		decompose_one, zero_padding, wH, wV, alpha, __func__);
 }
 
@@ -131,7 +160,7 @@ void dwt_eaw53_2f_inplace_s(void *ptr, int stride_x, int stride_y, int size_o_bi
 void dwt_eaw53_2i_inplace_s(void *ptr, int stride_x, int stride_y, int size_o_big_x, int size_o_big_y, int size_i_big_x,
 	int size_i_big_y, int j_max, int decompose_one, int zero_padding, float *wH[], float *wV[])
 {
-	eaw_inverse(DWT_HIP_EAW_INTERLEAVED, ptr, stride_x, stride_y, size_o_big_x, size_o_big_y, size_i_big_x, size_i_big_y, j_max,
+	eaw_inverse(EAW53, DWT_HIP_EAW_INTERLEAVED, ptr, stride_x, stride_y, size_o_big_x, size_o_big_y, size_i_big_x, size_i_big_y, j_max,
 		decompose_one, zero_padding, wH, wV, __func__);
 }
 

@@ -162,6 +162,11 @@ struct EawLevelArgs {
 	int W = 0, H = 0, batch = 1;
 };
 hipError_t launch_eaw_level(bool inverse, const EawLevelArgs &a, float alpha, hipStream_t s);
+// Edge-avoiding 9/7 (dwt_eaw97.hip): the same two routes with the same arguments (hoff as above); the line pass's
+// result is placed by launch_eaw_place.
+hipError_t launch_eaw97_line(bool inverse, const void *src, long ls, long es, int n_lines, int N, int hoff, float *tmp, float *w,
+	bool lanes_along_lines, float alpha, hipStream_t s);
+hipError_t launch_eaw97_level(bool inverse, const EawLevelArgs &a, float alpha, hipStream_t s);
 
 // z-pass knobs of the 3-D path (measured defaults; options vol_cpt / vol_tile_pairs / vol_nt)
 struct VolTuning {
