@@ -335,6 +335,24 @@ void dwt_util_subband_const_s(const void *ptr, int stride_x, int stride_y, int s
 	int size_i_big_x, int size_i_big_y, int j_max, enum dwt_subbands band, const void **dst_ptr, int *dst_size_x, int *dst_size_y);
 /* |x| in place, host or device memory */
 void dwt_util_abs_s(void *ptr, int stride_x, int stride_y, int size_x, int size_y);
+/* ---- conditioning of spectra (src/libdwt.h; src/libdwt.c:25426-26055): NOTE the sizes come before the strides.  Host
+ * or device memory; DESIGN.md s16 states what is bit-identical to the reference and how the centre is decided --------- */
+int dwt_util_find_min_max_s(const void *ptr, int size_x, int size_y, int stride_x, int stride_y, float *min, float *max);
+int dwt_util_shift_s(void *ptr, int size_x, int size_y, int stride_x, int stride_y, float a);
+int dwt_util_scale_s(void *ptr, int size_x, int size_y, int stride_x, int stride_y, float a);
+/* every row's range mapped to [lo, hi]; constant rows are left alone (one summary warning) */
+int dwt_util_scale21_s(void *ptr, int size_x, int size_y, int stride_x, int stride_y, float lo, float hi);
+/* row[x] = row[x + displ_x], the border sample / zero moving in */
+int dwt_util_displace1_s(void *ptr, int size_x, int stride_y, int displ_x);
+int dwt_util_displace1_zero_s(void *ptr, int size_x, int stride_y, int displ_x);
+int dwt_util_get_center1_s(const void *ptr, int size_x, int stride_y);
+int dwt_util_center1_s(void *ptr, int size_x, int stride_y, int max_iters);
+int dwt_util_center21_s(void *ptr, int size_x, int size_y, int stride_x, int stride_y, int max_iters);
+/* every row minus its median */
+void dwt_util_shift21_med_s(void *ptr, int size_x, int size_y, int stride_x, int stride_y);
+/* pointer arithmetic only: the address of (offset_y, offset_x) / of the len_x columns about the centre column */
+void *dwt_util_viewport(void *ptr, int size_x, int size_y, int stride_x, int stride_y, int offset_x, int offset_y);
+void *dwt_util_crop21(void *ptr, int size_x, int size_y, int stride_x, int stride_y, int len_x);
 float *dwt_util_addr_coeff_s(void *ptr, int y, int x, int stride_x, int stride_y); /* src/libdwt.c:1064 */
 int *dwt_util_addr_coeff_i(void *ptr, int y, int x, int stride_x, int stride_y);
 

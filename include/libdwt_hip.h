@@ -366,6 +366,39 @@ int dwt_hip_band_moment(const void *ptr, int stride_x, int stride_y, int size_x,
 /* |x| in place (dwt_util_abs_s): the sign bit cleared, so -0 -> +0 and Inf stays Inf */
 int dwt_hip_abs(void *ptr, int stride_x, int stride_y, int size_x, int size_y);
 
+/* Conditioning of row batches before a transform, as the reference's spectra programs do (dwt_util_shift21_med_s,
+ * dwt_util_center21_s, dwt_util_scale21_s, src/libdwt.c:25426-26055).  Sample i of row y lies at
+ * ptr + y*line_stride + i*elem_stride (bytes), in host or device memory; rows are conditioned in place.  Dense device
+ * rows of up to 8192 samples take ONE launch whatever the iteration count, up to the batch size from which one kernel per
+ * operation is faster (option "cond_fused" = 1 / 0 forces either route, -1 restores the choice; same bits).  The per-row arrays (info, center, min, max, displ) may each be host
+ * or device memory.
+ *   MED_SHIFT  x += -median, the median being the element of rank size/2 of the row's signed values;
+ *   CENTER     up to max_iters times: c = the row's centre; stop if c == size/2, else row[x] = row[x + c - size/2] with
+ *              zeros moving in (samples moved out are lost: the iterations are not one shift of the original row);
+ *   SCALE      x += (lo - min), then x *= ((hi - lo) / (max - min)); a row with max == min is left alone.
+ * Everything but the centre decision is the reference's arithmetic bit for bit (NaN-free input).  The centre is decided
+ * in float sums in index order like the reference's, over terms |x|^10 formed as double products rounded to float once,
+ * where the reference calls powf: rows where a 1-ulp term difference flips a strict comparison can centre differently. */
+enum dwt_hip_rows_op { DWT_HIP_ROWS_MED_SHIFT = 1, DWT_HIP_ROWS_CENTER = 2, DWT_HIP_ROWS_SCALE = 4 };
+/* ops applied in this order; info (optional): 4 ints per row =
+ * { net offset d (out[x] = in[x+d] where kept), moves made, last centre found (-1: none looked for), 1 if SCALE skipped the row } */
+int dwt_hip_rows_condition(unsigned ops, void *ptr, size_t line_stride, size_t elem_stride, int n_lines, int size, int max_iters,
+	float lo, float hi, int *info);
+/* dwt_util_get_center1_s of every row */
+int dwt_hip_rows_center_index(const void *ptr, size_t line_stride, size_t elem_stride, int n_lines, int size, int *center);
+/* What the reference would have warned about in the centre evaluations of this thread's last dwt_hip_rows_condition or
+ * dwt_hip_rows_center_index call: how many found a zero norm, how many found no crossing index (each optional) */
+int dwt_hip_rows_warnings(int *zero_norm, int *no_index);
+/* dwt_util_find_min_max_s of every row (as values: which of +0 / -0 stands for an extreme zero is unspecified) */
+int dwt_hip_rows_min_max(const void *ptr, size_t line_stride, size_t elem_stride, int n_lines, int size, float *min, float *max);
+/* row[x] = row[x + d], d = displ[row] or displ_all; from outside the row comes zero (zero_fill: dwt_util_displace1_zero_s)
+ * or the nearest sample (dwt_util_displace1_s) */
+int dwt_hip_rows_displace(void *ptr, size_t line_stride, size_t elem_stride, int n_lines, int size, const int *displ, int displ_all,
+	int zero_fill);
+/* x += a / x *= a over size_x x size_y elements, element (y, x) at ptr + y*stride_x + x*stride_y (dwt_util_shift_s, _scale_s) */
+int dwt_hip_shift(void *ptr, int stride_x, int stride_y, int size_x, int size_y, float a);
+int dwt_hip_scale(void *ptr, int stride_x, int stride_y, int size_x, int size_y, float a);
+
 /* The stationary (undecimated) wavelet transform of rows: swt_cdf97_f_ex_stride_s / swt_cdf53_f_ex_stride_s (src/swt.c),
  * every level of a batch of lines in one call.  Level l (0-based) filters the low-pass plane of level
  * l-1 (level 0: the input) with the low-pass and the high-pass filter dilated by 1 << l, borders replicated; every plane

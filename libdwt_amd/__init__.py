@@ -837,6 +837,150 @@ def dwt_util_subband_const_s(ptr, stride_x, stride_y, size_o_x, size_o_y, size_i
     return q.value, sx.value, sy.value
 
 
+# ---- conditioning of row batches (include/libdwt_hip.h, include/libdwt.h) ------------------------------
+ROWS_OP = {"med_shift": 1, "center": 2, "scale": 4}  # name -> bit of an operation mask (enum dwt_hip_rows_op)
+lib.dwt_hip_rows_condition.argtypes = [C.c_uint, _P, _S, _S, _I, _I, _I, _F, _F, _P]
+lib.dwt_hip_rows_condition.restype = _I
+lib.dwt_hip_rows_center_index.argtypes = [_P, _S, _S, _I, _I, _P]
+lib.dwt_hip_rows_center_index.restype = _I
+lib.dwt_hip_rows_warnings.argtypes = [C.POINTER(_I), C.POINTER(_I)]
+lib.dwt_hip_rows_warnings.restype = _I
+lib.dwt_hip_rows_min_max.argtypes = [_P, _S, _S, _I, _I, _P, _P]
+lib.dwt_hip_rows_min_max.restype = _I
+lib.dwt_hip_rows_displace.argtypes = [_P, _S, _S, _I, _I, _P, _I, _I]
+lib.dwt_hip_rows_displace.restype = _I
+lib.dwt_hip_shift.argtypes = [_P, _I, _I, _I, _I, _F]
+lib.dwt_hip_shift.restype = _I
+lib.dwt_hip_scale.argtypes = [_P, _I, _I, _I, _I, _F]
+lib.dwt_hip_scale.restype = _I
+for _n in ("dwt_util_viewport", "dwt_util_crop21"):
+    getattr(lib, _n).argtypes = [_P, _I, _I, _I, _I, _I] + ([_I] if _n == "dwt_util_viewport" else [])
+    getattr(lib, _n).restype = _P
+
+
+def rows_op_mask(ops):
+    """An operation mask from a mask, a name or an iterable of names of ROWS_OP."""
+    if isinstance(ops, int):
+        return ops
+    if isinstance(ops, str):
+        ops = (ops,)
+    return sum({ROWS_OP[o] for o in ops})
+
+
+def rows_condition(ops, ptr, line_stride, elem_stride, n_lines, size, max_iters=20, lo=0.0, hi=1.0, info=None):
+    """dwt_hip_rows_condition: median shift, centring and range scaling of n_lines rows in place, in this order; `info`
+    (host or device, 4 int32 per row) receives net offset, moves made, last centre found, 1 if the scale skipped the row.
+    Dense device rows of up to 8192 samples take one launch up to the batch size from which one kernel per operation is
+    faster (option "cond_fused": 1 / 0 force either route, -1 the choice)."""
+    _check(lib.dwt_hip_rows_condition(rows_op_mask(ops), _addr(ptr), line_stride, elem_stride, n_lines, size, max_iters, float(lo),
+                                      float(hi), None if info is None else _addr(info)), "dwt_hip_rows_condition")
+
+
+def rows_center_index(ptr, line_stride, elem_stride, n_lines, size, center=None):
+    """dwt_hip_rows_center_index: dwt_util_get_center1_s of every row -> `center` (int32, host or device; a host array is
+    made and returned when None)."""
+    import numpy as np
+
+    if center is None:
+        center = np.zeros(n_lines, dtype=np.int32)
+    _check(lib.dwt_hip_rows_center_index(_addr(ptr), line_stride, elem_stride, n_lines, size, _addr(center)), "dwt_hip_rows_center_index")
+    return center
+
+
+def rows_warnings():
+    """dwt_hip_rows_warnings -> (zero norms, missing crossing indexes) among the centre evaluations of this thread's last
+    rows_condition / rows_center_index call: what the reference would have warned about."""
+    a, b = _I(), _I()
+    _check(lib.dwt_hip_rows_warnings(C.byref(a), C.byref(b)), "dwt_hip_rows_warnings")
+    return a.value, b.value
+
+
+def rows_min_max(ptr, line_stride, elem_stride, n_lines, size, mn=None, mx=None):
+    """dwt_hip_rows_min_max -> (min, max), float32 per row (host arrays are made when None)."""
+    import numpy as np
+
+    mn = np.zeros(n_lines, dtype=np.float32) if mn is None else mn
+    mx = np.zeros(n_lines, dtype=np.float32) if mx is None else mx
+    _check(lib.dwt_hip_rows_min_max(_addr(ptr), line_stride, elem_stride, n_lines, size, _addr(mn), _addr(mx)), "dwt_hip_rows_min_max")
+    return mn, mx
+
+
+def rows_displace(ptr, line_stride, elem_stride, n_lines, size, displ, zero_fill=True):
+    """dwt_hip_rows_displace: row[x] = row[x + d] in place; `displ` is one int for every row or an int32 array (host or
+    device) with one per row; zeros (zero_fill) or the border sample move in."""
+    import numbers
+
+    per_row = not isinstance(displ, numbers.Integral)  # (numpy integer scalars are Integral too)
+    _check(lib.dwt_hip_rows_displace(_addr(ptr), line_stride, elem_stride, n_lines, size, _addr(displ) if per_row else None,
+                                     0 if per_row else int(displ), 1 if zero_fill else 0), "dwt_hip_rows_displace")
+
+
+def _row_stride(stride_x, size_y):
+    return stride_x if size_y > 1 else 0
+
+
+def dwt_util_shift21_med_s(ptr, size_x, size_y, stride_x, stride_y):
+    """libdwt's prototype (sizes before strides, as every entry of this block); host or device memory."""
+    rows_condition(1, ptr, _row_stride(stride_x, size_y), stride_y, size_y, size_x, 0)
+
+
+def dwt_util_center21_s(ptr, size_x, size_y, stride_x, stride_y, max_iters):
+    if max_iters > 0:
+        rows_condition(2, ptr, _row_stride(stride_x, size_y), stride_y, size_y, size_x, max_iters)
+    return 0
+
+
+def dwt_util_center1_s(ptr, size_x, stride_y, max_iters):
+    return dwt_util_center21_s(ptr, size_x, 1, 0, stride_y, max_iters)
+
+
+def dwt_util_get_center1_s(ptr, size_x, stride_y):
+    return int(rows_center_index(ptr, 0, stride_y, 1, size_x)[0])
+
+
+def dwt_util_displace1_s(ptr, size_x, stride_y, displ_x):
+    if displ_x:
+        rows_displace(ptr, 0, stride_y, 1, size_x, int(displ_x), zero_fill=False)
+    return 0
+
+
+def dwt_util_displace1_zero_s(ptr, size_x, stride_y, displ_x):
+    if displ_x:
+        rows_displace(ptr, 0, stride_y, 1, size_x, int(displ_x), zero_fill=True)
+    return 0
+
+
+def dwt_util_scale21_s(ptr, size_x, size_y, stride_x, stride_y, lo, hi):
+    rows_condition(4, ptr, _row_stride(stride_x, size_y), stride_y, size_y, size_x, 0, lo, hi)
+    return 0
+
+
+def dwt_util_shift_s(ptr, size_x, size_y, stride_x, stride_y, a):
+    _check(lib.dwt_hip_shift(_addr(ptr), stride_x, stride_y, size_x, size_y, float(a)), "dwt_hip_shift")
+    return 0
+
+
+def dwt_util_scale_s(ptr, size_x, size_y, stride_x, stride_y, a):
+    _check(lib.dwt_hip_scale(_addr(ptr), stride_x, stride_y, size_x, size_y, float(a)), "dwt_hip_scale")
+    return 0
+
+
+def dwt_util_find_min_max_s(ptr, size_x, size_y, stride_x, stride_y):
+    """-> (min, max) over the size_x x size_y elements"""
+    mn, mx = rows_min_max(ptr, _row_stride(stride_x, size_y), stride_y, size_y, size_x)
+    return float(mn.min()), float(mx.max())
+
+
+def dwt_util_viewport(ptr, size_x, size_y, stride_x, stride_y, offset_x, offset_y):
+    """the address of element (offset_y, offset_x): pointer arithmetic only"""
+    return lib.dwt_util_viewport(_addr(ptr), size_x, size_y, stride_x, stride_y, offset_x, offset_y)
+
+
+def dwt_util_crop21(ptr, size_x, size_y, stride_x, stride_y, len_x):
+    """the address of the first of the len_x columns about column size_x / 2: pointer arithmetic only"""
+    return lib.dwt_util_crop21(_addr(ptr), size_x, size_y, stride_x, stride_y, len_x)
+
+
 # ---- stationary wavelet transform of rows (include/libdwt_hip.h, include/swt.h; DESIGN.md s13) -------------------------
 SWT_MAX_LEVELS = 24
 lib.dwt_hip_swt1d_batch.argtypes = [_I, _P, _S, _S, _I, _I, _I, _P, _P, _I, _S, _S]

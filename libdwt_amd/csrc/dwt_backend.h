@@ -51,10 +51,11 @@ struct Ctx {
 	Buf eaw_w, eaw_ll[2]; // EAW: device weights of a host-pointer call, LL ping-pong of the fused levels
 	Buf feat_ws; // feature statistics: records, slab partials, band table, select histograms (dwt_backend_features.hip)
 	Buf swt_ws;  // SWT level by level: the L chain's two dense images (dwt_backend_swt.hip)
+	Buf cond_ws; // row conditioning: per-row medians, extrema, centres, moves, records (dwt_backend_condition.hip)
 	// every device scratch buffer above: a new one is declared there, listed here, and named nowhere else for freeing
 	auto bufs()
 	{
-		return std::array{&stage_img, &ll[0], &ll[1], &frame_a, &frame_b, &vol_out, &vol_host[0], &vol_host[1], &eaw_w, &eaw_ll[0], &eaw_ll[1], &feat_ws, &swt_ws};
+		return std::array{&stage_img, &ll[0], &ll[1], &frame_a, &frame_b, &vol_out, &vol_host[0], &vol_host[1], &eaw_w, &eaw_ll[0], &eaw_ll[1], &feat_ws, &swt_ws, &cond_ws};
 	}
 	hipEvent_t dl_ev[8] = {}; // strip events of the host downloads (dwt_host_xfer.hip), created once
 	hipEvent_t switch_ev = nullptr; // dwt_hip_set_stream: orders a newly set stream behind the old one's work
@@ -66,6 +67,7 @@ struct Ctx {
 	size_t pin_bytes = 0;
 	int feat_groups = 0; // workgroups of the feature slab passes (0: the launcher's rule); results do not depend on it
 	int tf_tiled = 1;  // time-frequency planes of dense lines through the LDS-tiled kernel (0: one thread per output, the cross-check)
+	int cond_fused = -1; // conditioning of dense rows of up to N1D_MAX samples: 1 in one launch, 0 one kernel per operation (the cross-check), -1 by batch size
 	int swt_fused = 1; // SWT lines of up to N1D_MAX samples in one launch (0: one launch per level, the cross-check)
 	// options
 	SweepTuning tune;

@@ -352,6 +352,40 @@ hipError_t launch_feat_pick(const FeatImgArgs &a, int pass, hipStream_t s);
 // |x| in place over w x h floats, element (y, x) at y*sx + x*sy bytes
 hipError_t launch_feat_abs(void *p, long sx, long sy, int w, int h, hipStream_t s);
 
+// Conditioning of rows (dwt_condition.hip): median shift, centring, range scaling.  The bits are those of
+// enum dwt_hip_rows_op; a row's record is 4 ints: net offset, moves made, last centre found (-1: none), SCALE skipped it.
+enum CondOp { kCondMedShift = 1, kCondCenter = 2, kCondScale = 4 };
+struct CondLineArgs {
+	char *ptr;        // dense rows of N <= N1D_MAX floats, conditioned in place
+	long line_stride; // bytes
+	int n_lines, N;
+	unsigned ops;
+	int max_iters;
+	float lo, hi;
+	int *info; // device memory, 4 ints per row, or null
+	int *warn; // device memory, two counters the centre evaluations add to: zero norm, crossing not found
+	int vec;   // 16-byte accesses of the rows are aligned
+	int rows;  // rows per workgroup (set by the launcher: cond_rows_per_group, at most n_lines)
+};
+int cond_rows_per_group(int N);
+// all the operations of `ops`, in the order of their bits, in ONE launch
+hipError_t launch_cond_lines(CondLineArgs a, hipStream_t s);
+// the per-operation kernels: sample i of row y at p + y*ls + 4*i, any N >= 1; per-row results in device memory
+hipError_t launch_rows_median(const char *p, long ls, int n_lines, int N, float *med, hipStream_t s);
+hipError_t launch_rows_minmax(const char *p, long ls, int n_lines, int N, float *mn, float *mx, hipStream_t s);
+// center[y]; displ[y] = center - N/2, info updated as by one iteration of center1, *moved set if any row moves (each optional);
+// warn: two counters added to (zero norm, crossing not found); skip_done: rows whose displ is 0 are not looked at again
+hipError_t launch_rows_center(const char *p, long ls, int n_lines, int N, int *center, int *displ, int *info, int *moved, int *warn,
+	int skip_done, hipStream_t s);
+// dst[x] = src[x + d] (d = displ[y], or displ_all), outside the row zero (zero_fill) or the nearest sample; src != dst
+hipError_t launch_rows_displace(const char *src, long sls, char *dst, long dls, int n_lines, int N, const int *displ, int displ_all,
+	int zero_fill, hipStream_t s);
+// element (y, x) at p + y*sx + x*sy.  op 0: += a; 1: *= a; 2: += -v[y]; 3: scale21 to [a, b] from min v[y] and max v2[y],
+// the skip flag into info[4*y + 3] (info optional)
+hipError_t launch_elem_op(char *p, long sx, long sy, int w, int h, int op, float a, float b, const float *v, const float *v2, int *info,
+	hipStream_t s);
+hipError_t launch_info_init(int *info, int n_lines, hipStream_t s);
+
 // The stationary (undecimated) wavelet transform of rows (dwt_swt1d.hip): level l filters the previous
 // level's low-pass plane with both filters dilated by 1 << (level0 + l), borders replicated; every plane has N samples.
 constexpr int SWT_MAX_LEVELS = 24; // level0 + levels <= 24: (half a filter) << level stays far inside int
