@@ -399,6 +399,67 @@ int dwt_hip_rows_displace(void *ptr, size_t line_stride, size_t elem_stride, int
 int dwt_hip_shift(void *ptr, int stride_x, int stride_y, int size_x, int size_y, float a);
 int dwt_hip_scale(void *ptr, int stride_x, int stride_y, int size_x, int size_y, float a);
 
+/* Per-band coefficient operators: what the reference's synthesis programs do between a forward and an inverse transform
+ * (examples/hdr, examples/mra, examples/displ-vectors, src/denoise.c), on coefficients that stay where they lie (DESIGN.md
+ * s17).  A Mallat frame decomposed to J levels has 3J + 1 SLOTS: slot 3(j-1) + {0, 1, 2} is HL, LH, HH of level j = 1 .. J,
+ * slot 3J is LL of level J, each with the geometry of dwt_util_subband_s over the outer and inner sizes.  Empty bands keep
+ * their slot; a frame of one row has its H bands in the HL slots.  Every slot carries one operator and one float `a`:
+ *   KEEP      untouched: neither read nor written
+ *   ZERO      +0.0f
+ *   SCALE     c * a                                   (dwt_util_scale_s)
+ *   HARD      fabsf(c) > a ? c : +0.0f
+ *   SOFT      c > a ? c - a : (c < -a ? c + a : +0.0f)
+ *   COMPRESS  s * P, s = c > 0 ? +1 : -1, P = |c|^a  (dwt_util_compress_s of examples/hdr/hdr.c; P is pow in double
+ *             rounded to float once: within 1 ulp of the correctly rounded float, where the reference calls powf)
+ * A NaN coefficient is left as it is by every operator but ZERO.  ONE kernel launch applies the whole table to every
+ * frame of a batch, in place; a table of KEEPs launches nothing.
+ * Levels: j_max is the level count the forward transform RETURNED (its `*j`).  j_max < 0 stands for what the transforms
+ * give these sizes by default (ceil(log2) of the smaller side; of the length of a single row or column) and a j_max
+ * beyond ceil(log2) of the larger side is cut to that; dwt_hip_band_levels returns the count a call will use, and the
+ * tables hold dwt_hip_band_slots(that count) entries.
+ * `ptr` may be host or device memory; `ops` / `params` are HOST arrays.  Dense device frames (stride_y == 4) run where
+ * they lie, host frames and other strides are staged through a dense device image and only the frame's own elements are
+ * written back.  Calls are ordered on the context's stream.  Bad sizes, a null table or an unknown operator return an
+ * error and launch nothing. */
+enum dwt_hip_band_op {
+	DWT_HIP_BAND_KEEP = 0,
+	DWT_HIP_BAND_ZERO,
+	DWT_HIP_BAND_SCALE,
+	DWT_HIP_BAND_HARD,
+	DWT_HIP_BAND_SOFT,
+	DWT_HIP_BAND_COMPRESS
+};
+#define DWT_HIP_BAND_MAX_SLOTS 94 /* 3 * 31 + 1: no table is longer */
+/* 3 * j_max + 1 (-1 for j_max outside 0 .. 31) */
+int dwt_hip_band_slots(int j_max);
+/* the level count the band entries use for a frame of these outer sizes and this j_max (-1: bad sizes) */
+int dwt_hip_band_levels(int size_o_x, int size_o_y, int j_max);
+/* {x, y, size_x, size_y} of every slot, in elements from the frame's origin -> xywh (4 ints per slot); returns the slot
+ * count, -1 for bad sizes */
+int dwt_hip_band_geometry(int size_o_x, int size_o_y, int size_i_x, int size_i_y, int j_max, int *xywh);
+int dwt_hip_bands_apply(void *ptr, int stride_x, int stride_y, int size_o_x, int size_o_y, int size_i_x, int size_i_y,
+	int j_max, const int *ops, const float *params);
+/* `batch` dense frames (size_o == size_i) batch_stride bytes apart.  table_stride 0: one table for all frames;
+ * otherwise frame b reads ops + b * table_stride and params + b * table_stride (per-image thresholds) -- still ONE
+ * launch (the tables cross to the device in one small copy). */
+int dwt_hip_bands_apply_batch(void *ptr, size_t batch_stride, int batch, int stride_x, int size_x, int size_y, int j_max,
+	const int *ops, const float *params, size_t table_stride);
+/* The pointwise maps of the hdr flow over a frame or a batch of frames, in place, one launch:
+ *   LOG  (float)log((double)(c + a)), c + a the float sum        (the reference's logf(*c + eps))
+ *   EXP  (float)exp((double)c) - a, a float subtraction          (expf(*c) - eps)
+ * NaN stays NaN.  Memory spaces as above. */
+enum dwt_hip_map_op { DWT_HIP_MAP_LOG = 0, DWT_HIP_MAP_EXP };
+int dwt_hip_map(int op, void *ptr, int stride_x, int stride_y, int size_x, int size_y, float a);
+int dwt_hip_map_batch(int op, void *ptr, size_t batch_stride, int batch, int stride_x, int size_x, int size_y, float a);
+/* The universal threshold of every frame of a batch of transformed dense frames -> lambda (HOST memory, one per frame):
+ *   lambda = (med / 0.6745f) * sqrtf(2.f * logf((float)(size_x * size_y))),
+ * med the median magnitude of the Mallat HH(1) band (the element of rank n/2 of |c|, as dwt_util_abs_s +
+ * dwt_util_band_med_s give it on a copy), finished in float as the reference's denoise_estimate_threshold writes it.  The
+ * frames are only read.  NOT a drop-in for that function, which addresses HH(1) as element (1, 1) with both strides
+ * 2 * stride_x and so reads past the frame of every real image. */
+int dwt_hip_universal_threshold_batch(const void *ptr, size_t batch_stride, int batch, int stride_x, int size_x, int size_y,
+	float *lambda);
+
 /* The stationary (undecimated) wavelet transform of rows: swt_cdf97_f_ex_stride_s / swt_cdf53_f_ex_stride_s (src/swt.c),
  * every level of a batch of lines in one call.  Level l (0-based) filters the low-pass plane of level
  * l-1 (level 0: the input) with the low-pass and the high-pass filter dilated by 1 << l, borders replicated; every plane

@@ -981,6 +981,113 @@ def dwt_util_crop21(ptr, size_x, size_y, stride_x, stride_y, len_x):
     return lib.dwt_util_crop21(_addr(ptr), size_x, size_y, stride_x, stride_y, len_x)
 
 
+# ---- per-band coefficient operators, log / exp maps, universal threshold (include/libdwt_hip.h) ----------
+BAND_OP = {"keep": 0, "zero": 1, "scale": 2, "hard": 3, "soft": 4, "compress": 5}  # name -> enum dwt_hip_band_op
+MAP_OP = {"log": 0, "exp": 1}  # name -> enum dwt_hip_map_op
+lib.dwt_hip_band_slots.argtypes = [_I]
+lib.dwt_hip_band_slots.restype = _I
+lib.dwt_hip_band_levels.argtypes = [_I, _I, _I]
+lib.dwt_hip_band_levels.restype = _I
+lib.dwt_hip_band_geometry.argtypes = [_I, _I, _I, _I, _I, _P]
+lib.dwt_hip_band_geometry.restype = _I
+lib.dwt_hip_bands_apply.argtypes = [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P]
+lib.dwt_hip_bands_apply.restype = _I
+lib.dwt_hip_bands_apply_batch.argtypes = [_P, _S, _I, _I, _I, _I, _I, _P, _P, _S]
+lib.dwt_hip_bands_apply_batch.restype = _I
+lib.dwt_hip_map.argtypes = [_I, _P, _I, _I, _I, _I, _F]
+lib.dwt_hip_map.restype = _I
+lib.dwt_hip_map_batch.argtypes = [_I, _P, _S, _I, _I, _I, _I, _F]
+lib.dwt_hip_map_batch.restype = _I
+lib.dwt_hip_universal_threshold_batch.argtypes = [_P, _S, _I, _I, _I, _I, _P]
+lib.dwt_hip_universal_threshold_batch.restype = _I
+
+
+def band_slots(j_max):
+    """dwt_hip_band_slots: 3 * j_max + 1, the entries of a table for j_max levels."""
+    n = lib.dwt_hip_band_slots(j_max)
+    if n < 0:
+        raise DwtError("dwt_hip_band_slots: bad level count %d" % j_max)
+    return n
+
+
+def band_levels(size_o_x, size_o_y, j_max=-1):
+    """dwt_hip_band_levels: the level count the band entries use for these sizes and this j_max."""
+    n = lib.dwt_hip_band_levels(size_o_x, size_o_y, j_max)
+    if n < 0:
+        raise DwtError("dwt_hip_band_levels: bad sizes")
+    return n
+
+
+def band_geometry(size_o_x, size_o_y, size_i_x, size_i_y, j_max=-1):
+    """dwt_hip_band_geometry -> int32 array (slots, 4) of x, y, size_x, size_y."""
+    import numpy as np
+
+    out = np.zeros((94, 4), dtype=np.int32)
+    n = lib.dwt_hip_band_geometry(size_o_x, size_o_y, size_i_x, size_i_y, j_max, out.ctypes.data)
+    if n < 0:
+        raise DwtError("dwt_hip_band_geometry: bad sizes")
+    return out[:n]
+
+
+def _band_table(ops, params):
+    """(int32 array, float32 array) of a table given as numbers or names of BAND_OP; the arrays are what the C entry reads"""
+    import numpy as np
+
+    if ops is None or params is None:
+        return None, None
+    if not isinstance(ops, np.ndarray):
+        ops = [[BAND_OP[o] if isinstance(o, str) else int(o) for o in row] if isinstance(row, (list, tuple)) else
+               (BAND_OP[row] if isinstance(row, str) else int(row)) for row in ops]
+    return np.ascontiguousarray(ops, dtype=np.int32), np.ascontiguousarray(params, dtype=np.float32)
+
+
+def bands_apply(ptr, stride_x, stride_y, size_o_x, size_o_y, size_i_x, size_i_y, j_max, ops, params):
+    """dwt_hip_bands_apply: one operator and one parameter per slot of a Mallat frame (host or device), in place, in one
+    launch.  `ops` holds numbers or names of BAND_OP, band_slots(band_levels(size_o_x, size_o_y, j_max)) of them."""
+    o, p = _band_table(ops, params)
+    _check(lib.dwt_hip_bands_apply(_addr(ptr), stride_x, stride_y, size_o_x, size_o_y, size_i_x, size_i_y, j_max,
+                                   None if o is None else o.ctypes.data, None if p is None else p.ctypes.data), "dwt_hip_bands_apply")
+
+
+def bands_apply_batch(ptr, batch_stride, batch, stride_x, size_x, size_y, j_max, ops, params, table_stride=0):
+    """dwt_hip_bands_apply_batch: table_stride 0 -- one table for every frame; otherwise frame b's table at entry
+    b * table_stride of `ops` / `params` (per-image thresholds), still one launch."""
+    o, p = _band_table(ops, params)
+    _check(lib.dwt_hip_bands_apply_batch(_addr(ptr), batch_stride, batch, stride_x, size_x, size_y, j_max,
+                                         None if o is None else o.ctypes.data, None if p is None else p.ctypes.data, table_stride),
+           "dwt_hip_bands_apply_batch")
+
+
+def map_log(ptr, stride_x, stride_y, size_x, size_y, a):
+    """dwt_hip_map(LOG): c = log(c + a) in place (the hdr flow's logf(*c + eps))."""
+    _check(lib.dwt_hip_map(0, _addr(ptr), stride_x, stride_y, size_x, size_y, float(a)), "dwt_hip_map")
+
+
+def map_exp(ptr, stride_x, stride_y, size_x, size_y, a):
+    """dwt_hip_map(EXP): c = exp(c) - a in place."""
+    _check(lib.dwt_hip_map(1, _addr(ptr), stride_x, stride_y, size_x, size_y, float(a)), "dwt_hip_map")
+
+
+def map_log_batch(ptr, batch_stride, batch, stride_x, size_x, size_y, a):
+    _check(lib.dwt_hip_map_batch(0, _addr(ptr), batch_stride, batch, stride_x, size_x, size_y, float(a)), "dwt_hip_map_batch")
+
+
+def map_exp_batch(ptr, batch_stride, batch, stride_x, size_x, size_y, a):
+    _check(lib.dwt_hip_map_batch(1, _addr(ptr), batch_stride, batch, stride_x, size_x, size_y, float(a)), "dwt_hip_map_batch")
+
+
+def universal_threshold_batch(ptr, batch_stride, batch, stride_x, size_x, size_y, lam=None):
+    """dwt_hip_universal_threshold_batch -> float32 host array, one threshold per frame, from the median magnitude of
+    the Mallat HH(1) band; the frames are only read."""
+    import numpy as np
+
+    if lam is None:
+        lam = np.zeros(batch, dtype=np.float32)
+    _check(lib.dwt_hip_universal_threshold_batch(_addr(ptr), batch_stride, batch, stride_x, size_x, size_y, lam.ctypes.data),
+           "dwt_hip_universal_threshold_batch")
+    return lam
+
+
 # ---- stationary wavelet transform of rows (include/libdwt_hip.h, include/swt.h; DESIGN.md s13) -------------------------
 SWT_MAX_LEVELS = 24
 lib.dwt_hip_swt1d_batch.argtypes = [_I, _P, _S, _S, _I, _I, _I, _P, _P, _I, _S, _S]

@@ -52,10 +52,11 @@ struct Ctx {
 	Buf feat_ws; // feature statistics: records, slab partials, band table, select histograms (dwt_backend_features.hip)
 	Buf swt_ws;  // SWT level by level: the L chain's two dense images (dwt_backend_swt.hip)
 	Buf cond_ws; // row conditioning: per-row medians, extrema, centres, moves, records (dwt_backend_condition.hip)
+	Buf band_ws; // band operators: the per-image operator tables of a batch (dwt_backend_bandops.hip)
 	// every device scratch buffer above: a new one is declared there, listed here, and named nowhere else for freeing
 	auto bufs()
 	{
-		return std::array{&stage_img, &ll[0], &ll[1], &frame_a, &frame_b, &vol_out, &vol_host[0], &vol_host[1], &eaw_w, &eaw_ll[0], &eaw_ll[1], &feat_ws, &swt_ws, &cond_ws};
+		return std::array{&stage_img, &ll[0], &ll[1], &frame_a, &frame_b, &vol_out, &vol_host[0], &vol_host[1], &eaw_w, &eaw_ll[0], &eaw_ll[1], &feat_ws, &swt_ws, &cond_ws, &band_ws};
 	}
 	hipEvent_t dl_ev[8] = {}; // strip events of the host downloads (dwt_host_xfer.hip), created once
 	hipEvent_t switch_ev = nullptr; // dwt_hip_set_stream: orders a newly set stream behind the old one's work
@@ -239,6 +240,8 @@ int host_inverse_pipelined(Wavelet w, const void *src, void *dst, int stride_x, 
 bool swt_fused_ok(const void *src, long ls, long es, int N);
 int swt_device(Wavelet w, const char *src, long ls, long es, int n_lines, int N, int level0, int levels, char *dst_h, long h_es,
 	char *dst_l, long l_es, int l_mode, long plane_stride, long dls);
+// the median magnitude of one band of every frame of a batch, the frames only read (dwt_backend_features.hip) -> med (host)
+int band_abs_median(const void *ptr, long bstride, int batch, long stride_x, int fw, int fh, int x0, int y0, int w, int h, float *med);
 int prof_drain();
 void prof_before(int level = 0);
 void prof_after(int level = 0);

@@ -148,6 +148,22 @@ int pmode_of(unsigned mask, float p)
 int finish_records(const u64 *rec, long nrec, int batch, const Band *bands, int nb, unsigned mask, int pmode, float p, const Moment &mom,
 	float *fv, long fv_stride);
 
+// a band's entry of the device table: cut into slabs, the first of them slab `slab0` of its image
+FeatBand cut_slabs(const Band &b, int slab0)
+{
+	FeatBand t;
+	t.x0 = b.x0;
+	t.y0 = b.y0;
+	t.w = b.w;
+	t.h = b.h;
+	t.cw = std::min(t.w, FEAT_SLAB_COLS);
+	t.rh = std::max(1, FEAT_SLAB / t.cw);
+	t.ncc = (t.w + t.cw - 1) / t.cw;
+	t.nslab = t.ncc * ((t.h + t.rh - 1) / t.rh);
+	t.slab0 = slab0;
+	return t;
+}
+
 // `batch` dense device images (4-byte elements, pitch d.sx) bstride bytes apart -> fv (HOST memory): per image one
 // block of nb floats per feature of `mask` in enum order, images fv_stride floats apart.
 int run_device(Img d, long bstride, int batch, const Band *bands, int nb, bool lines, int N, unsigned mask, float p, const Moment &mom,
@@ -183,17 +199,8 @@ int run_device(Img d, long bstride, int batch, const Band *bands, int nb, bool l
 		static thread_local FeatBand tab[FEAT_MAX_BANDS]; // (outlives the asynchronous copy below; the call ends synchronised)
 		int slabs = 0;
 		for (int k = 0; k < nb; k++) {
-			FeatBand &t = tab[k];
-			t.x0 = bands[k].x0;
-			t.y0 = bands[k].y0;
-			t.w = bands[k].w;
-			t.h = bands[k].h;
-			t.cw = std::min(t.w, FEAT_SLAB_COLS);
-			t.rh = std::max(1, FEAT_SLAB / t.cw);
-			t.ncc = (t.w + t.cw - 1) / t.cw;
-			t.nslab = t.ncc * ((t.h + t.rh - 1) / t.rh);
-			t.slab0 = slabs;
-			slabs += t.nslab;
+			tab[k] = cut_slabs(bands[k], slabs);
+			slabs += tab[k].nslab;
 		}
 		const long npart = (long)batch * slabs;
 		if (carve(nrec, npart, nb, select, &ws))
@@ -427,6 +434,52 @@ int swt_features_device(Wavelet w, unsigned mask, const char *src, long ls, int 
 }
 
 } // namespace
+
+// The median of |x| over the band (x0, y0, w, h) of each of `batch` dense frames of fw x fh floats -> med (HOST memory):
+// the element of rank w*h/2 of the magnitudes, as dwt_util_abs_s + dwt_util_band_med_s give it on a copy.  The images are
+// only read: the four rounds of the select run with a key that ignores the sign bit.
+int band_abs_median(const void *ptr, long bstride, int batch, long stride_x, int fw, int fh, int x0, int y0, int w, int h, float *med)
+{
+	const bool dev = dwt_hip_is_device_pointer(ptr);
+	if (dev && check_dev_align({ptr}, {stride_x, bstride}))
+		return 1;
+	Img d{nullptr, 0, 4};
+	long dbs = 0;
+	if (stage(ptr, dev, bstride, batch, stride_x, 4, fw, fh, &d, &dbs))
+		return 1;
+	static thread_local FeatBand tab; // (outlives the asynchronous copy below; the call ends synchronised)
+	tab = cut_slabs(Band{x0, y0, w, h, 1}, 0);
+	Ws ws;
+	if (carve(batch, 0, 1, true, &ws))
+		return 1;
+	HIP_TRY(hipMemcpyAsync(ws.bands, &tab, sizeof(FeatBand), hipMemcpyHostToDevice, g.stream));
+	FeatImgArgs a{};
+	a.img = d.p;
+	a.pitch = d.sx;
+	a.bstride = dbs;
+	a.batch = batch;
+	a.nb = 1;
+	a.slabs = tab.nslab;
+	a.bands = ws.bands;
+	a.rec = ws.rec;
+	a.nrec = batch;
+	a.hist = ws.hist;
+	a.sel = ws.sel;
+	a.groups = g.feat_groups;
+	a.abs_key = 1;
+	HIP_TRY(hipMemsetAsync(ws.hist, 0, ws.hist_bytes, g.stream));
+	for (int pass = 0; pass < 4; pass++)
+		if (launched(launch_feat_hist(a, pass, g.stream), "feature", "histogram") || launched(launch_feat_pick(a, pass, g.stream), "feature", "pick"))
+			return 1;
+	std::vector<u64> &host = t_host;
+	host.resize((size_t)batch);
+	t_nrec = 0; // (no raw sums behind this call)
+	HIP_TRY(hipMemcpyAsync(host.data(), ws.rec + (size_t)kFeatMed * batch, (size_t)batch * 8, hipMemcpyDeviceToHost, g.stream));
+	HIP_TRY(hipStreamSynchronize(g.stream));
+	for (int b = 0; b < batch; b++)
+		med[b] = __builtin_bit_cast(float, (unsigned)host[b]);
+	return 0;
+}
 
 } // namespace dwtb
 

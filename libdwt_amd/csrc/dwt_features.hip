@@ -12,6 +12,8 @@
 //   * max / argmax compare one 64-bit key, |x| bits above the complemented index: the largest |x|, then the lowest index;
 //   * the median is a 4 x 8-bit radix select over the order-preserving integer image of the float: integer histogram
 //     atomics, which commute.  NaN inputs are not pinned (the reference's qsort comparator is no order there).
+//     FeatImgArgs::abs_key orders |x| instead (the key ignores the sign bit): the median magnitude of a band that is
+//     only read, for the universal threshold.
 //
 // Lines of up to N1D_MAX samples: k_feat_lines, one workgroup per line, the line in LDS, every band of every level and
 // every statistic from ONE read of the line.  Images and longer lines: bands cut into slabs of about FEAT_SLAB elements;
@@ -203,7 +205,7 @@ __global__ __launch_bounds__(256) void k_feat_hist(FeatImgArgs a, int pass)
 		hist[threadIdx.x] = 0;
 		__syncthreads();
 		walk_slab(s, a.pitch, [&](float x, unsigned) {
-			const unsigned q = okey(x);
+			const unsigned q = okey(a.abs_key ? fabsf(x) : x);
 			if (pass == 0 || (q >> (shift + 8)) == prefix)
 				atomicAdd(&hist[(q >> shift) & 255], 1u);
 		});

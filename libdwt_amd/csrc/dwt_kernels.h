@@ -343,6 +343,7 @@ struct FeatImgArgs {
 	int use_c, mn; // pass 2 about c instead of the band's mean; mn outside 2..4: plane kFeatM2 takes (float)pow(x - c, mn)
 	float c;
 	int groups; // workgroups of the slab passes
+	int abs_key; // the select orders |x| instead of x (the key ignores the sign bit): the median magnitude, the band untouched
 };
 hipError_t launch_feat_pass1(const FeatImgArgs &a, hipStream_t s); // -> part planes 0..3
 hipError_t launch_feat_pass2(const FeatImgArgs &a, hipStream_t s); // -> part planes 0..2
@@ -351,6 +352,30 @@ hipError_t launch_feat_hist(const FeatImgArgs &a, int pass, hipStream_t s);
 hipError_t launch_feat_pick(const FeatImgArgs &a, int pass, hipStream_t s);
 // |x| in place over w x h floats, element (y, x) at y*sx + x*sy bytes
 hipError_t launch_feat_abs(void *p, long sx, long sy, int w, int h, hipStream_t s);
+
+// Per-band coefficient operators (dwt_bandops.hip): one operator and one parameter per slot of a Mallat
+// frame -- slot 3(j-1) + {0, 1, 2} is HL, LH, HH of level j, the last slot LL of the deepest level -- applied in place to
+// every image of a batch in ONE launch.  The ops are those of enum dwt_hip_band_op, then the two pointwise maps.
+enum BandOp { kBandKeep = 0, kBandZero, kBandScale, kBandHard, kBandSoft, kBandCompress, kBandOps, kMapLog = kBandOps, kMapExp, kBandOpsAll };
+constexpr int BAND_MAX_SLOTS = 94; // 3 * 31 + 1
+constexpr int BAND_CHUNK = 16384, BAND_CHUNK_COLS = 4096; // elements per workgroup chunk, widest chunk
+// a band of w x h elements is cut into chunks of band_chunk_cols(w) columns x band_chunk_rows(w) rows, column chunk fastest
+static __host__ __device__ inline int band_chunk_cols(int w) { return w < BAND_CHUNK_COLS ? w : BAND_CHUNK_COLS; }
+static __host__ __device__ inline int band_chunk_rows(int w) { return w < 1 ? 1 : BAND_CHUNK / band_chunk_cols(w); }
+struct BandOpsArgs {
+	char *img;           // dense images of 4-byte elements
+	long pitch, bstride; // bytes
+	int batch, nslots;
+	int x0[BAND_MAX_SLOTS], y0[BAND_MAX_SLOTS], w[BAND_MAX_SLOTS], h[BAND_MAX_SLOTS];
+	int first[BAND_MAX_SLOTS + 1]; // prefix of the slots' chunk counts within one image (a slot no image touches: none)
+	unsigned char op[BAND_MAX_SLOTS + 2];
+	float param[BAND_MAX_SLOTS];
+	// per-image tables (device memory; null: the one table above): image b reads entry b * tstride + slot
+	const int *dev_op;
+	const float *dev_param;
+	long tstride;
+};
+hipError_t launch_band_ops(const BandOpsArgs &a, hipStream_t s);
 
 // Conditioning of rows (dwt_condition.hip): median shift, centring, range scaling.  The bits are those of
 // enum dwt_hip_rows_op; a row's record is 4 ints: net offset, moves made, last centre found (-1: none), SCALE skipped it.
