@@ -98,6 +98,7 @@ struct Ctx {
 	double place_ms[8] = {0};   // what the last search measured, per candidate
 	int place_n = 0, place_best = -1;
 	int fused_d = 1; // double-precision wavelets through the fused sweeps (0: exact line passes only)
+	int fuse01 = 1;  // forward float 9/7, out of place: levels 0 and 1 in one launch -- 1 where it pays, 2 wherever it can run, 0 never (pair01_ok)
 	int ride_copy = 1; // in-place calls on one image: the staged subbands' copy rides along with the deeper levels' launches (0: a launch of its own)
 	int ride_mib = 32; // ... MiB of it per small level (8192^2: 8 / 16 / 24 / 32 / 48 MiB: forward 202 / 202 / 199 / 199 / 199 us, inverse 224 / 227 / 225 / 224 / 229)
 	// profiling
@@ -223,6 +224,7 @@ bool stream_is_capturing();
 bool may_measure(); // inside dwt_hip_tune, or DWT_HIP_TUNE=1 / option "tune_in_call"
 int tuned_tile_pairs(Wavelet w, const FwdLevelArgs &a); // the measured choice for this level (packed; 0: none) ...
 int tuned_tile_pairs(Wavelet w, const InvLevelArgs &a);
+int tuned_tile_pairs01(Wavelet w, const FwdLevelArgs &a); // the same for the fused pair of levels 0 and 1 (launch_fwd01)
 void apply_tile_choice(int choice, SweepTuning *t, bool inverse); // ... applied to the launch's tuning
 int forward2d(Wavelet w, Img src, Img dst, const Geom &ge, int *jp, int decompose_one, int zero_padding, int batch, long src_bstride, long dst_bstride);
 int inverse2d(Wavelet w, Img src, Img dst, const Geom &ge, int j_max, int decompose_one, int zero_padding, int batch, long src_bstride, long dst_bstride);

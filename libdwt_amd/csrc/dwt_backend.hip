@@ -10,6 +10,8 @@
 //     level 0 : image            -> HL/LH/HH at their final place, LL -> scratch0
 //     level j : scratch[(j-1)&1] -> HL/LH/HH at their final place, LL -> scratch[j&1]
 //     last    :                     LL -> its final place too
+//   (large out-of-place float 9/7 calls: levels 0 and 1 in one launch, image -> both levels' HL/LH/HH, LL -> scratch1;
+//    pair01_ok below)
 //
 // Every level therefore reads its input once and writes its output once: the
 // algorithmic traffic 2*sizeof(T)*sum_j(W_j*H_j).  Only when the caller's source
@@ -264,6 +266,33 @@ bool level_fused_ok(const Geom &ge, int j)
 	return !g.force_generic && (g_elems_are_32bit || g.fused_d) && ge.Wi(j) == ge.Wo(j) && ge.Hi(j) == ge.Ho(j) && ge.Wo(j) >= 2 &&
 		ge.Ho(j) >= 2;
 }
+// Levels 0 and 1 of a forward transform in ONE launch (launch_fwd01: overlapped tiles, level 0's LL band never written):
+// float 9/7 without contraction, Mallat layout, out of place (no staging detour, no copy riding along), two levels or
+// more, both fused, W and H multiples of 4 with both levels of 64 x 64 or more, and none of the sweep's geometry set by
+// hand to something the fused kernel is not (it is the 8-column, deep-ring tile).  Option fuse01: 0 never, 2 wherever
+// that holds, 1 (default) where it also pays:
+//   - the launch costs about level 0 x (ntx01 / ntx) x 1.05 (level 1's warm-up rows) x 1.02 (its arithmetic and stores)
+//     against level 0 + level 1 = 1.25 x level 0, so the overlapped tiles may cost up to 16 % more tiles per row; with a
+//     margin for what the overlap costs the caches the rule takes ntx01 / ntx <= 1.10: 8192 columns (17 for 16) and
+//     16384 (35 for 32) qualify, 4096 (9 for 8) and everything narrower do not;
+//   - only in launches of 32768 tiles of 512 columns x 64 pairs and more (32 images of 8192^2), the sizes it was measured
+//     to win at (profiles/fuse01_summary.md).  Below 3072 tiles level 0 does not take the deep ring itself -- a round or
+//     two of waves wants the shallow ring's 8 waves per CU --; in between nothing was measured, and a call on 16 images
+//     of 8192^2 is held to one launch per level (tests/test_hip_multi.py).
+static bool pair01_ok(Wavelet w, const Geom &ge, int J, int batch)
+{
+	const int W = ge.Wo(0), H = ge.Ho(0);
+	if (!g.fuse01 || g.fma || J < 2 || !level_fused_ok(ge, 0) || !level_fused_ok(ge, 1) || !fwd01_can(w, W, H))
+		return false;
+	const SweepTuning &t = g.tune;
+	if (t.cpt == 4 || t.ring == 8 || (t.nt & 8) || (t.tile_pairs & 1))
+		return false;
+	if (g.fuse01 >= 2)
+		return true;
+	const long ntx = (W + 511) / 512, nty = ((H >> 1) + 63) / 64;
+	return fwd01_tiles(W) * 10 <= ntx * 11 && ntx * nty * batch >= 32768;
+}
+
 // ---- forward ---------------------------------------------------------------------
 int forward2d(Wavelet w, Img src, Img dst, const Geom &ge, int *jp, int decompose_one, int zero_padding,
 	int batch, long src_bstride, long dst_bstride)
@@ -295,7 +324,10 @@ int forward2d(Wavelet w, Img src, Img dst, const Geom &ge, int *jp, int decompos
 		const int Wo = ge.Wo(j), Ho = ge.Ho(j), Wi = ge.Wi(j), Hi = ge.Hi(j);
 		const int Wd = ge.Wo(j + 1), Hd = ge.Ho(j + 1);
 		if (level_fused_ok(ge, j)) {
-			const bool last = (j == J - 1) || !level_fused_ok(ge, j + 1);
+			// (a fused pair: levels 0 and 1 of an out-of-place call; jl: the level whose LL band leaves the launch)
+			const bool pair = j == 0 && ll_in < 0 && cur.p != dst.p && pair01_ok(w, ge, J, batch);
+			const int jl = pair ? j + 1 : j;
+			const bool last = (jl == J - 1) || !level_fused_ok(ge, jl + 1);
 			FwdLevelArgs a;
 			a.W = Wo;
 			a.H = Ho;
@@ -328,21 +360,21 @@ int forward2d(Wavelet w, Img src, Img dst, const Geom &ge, int *jp, int decompos
 			a.out_h = hdst.p;
 			a.h_pitch = hdst.sx / es;
 			a.h_bstride = h_bstride / es;
-			// ping-pong: the other buffer than the one read (after a fused pair the parity
-			// of the level no longer tells which one that is); band j+1 fits either for j >= 1
-			const int ll_out = last ? -1 : (ll_in < 0 ? (j & 1) : 1 - ll_in);
+			// ping-pong: the other buffer than the one read; band j+1 fits either for j >= 1.  A fused pair writes level 1's
+			// band where the two launches would have left it, in scratch 1 (scratch 0 is sized for level 0's band, unused then)
+			const int ll_out = last ? -1 : (ll_in < 0 ? (jl & 1) : 1 - ll_in);
 			if (last) {
 				a.out_ll = hdst.p;
 				a.ll_pitch = a.h_pitch;
 				a.ll_bstride = a.h_bstride;
 			} else {
 				a.out_ll = ll_band(ll_out);
-				a.ll_pitch = ll_pitch_elems(Wd);
-				a.ll_bstride = a.ll_pitch * Hd;
+				a.ll_pitch = ll_pitch_elems(ge.Wo(jl + 1));
+				a.ll_bstride = a.ll_pitch * ge.Ho(jl + 1);
 			}
 			SweepTuning tune = g.tune;
 			if (!dbl && tune.tile_pairs <= 0)
-				apply_tile_choice(tuned_tile_pairs(w, a), &tune, false); // (nothing measured: the launcher's own rule)
+				apply_tile_choice(pair ? tuned_tile_pairs01(w, a) : tuned_tile_pairs(w, a), &tune, false); // (nothing measured: the launcher's own rule)
 			if (ride.on && ride.next < ride.total && !dbl && sweep_ride_ok(tune, Wo, Ho, batch, false)) {
 				a.ride = &ride.r;
 				a.ride_lo = ride.next;
@@ -350,8 +382,9 @@ int forward2d(Wavelet w, Img src, Img dst, const Geom &ge, int *jp, int decompos
 				ride.next = a.ride_hi;
 			}
 			prof_before(j);
-			hipError_t e = dbl ? launch_fwd_level_d(w, a, tune, g.stream)
-			                   : launch_fwd_level((g.fma && w == kCdf97S) ? kCdf97SFma : w, a, tune, g.stream);
+			hipError_t e = pair ? launch_fwd01(a, tune, g.stream)
+			             : dbl  ? launch_fwd_level_d(w, a, tune, g.stream)
+			                    : launch_fwd_level((g.fma && w == kCdf97S) ? kCdf97SFma : w, a, tune, g.stream);
 			prof_after(j);
 			if (e != hipSuccess)
 				return fail("forward level %d launch failed: %s", j, hipGetErrorString(e));
@@ -369,6 +402,7 @@ int forward2d(Wavelet w, Img src, Img dst, const Geom &ge, int *jp, int decompos
 			}
 			ll_in = ll_out;
 			cur = dst;
+			j = jl;
 			continue;
 		}
 

@@ -118,6 +118,14 @@ struct InvLevelArgs {
 struct IlStripArgs;
 hipError_t launch_fwd_level(Wavelet w, const FwdLevelArgs &a, const SweepTuning &t, hipStream_t s, const IlStripArgs *strip = nullptr);
 
+// Levels 0 AND 1 of a forward float 9/7 transform (Mallat, out of place) in ONE sweep over overlapped tiles
+// (k_fwd_sweep01): `a` describes level 0, except that out_ll / ll_pitch / ll_bstride are LEVEL 1's LL band -- level 0's is
+// never written -- and level 1's detail subbands go to their Mallat places relative to out_h as well.  Same bits as the
+// two launches.  fwd01_can: W and H multiples of 4, both levels of 64 x 64 or more; fwd01_tiles: tiles per row.
+bool fwd01_can(Wavelet w, int W, int H);
+int fwd01_tiles(int W);
+hipError_t launch_fwd01(const FwdLevelArgs &a, const SweepTuning &t, hipStream_t s);
+
 hipError_t launch_inv_level(Wavelet w, const InvLevelArgs &a, const SweepTuning &t, hipStream_t s, const IlStripArgs *strip = nullptr);
 // the same two sweeps for the double-precision wavelets (dwt_sweep2d_d.hip); pitches in 8-byte ELEMENTS
 hipError_t launch_fwd_level_d(Wavelet w, const FwdLevelArgs &a, const SweepTuning &t, hipStream_t s);

@@ -185,9 +185,27 @@ static __device__ __forceinline__ void vertical_pairs(const T (&row)[2][CPT], T 
 	}
 }
 
-template <class W, int CPT, int RING, int NT, bool IL, bool X>
+// F01 (float 9/7 by selection, 8 columns per lane, Mallat): levels 0 AND 1 in this one sweep.  The tiles keep their 512
+// columns but start 480 apart (15 lines of 128 bytes: every row load stays line-aligned), so that each seam of level 1 is
+// computed twice, inside a wave, and nothing passes between waves:
+//   - after the vertical pass a lane holds 4 samples of the LL row its iteration completes; level 1's horizontal lift
+//     takes the 4 neighbours on either side from the adjacent lanes' registers (wavefront shifts).  Lanes 0 and 63 have
+//     no such neighbour: their level-1 results are valid only where the lane holds an end of the line, which takes the
+//     end form (selection, doubled coefficient) and needs none;
+//   - every second iteration completes an LL row pair: level 1's horizontal lift of both rows, its vertical pass (a state
+//     of 4 columns) and the stores of its four quarter rows.  Its ends of a column take the end form too, the bottom one
+//     by dropping the NEWER tap: the rows this sweep computes beyond the last LL row mirror the level's input, not the band;
+//   - tile t stores the level-0 details of its first 480 columns (lanes 0..59) and level 1 of lanes 1..60 (LL columns
+//     240 t + 4 .. 240 t + 243); tile 0 also lane 0, the tile that holds the last column everything up to it.  Every
+//     sample is written once; the LL band of level 0 is never written.  `out_ll` is level 1's LL band;
+//   - vertically a tile warms level 1 up with 4 more iterations above (none at the top of the image: the end form cuts
+//     the dependence) and flushes it with 3 more below.
+// W and H are multiples of 4 and at least 128 (both levels of 64 x 64 or more); the last column of either level can then
+// be a lane's last own column or the one in the middle of its columns, and both are candidates of the selection.
+template <class W, int CPT, int RING, int NT, bool IL, bool X, bool F01 = false>
 static __device__ __forceinline__ void fwd_sweep_tile(const FwdLevelArgs &a, const SweepGeom &g)
 {
+	static_assert(!F01 || (kIsSelEnds<W> && CPT == 8 && !IL && !X && W::K == 4 && !(NT & 8)), "the fused pair: float 9/7 by selection, Mallat");
 	using T = typename W::T;
 	constexpr int K = W::K;
 	constexpr int kRing = RING;           // ring rows per wave (any even number)
@@ -216,6 +234,12 @@ static __device__ __forceinline__ void fwd_sweep_tile(const FwdLevelArgs &a, con
 	const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
 	const int bid = tile_block_id(g.swz, X ? g.first : 0, g.tile_blocks);
 	int tx, ty;
+	if constexpr (F01) {
+		// (consecutive waves take consecutive tiles across the rows' ends: a row of 17 tiles leaves no wave of a workgroup idle)
+		const int t = bid * nwv + wv;
+		tx = t % g.ntx;
+		ty = t / g.ntx;
+	} else
 	if (g.wave_horiz) {
 		const int ntxb = (g.ntx + nwv - 1) / nwv;
 		tx = (bid % ntxb) * nwv + wv;
@@ -232,9 +256,10 @@ static __device__ __forceinline__ void fwd_sweep_tile(const FwdLevelArgs &a, con
 	if (a.pair_hi > 0 && (A < a.pair_lo || A >= a.pair_hi))
 		return; // this launch computes a band of the level only
 	const int B = min(A + g.tile_pairs, Hd);
-	const int c0 = tx * TW;
-	const int n_iter = (B - A) + K;
-	const int q0 = A - K / 2;
+	const int c0 = tx * (F01 ? TW - 32 : TW);
+	const int warm = (F01 && A > 0) ? K : 0; // level 1's warm-up above the tile
+	const int n_iter = (B - A) + K + warm + (F01 ? 3 : 0);
+	const int q0 = A - K / 2 - warm;
 
 	const T *in = (const T *)a.in + (long)img * a.in_bstride;
 	T *out_ll = (T *)a.out_ll + (long)img * a.ll_bstride;
@@ -298,7 +323,7 @@ static __device__ __forceinline__ void fwd_sweep_tile(const FwdLevelArgs &a, con
 			// tile above at the end of its march.  The first read is TEMPORAL whatever the policy, so that the
 			// lines can wait in the Infinity Cache for the second one (every other row is read once).  Round 4,
 			// 32 x 8192^2, one placement: level 0 6108 -> 6240 GB/s; with the halo columns temporal too 6285.
-			if (kLdAux != 0 && it < K && A > 0) {
+			if (kLdAux != 0 && it < K + warm && A > 0) {
 #pragma unroll
 				for (int i = 0; i < CPT / 4; i++)
 					dma16_row<0>(rs, (unsigned)(c0 + i * 256 + lane * 4) * 4, lrow + i * 1024);
@@ -352,6 +377,22 @@ static __device__ __forceinline__ void fwd_sweep_tile(const FwdLevelArgs &a, con
 		e0 = (m >> HK) & 1;
 		e1 = (m >> (HK + CPT - 1)) & 1;
 		sel_coefs<W, false, HK>(kh, e0, e1);
+	}
+	// (F01) the last column in the middle of a lane's columns (a width that is 4 modulo 8); level 1's candidates in its
+	// window of 12 (the neighbours' 4, the lane's own 4): column 0 at entry 4, the last column at 5 or 7, or at 9 -- the
+	// right neighbour's second column, which this lane's results reach through step 0; the rows level 1 holds back
+	[[maybe_unused]] bool e1m = false, g0 = false, g5 = false, g7 = false, g9 = false, own0 = true, own1 = true;
+	[[maybe_unused]] T st1[K][4] = {}, held[4] = {};
+	if constexpr (F01) {
+		e1m = c0 + lane * CPT + 3 == a.W - 1;
+		const unsigned m1 = end_mask_long<12>((c0 >> 1) + lane * 4 - 4, a.W >> 1);
+		g0 = (m1 >> 4) & 1;
+		g5 = (m1 >> 5) & 1;
+		g7 = (m1 >> 7) & 1;
+		g9 = (m1 >> 9) & 1;
+		const bool last_tile = tx == g.ntx - 1;
+		own0 = last_tile || lane < 60;
+		own1 = (tx == 0 || lane >= 1) && (last_tile || lane <= 60);
 	}
 	// row r (any r the sweep meets) is an end of its column: r == 0 or r == H - 1 after reflection (one bounce when tall)
 	[[maybe_unused]] auto row_is_end = [&](int r) {
@@ -465,6 +506,8 @@ static __device__ __forceinline__ void fwd_sweep_tile(const FwdLevelArgs &a, con
 						x2[j] = x2[j] + kh[s_] * ((e0 ? f2{-0.0f, -0.0f} : x2[j - 1]) + x2[j + 1]);
 					else if (j == HK + CPT - 1)
 						x2[j] = x2[j] + kh[s_] * (x2[j - 1] + (e1 ? f2{-0.0f, -0.0f} : x2[j + 1]));
+					else if (F01 && j == HK + 3)
+						x2[j] = x2[j] + (e1m ? 2.0f * W::fk(s_) : W::fk(s_)) * (x2[j - 1] + (e1m ? f2{-0.0f, -0.0f} : x2[j + 1]));
 					else
 						x2[j] = x2[j] + W::fk(s_) * (x2[j - 1] + x2[j + 1]);
 				}
@@ -656,6 +699,96 @@ static __device__ __forceinline__ void fwd_sweep_tile(const FwdLevelArgs &a, con
 				}
 			}
 		} else
+		if constexpr (F01) {
+			typedef float f2 __attribute__((ext_vector_type(2)));
+			const f2 nz = f2{-0.0f, -0.0f};
+			const int k = q0 + it - K / 2; // the pair of level 0 this iteration completes (k and `it` are both even or both odd)
+			if (k >= A && k < B && own0) {
+				const unsigned clb = (unsigned)((c0 + lane * CPT) >> 1) * 4;
+				const T *top = out_h + (long)k * a.h_pitch, *bot = out_h + (long)(Hd + k) * a.h_pitch;
+				const unsigned nb = (unsigned)Wd * 4;
+				store16_row<kNtStore>(row_rsrc(top + Wd, nb), clb, u4{to_bits(lo[1]), to_bits(lo[3]), to_bits(lo[5]), to_bits(lo[7])});
+				store16_row<kNtStore>(row_rsrc(bot, nb), clb, u4{to_bits(hi[0]), to_bits(hi[2]), to_bits(hi[4]), to_bits(hi[6])});
+				store16_row<kNtStore>(row_rsrc(bot + Wd, nb), clb, u4{to_bits(hi[1]), to_bits(hi[3]), to_bits(hi[5]), to_bits(hi[7])});
+			}
+			if (it & 1) {
+				// LL row k, odd: waits for its pair
+#pragma unroll
+				for (int e = 0; e < 4; e++)
+					held[e] = lo[2 * e];
+			} else {
+				// level 1, iteration q1: its rows 2 q1 - 1 (held) and 2 q1 (this LL row), as the halves of packed operations
+				const int q1 = k >> 1, W1 = Wd, H1 = Hd;
+				f2 y[12];
+#pragma unroll
+				for (int e = 0; e < 4; e++) {
+					const unsigned b0 = to_bits(held[e]), b1 = to_bits(lo[2 * e]);
+					y[e] = f2{from_bits<T>(from_left_lane(b0)), from_bits<T>(from_left_lane(b1))};
+					y[4 + e] = f2{held[e], lo[2 * e]};
+					y[8 + e] = f2{from_bits<T>(from_right_lane(b0)), from_bits<T>(from_right_lane(b1))};
+				}
+#pragma unroll
+				for (int s_ = 0; s_ < K; s_++) {
+#pragma unroll
+					for (int j = s_ + 1; j <= 10 - s_; j += 2) {
+						if (j == 4 || j == 5 || j == 7 || j == 9) {
+							const bool el = j == 4 && g0, er = j == 5 ? g5 : j == 7 ? g7 : j == 9 ? g9 : false;
+							y[j] = y[j] + ((el || er) ? 2.0f * W::fk(s_) : W::fk(s_)) * ((el ? nz : y[j - 1]) + (er ? nz : y[j + 1]));
+						} else
+							y[j] = y[j] + W::fk(s_) * (y[j - 1] + y[j + 1]);
+					}
+				}
+				const float ze = W::fwd_scale(0, 1.0f), zo = W::fwd_scale(1, 1.0f);
+				// vertical pass: step s acts on row 2 q1 - 1 - s; row 0 drops its older tap, row H1 - 1 its newer one
+				bool vt[K], vb[K];
+				T kv[K];
+#pragma unroll
+				for (int s_ = 0; s_ < K; s_++) {
+					vt[s_] = 2 * q1 - 1 - s_ == 0;
+					vb[s_] = 2 * q1 - 1 - s_ == H1 - 1;
+					kv[s_] = (vt[s_] || vb[s_]) ? 2.0f * W::fk(s_) : W::fk(s_);
+				}
+				auto older = [&](int s_, f2 v) { return vt[s_] ? nz : v; };
+				auto newer = [&](int s_, f2 v) { return vb[s_] ? nz : v; };
+				T lo1[4], hi1[4];
+#pragma unroll
+				for (int v = 0; v < 2; v++) {
+					// (columns v and v + 2: the stores take them as consecutive registers)
+					const f2 c0v = y[4 + v] * (v ? zo : ze), c2v = y[6 + v] * (v ? zo : ze);
+					const f2 ov = f2{c0v[0], c2v[0]}, ev = f2{c0v[1], c2v[1]};
+					f2 s_[K], n_[K];
+#pragma unroll
+					for (int i = 0; i < K; i++)
+						s_[i] = f2{st1[i][v], st1[i][v + 2]};
+					n_[0] = ev;
+					n_[1] = ov + kv[0] * (older(0, s_[0]) + newer(0, ev));
+					n_[2] = s_[0] + kv[1] * (older(1, s_[1]) + newer(1, n_[1]));
+					n_[3] = s_[1] + kv[2] * (older(2, s_[2]) + newer(2, n_[2]));
+					const f2 s2n = s_[2] + kv[3] * (older(3, s_[3]) + newer(3, n_[3]));
+					const f2 l2 = s2n * ze, h2 = n_[3] * zo;
+#pragma unroll
+					for (int i = 0; i < K; i++) {
+						st1[i][v] = n_[i][0];
+						st1[i][v + 2] = n_[i][1];
+					}
+					lo1[v] = l2[0];
+					lo1[v + 2] = l2[1];
+					hi1[v] = h2[0];
+					hi1[v + 2] = h2[1];
+				}
+				const int k1 = q1 - K / 2;
+				if (k1 >= (A >> 1) && k1 < (B >> 1) && own1) {
+					// level 1's Mallat rows in the LL quadrant of level 0: [LL | HL] at row k1, [LH | HH] at row H1 / 2 + k1
+					const int W2 = W1 >> 1, H2 = H1 >> 1;
+					const unsigned cb = (unsigned)((c0 >> 2) + lane * 2) * 4, nb = (unsigned)W2 * 4;
+					const T *top = out_h + (long)k1 * a.h_pitch, *bot = out_h + (long)(H2 + k1) * a.h_pitch;
+					store8_row<kNtStoreLL>(row_rsrc(out_ll + (long)k1 * a.ll_pitch, nb), cb, u2{to_bits(lo1[0]), to_bits(lo1[2])});
+					store8_row<kNtStore>(row_rsrc(top + W2, nb), cb, u2{to_bits(lo1[1]), to_bits(lo1[3])});
+					store8_row<kNtStore>(row_rsrc(bot, nb), cb, u2{to_bits(hi1[0]), to_bits(hi1[2])});
+					store8_row<kNtStore>(row_rsrc(bot + W2, nb), cb, u2{to_bits(hi1[1]), to_bits(hi1[3])});
+				}
+			}
+		} else
 		if (it >= K) {
 			// Mallat rows: [LL (Wd) | HL (W/2)] at row k, [LH | HH] at row Hd + k; each quarter row is a
 			// buffer of its own, so the lanes (and dwords) beyond its end are dropped
@@ -703,6 +836,13 @@ template <class W, int CPT, int RING, int NT, bool IL = false>
 __global__ __launch_bounds__(256) void k_fwd_sweep(FwdLevelArgs a, SweepGeom g)
 {
 	fwd_sweep_any_tile<W, CPT, RING, NT, IL, false>(a, g);
+}
+
+// levels 0 and 1 of a float 9/7 transform in one sweep over overlapped tiles (fwd_sweep_tile, F01)
+template <int NT>
+__global__ __launch_bounds__(256) void k_fwd_sweep01(FwdLevelArgs a, SweepGeom g)
+{
+	fwd_sweep_tile<SelEnds<Cdf97S>, 8, 16, NT, false, false, true>(a, g);
 }
 
 // a level with a rectangle copy riding along: the workgroups behind the tiles' copy blocks of `r` (FwdLevelArgs::ride)
@@ -857,6 +997,57 @@ static hipError_t fwd_level_t(const FwdLevelArgs &a, const SweepTuning &t, hipSt
 	if (tt.nt_auto && (tt.nt & 12) == 4 && (size_t)a.batch * ((a.W + 1) / 2) * ((a.H + 1) / 2) * sizeof(typename W::T) >= ((size_t)1 << 30))
 		tt.nt = 3;
 	return cpt == 8 ? fwd_pick<W, 8>(a, g, grid, waves, tt, s) : fwd_pick<W, 4>(a, g, grid, waves, tt, s);
+}
+
+// ---- the fused pair of levels 0 and 1 --------------------------------------------
+bool fwd01_can(Wavelet w, int W, int H)
+{
+	// (both levels of 64 x 64 or more: the select form of the line ends; the build with reflected ends has none)
+	return Cdf97S::kEndForms && w == kCdf97S && W % 4 == 0 && H % 4 == 0 && W >= 128 && H >= 128;
+}
+
+int fwd01_tiles(int W)
+{
+	// tile t reaches LL column 240 t + 255: the first tile that holds the last LL column is the last one
+	const int W1 = W >> 1;
+	return W1 <= 256 ? 1 : (W1 - 256 + 239) / 240 + 1;
+}
+
+hipError_t launch_fwd01(const FwdLevelArgs &a, const SweepTuning &t, hipStream_t s)
+{
+	if (!fwd01_can(kCdf97S, a.W, a.H) || a.batch < 1 || a.interleaved || a.ride || a.pair_hi > 0 || (t.tile_pairs & 1))
+		return hipErrorInvalidValue;
+	const int waves = t.waves >= 1 && t.waves <= 4 ? t.waves : 4;
+	const int Hd = a.H >> 1;
+	SweepGeom g;
+	g.ntx = fwd01_tiles(a.W);
+	g.swz = t.xcd_swizzle;
+	g.wave_horiz = 1;
+	g.tile_pairs = t.tile_pairs;
+	if (g.tile_pairs <= 0) {
+		// 7 iterations of a tile are level 1's warm-up: tall tiles, unless that leaves too few of them
+		g.tile_pairs = 64;
+		while (g.tile_pairs > 16 && (long)g.ntx * ((Hd + g.tile_pairs - 1) / g.tile_pairs) * a.batch < 1024)
+			g.tile_pairs >>= 1;
+	}
+	const long tiles = (long)g.ntx * ((Hd + g.tile_pairs - 1) / g.tile_pairs);
+	const dim3 grid((unsigned)((tiles + waves - 1) / waves), a.batch);
+	const size_t lds = (size_t)waves * 16 * (64 * 8 + 8) * 4;
+	// Cache policy as fwd_pick reads `nt`: loads and detail stores non-temporal whatever its bits 0 and 1 say; bit 2 keeps
+	// the LL band's stores -- here level 1's -- temporal while the launch's bands fit the Infinity Cache (as fwd_level_t
+	// decides it).  Bit 3, a ring of 8 rows and 4 columns per lane have no fused kernel: pair01_ok keeps such settings
+	// level by level; `ring` 16 is what this kernel is.
+	const bool ll_nt = !(t.nt & 4) || (t.nt_auto && (size_t)a.batch * (a.W >> 2) * (a.H >> 2) * sizeof(float) >= ((size_t)1 << 30));
+	if (ll_nt) {
+		if (hipError_t e = allow_lds((const void *)k_fwd_sweep01<3>, lds))
+			return e;
+		k_fwd_sweep01<3><<<grid, 64 * waves, lds, s>>>(a, g);
+	} else {
+		if (hipError_t e = allow_lds((const void *)k_fwd_sweep01<7>, lds))
+			return e;
+		k_fwd_sweep01<7><<<grid, 64 * waves, lds, s>>>(a, g);
+	}
+	return hipGetLastError();
 }
 
 // whether launch_fwd_level / launch_inv_level would take a kernel that can carry a copy along for this level

@@ -124,6 +124,16 @@ int tuned_tile_pairs(Wavelet w, const FwdLevelArgs &a)
 		[&](const SweepTuning &t) { return launch_fwd_level(wk, a, t, g.stream); });
 }
 
+// the fused pair of levels 0 and 1 (launch_fwd01; a key of its own): 7 iterations of every tile are level 1's warm-up,
+// so 128 pairs join the candidates; idempotent like a single level -- it reads the image and writes elsewhere
+int tuned_tile_pairs01(Wavelet w, const FwdLevelArgs &a)
+{
+	if (!tunable(a.W, a.H, a.batch, a.interleaved))
+		return 0;
+	return tune_tile_pairs(tile_key(w, false, a.W, a.H, a.batch) ^ (1ull << 63), false, {{64, 0, 0}, {128, 0, 0}, {32, 0, 0}},
+		[&](const SweepTuning &t) { return launch_fwd01(a, t, g.stream); });
+}
+
 // the inverse levels alike (32 images of 8192^2: 16 pairs 520 against 507-510 Gsamples/s with the rule's 32)
 int tuned_tile_pairs(Wavelet w, const InvLevelArgs &a)
 {
