@@ -3,8 +3,8 @@
 // :17932) and 9/7 (dwt_eaw97_2f_s / _2i_s, src/eaw-experimental.c:300, 398, Mallat only).  The two wavelets' drivers are
 // the same loop over different line functions, so one set of functions here takes the wavelet in its frame.
 //
-// A dense Mallat frame in HBM runs one launch of the wavelet's forward / inverse tile kernel per level (dwt_eaw.hip,
-// dwt_eaw97.hip), for a whole batch at once: the level reads a copy of the image (forward level 0, every inverse
+// A dense Mallat frame in HBM runs one launch of the wavelet's forward / inverse tile kernel per level (dwt_eaw.hip),
+// for a whole batch at once: the level reads a copy of the image (forward level 0, every inverse
 // level's detail bands) or the LL ping-pong, so no tile reads what another one writes.  Levels whose LL side has shrunk
 // to 1 (decompose_one), sparse frames, the interleaved layout and option "eaw_two_pass" run the reference's loop: per
 // level an exact row pass and an exact column pass (each one line kernel into a dense scratch and one placing kernel),
@@ -17,8 +17,6 @@
 namespace dwtb {
 
 namespace {
-
-enum EawWavelet { kEaw53, kEaw97 };
 
 struct EawFrame {
 	EawWavelet wavelet;
@@ -67,9 +65,7 @@ int line_pass(EawWavelet wv, bool inverse, char *base, long ls, long es, int n_l
 		return 1;
 	float *tmp = (float *)g.frame_b.p;
 	const bool lanes_along_lines = ls < es; // columns of a row-major image
-	const hipError_t e = wv == kEaw97 ? launch_eaw97_line(inverse, base, ls, es, n_lines, N, hoff, tmp, w, lanes_along_lines, alpha, g.stream)
-	                                  : launch_eaw_line(inverse, base, ls, es, n_lines, N, hoff, tmp, w, lanes_along_lines, alpha, g.stream);
-	return launched(e, "EAW", "line pass") ||
+	return launched(launch_eaw_line(wv, inverse, base, ls, es, n_lines, N, hoff, tmp, w, lanes_along_lines, alpha, g.stream), "EAW", "line pass") ||
 	       launched(launch_eaw_place(base, ls, es, n_lines, N, inverse ? -1 : hoff, tmp, lanes_along_lines, g.stream), "EAW", "line pass");
 }
 
@@ -127,19 +123,23 @@ int fused_levels(const EawFrame &f)
 
 int level_launch(EawWavelet wv, bool inverse, const EawLevelArgs &a, float alpha)
 {
-	return launched(wv == kEaw97 ? launch_eaw97_level(inverse, a, alpha, g.stream) : launch_eaw_level(inverse, a, alpha, g.stream), "EAW", "level");
+	return launched(launch_eaw_level(wv, inverse, a, alpha, g.stream), "EAW", "level");
 }
 
-// scratch of the fused levels: the image copy (frame_b) and the LL ping-pong, for `batch` images
-int fused_scratch(const EawFrame &f, int batch, float **copy, float **ll)
+// scratch of the fused levels for the `batch` images at d.p + b*bs: a dense copy of them (frame_b), made here, and the
+// LL ping-pong
+int fused_scratch(const EawFrame &f, Img d, int batch, long bs, float **copy, float **ll)
 {
 	const Geom &ge = f.ge;
-	const size_t img = (size_t)ge.sox * ge.soy * 4 * batch, llb = (size_t)ge.Wo(1) * ge.Ho(1) * 4 * batch;
+	const int W = ge.sox, H = ge.soy;
+	const size_t img = (size_t)W * H * 4 * batch, llb = (size_t)ge.Wo(1) * ge.Ho(1) * 4 * batch;
 	if (grow(g.frame_b, img) || grow(g.eaw_ll[0], llb) || grow(g.eaw_ll[1], llb))
 		return 1;
 	*copy = (float *)g.frame_b.p;
 	ll[0] = (float *)g.eaw_ll[0].p;
 	ll[1] = (float *)g.eaw_ll[1].p;
+	for (int b = 0; b < batch; b++)
+		HIP_TRY(hipMemcpy2DAsync(*copy + (long)b * W * H, (size_t)W * 4, d.p + b * bs, d.sx, (size_t)W * 4, H, hipMemcpyDeviceToDevice, g.stream));
 	return 0;
 }
 
@@ -155,15 +155,14 @@ int run_device(bool inverse, const EawFrame &f, Img d, int batch, long bs, float
 				return 1;
 		return 0;
 	};
+	// the fused levels: the image copy C (pitch W) and the LL ping-pong (pitch pll), images bll floats apart
+	float *C = nullptr, *LL[2] = {nullptr, nullptr};
+	const int W = ge.sox, H = ge.soy;
+	const long pll = ge.Wo(1), bll = (long)ge.Wo(1) * ge.Ho(1);
 	if (!inverse) {
 		if (nf > 0) {
-			float *C, *LL[2];
-			if (fused_scratch(f, batch, &C, LL))
+			if (fused_scratch(f, d, batch, bs, &C, LL))
 				return 1;
-			const int W = ge.sox, H = ge.soy;
-			for (int b = 0; b < batch; b++)
-				HIP_TRY(hipMemcpy2DAsync(C + (long)b * W * H, (size_t)W * 4, d.p + b * bs, d.sx, (size_t)W * 4, H, hipMemcpyDeviceToDevice, g.stream));
-			const long pll = ge.Wo(1), bll = (long)ge.Wo(1) * ge.Ho(1);
 			for (int j = 0; j < nf; j++) {
 				EawLevelArgs a;
 				a.W = ge.Wo(j);
@@ -200,13 +199,8 @@ int run_device(bool inverse, const EawFrame &f, Img d, int batch, long bs, float
 		if (two_pass(j))
 			return 1;
 	if (nf > 0) {
-		float *C, *LL[2];
-		if (fused_scratch(f, batch, &C, LL))
+		if (fused_scratch(f, d, batch, bs, &C, LL))
 			return 1;
-		const int W = ge.sox, H = ge.soy;
-		for (int b = 0; b < batch; b++)
-			HIP_TRY(hipMemcpy2DAsync(C + (long)b * W * H, (size_t)W * 4, d.p + b * bs, d.sx, (size_t)W * 4, H, hipMemcpyDeviceToDevice, g.stream));
-		const long pll = ge.Wo(1), bll = (long)ge.Wo(1) * ge.Ho(1);
 		for (int j = nf; j >= 1; j--) {
 			EawLevelArgs a;
 			a.W = ge.Wo(j - 1);

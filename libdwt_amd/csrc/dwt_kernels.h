@@ -149,13 +149,14 @@ constexpr int N1D_MAX = 8192; // LDS: 56 KiB per line of an inverse at this leng
 hipError_t launch_line_levels(Wavelet w, bool inverse, const void *src, void *dst, long line_stride, long elem_stride,
 	int n_lines, int N, int levels, hipStream_t s);
 
-// Edge-avoiding 5/3 (dwt_eaw.hip).  One exact pass over n_lines lines (line l at src + l*ls, elements es bytes apart, a
-// multiple of 4) into the dense scratch tmp (n_lines x N floats, sample order); weights w[l*N + i] written (forward) or
-// read (inverse).  hoff: where the line's H half starts (Mallat), or -1 (interleaved: sample i at i).  The inverse reads
-// its input at those places; launch_eaw_place then moves tmp to its places in the lines (forward: Mallat / interleaved
-// places, inverse: hoff = -1).
-hipError_t launch_eaw_line(bool inverse, const void *src, long ls, long es, int n_lines, int N, int hoff, float *tmp, float *w,
-	bool lanes_along_lines, float alpha, hipStream_t s);
+// Edge-avoiding 5/3 and 9/7 (dwt_eaw.hip).  One exact pass over n_lines lines (line l at src + l*ls, elements es bytes
+// apart, a multiple of 4) into the dense scratch tmp (n_lines x N floats, sample order); weights w[l*N + i] written
+// (forward) or read (inverse).  hoff: where the line's H half starts (Mallat), or -1 (interleaved: sample i at i).  The
+// inverse reads its input at those places; launch_eaw_place then moves tmp to its places in the lines (forward: Mallat /
+// interleaved places, inverse: hoff = -1).
+enum EawWavelet { kEaw53, kEaw97 };
+hipError_t launch_eaw_line(EawWavelet wv, bool inverse, const void *src, long ls, long es, int n_lines, int N, int hoff, float *tmp,
+	float *w, bool lanes_along_lines, float alpha, hipStream_t s);
 hipError_t launch_eaw_place(void *dst, long ls, long es, int n_lines, int N, int hoff, const float *tmp, bool lanes_along_lines, hipStream_t s);
 // One fused level of a dense Mallat frame (W, H >= 2), `batch` images bi_* floats apart; pitches in floats.
 // Forward: in -> LL to ll_out, the detail subbands to det_out at their Mallat places, weights to wH_out (H x W) /
@@ -169,12 +170,7 @@ struct EawLevelArgs {
 	long bi_in = 0, bi_ll = 0, bi_det = 0, bi_w = 0, bi_out = 0;
 	int W = 0, H = 0, batch = 1;
 };
-hipError_t launch_eaw_level(bool inverse, const EawLevelArgs &a, float alpha, hipStream_t s);
-// Edge-avoiding 9/7 (dwt_eaw97.hip): the same two routes with the same arguments (hoff as above); the line pass's
-// result is placed by launch_eaw_place.
-hipError_t launch_eaw97_line(bool inverse, const void *src, long ls, long es, int n_lines, int N, int hoff, float *tmp, float *w,
-	bool lanes_along_lines, float alpha, hipStream_t s);
-hipError_t launch_eaw97_level(bool inverse, const EawLevelArgs &a, float alpha, hipStream_t s);
+hipError_t launch_eaw_level(EawWavelet wv, bool inverse, const EawLevelArgs &a, float alpha, hipStream_t s);
 
 // z-pass knobs of the 3-D path (measured defaults; options vol_cpt / vol_tile_pairs / vol_nt)
 struct VolTuning {

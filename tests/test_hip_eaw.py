@@ -103,6 +103,30 @@ def test_device_bit_exact(dwt, ref, shape, interleaved):
     assert same_floats(d.get(), expect_inv(ref, want, wHw, wVw, interleaved, j_max=jw))
 
 
+SEAM_SIDES = [63, 64, 65, 66, 127, 129]
+
+
+@pytest.mark.parametrize("w", SEAM_SIDES)
+@pytest.mark.parametrize("h", SEAM_SIDES)
+def test_tile_seam_bit_exact(dwt, ref, h, w):
+    """The last column and row on every place relative to the end of a 64-wide tile and its halo (2 samples before, 1
+    after; the inverse 1 and 2), at level 0 and, with 32 .. 65 samples, at level 1: the fused tiles and the line route."""
+    img = np.random.default_rng(h * 131 + w).random((h, w), dtype=np.float32)
+    want, jw, wHw, wVw = expect_fwd(ref, img, j_max=2)
+    back = expect_inv(ref, want, wHw, wVw, j_max=jw)
+    for two_pass in (0, 1):
+        dwt.set_option("eaw_two_pass", two_pass)
+        try:
+            d = to_device(img)
+            jg, wH, wV = dwt.dwt_eaw53_2f_s(d.ptr, w * 4, 4, w, h, w, h, 2, 0, 0)
+            assert jg == jw and same_floats(d.get(), want), two_pass
+            assert weights_ok(wH, wHw) and weights_ok(wV, wVw), two_pass
+            dwt.dwt_eaw53_2i_s(d.ptr, w * 4, 4, w, h, w, h, jg, 0, 0, wH, wV)
+            assert same_floats(d.get(), back), two_pass
+        finally:
+            dwt.set_option("eaw_two_pass", 0)
+
+
 @pytest.mark.parametrize("where", ["host", "device"])
 @pytest.mark.parametrize("interleaved", [False, True], ids=["mallat", "interleaved"])
 def test_prime_pitch(dwt, ref, where, interleaved):

@@ -106,6 +106,30 @@ def test_device_bit_exact(dwt, shape):
     assert same_floats(d.get(), expect_inv(want, wHw, wVw, j_max=jw))
 
 
+SEAM_SIDES = [63, 64, 65, 66, 127, 129]
+
+
+@pytest.mark.parametrize("w", SEAM_SIDES)
+@pytest.mark.parametrize("h", SEAM_SIDES)
+def test_tile_seam_bit_exact(dwt, h, w):
+    """The last column and row on every place relative to the end of a 64-wide tile and its halo (4 samples before, 3
+    after; the inverse 3 and 4), at level 0 and, with 32 .. 65 samples, at level 1: the fused tiles and the line route."""
+    img = np.random.default_rng(h * 131 + w).random((h, w), dtype=np.float32)
+    want, jw, wHw, wVw = expect_fwd(img, j_max=2)
+    back = expect_inv(want, wHw, wVw, j_max=jw)
+    for two_pass in (0, 1):
+        dwt.set_option("eaw_two_pass", two_pass)
+        try:
+            d = to_device(img)
+            jg, wH, wV = dwt.dwt_eaw97_2f_s(d.ptr, w * 4, 4, w, h, w, h, 2, 0, 0)
+            assert jg == jw and same_floats(d.get(), want), two_pass
+            assert weights_ok(wH, wHw) and weights_ok(wV, wVw), two_pass
+            dwt.dwt_eaw97_2i_s(d.ptr, w * 4, 4, w, h, w, h, jg, 0, 0, wH, wV)
+            assert same_floats(d.get(), back), two_pass
+        finally:
+            dwt.set_option("eaw_two_pass", 0)
+
+
 @pytest.mark.parametrize("where", ["host", "device"])
 def test_prime_pitch(dwt, where):
     """Rows 2053 bytes apart: every float is unaligned in all rows but one in four."""
