@@ -25,6 +25,10 @@
 //     Image borders use whole-sample symmetric reflection applied to the SOURCE
 //     address of the DMA, so the arithmetic needs no edge cases.
 //
+// What this sweep shares with the inverse and the double-precision ones -- a wave's tile, the streaming vertical pass,
+// the launch grid -- lives in dwt_sweep2d.h; loaders, LDS reads, stores and the fused pair of levels are this file's own,
+// and so are its line-end state and row-end test (the double sweeps take theirs from the header: fwd_sweep_tile says why).
+//
 // Arithmetic order follows the reference exactly (rows before columns, etc.) and
 // this file is compiled with -ffp-contract=off, so float results are bit-identical
 // to libdwt's CPU path; int results are exact.
@@ -134,57 +138,6 @@ hipError_t launch_line_pass(Wavelet w, bool inverse, const void *src, void *dst,
 // X (interleaved layout, phase-ordered wavelets): the tiles leave out the samples whose rounding depends on the
 // reference's phase order -- rows 0..7 and the last 8 columns of the level -- for the strip workgroups of the
 // same launch (dwt_il_strip.h).
-// The vertical pass of one iteration (no row of it a column end) on two adjacent columns at once, as the halves of packed
-// operations: the same steps and rounding as W::fwd_step / fwd_scale (float policies with fk: c + k (l + r)).
-// row[0] / row[1]: the odd / even row of the iteration; st: the streaming state; lo / hi: the scaled outputs.
-// SEL: the select form of the line ends -- ve[s]: step s acts on a row that is a column's end (wave-uniform), kv[s] its
-// coefficient (doubled there); the state tap gives way to -0.0 (dwt_lift.h, SelEnds).
-// (K = 2 and 4; a policy of one step takes the scalar form of the sweep)
-template <class W, int CPT, bool SEL = false, class T>
-static __device__ __forceinline__ void vertical_pairs(const T (&row)[2][CPT], T (&st)[W::K][CPT], T (&lo)[CPT], T (&hi)[CPT],
-	const bool *ve = nullptr, const T *kv = nullptr)
-{
-	typedef float f2 __attribute__((ext_vector_type(2)));
-	constexpr int K = W::K;
-	[[maybe_unused]] const f2 nz = f2{-0.0f, -0.0f};
-	auto kk = [&](int s) { return SEL ? kv[s] : W::fk(s); };
-	auto tap = [&](int s, f2 v) { return (SEL && ve[s]) ? nz : v; };
-	const float zl = W::fwd_scale(0, 1.0f), zh = W::fwd_scale(1, 1.0f); // (the scale factors themselves)
-#pragma unroll
-	for (int v = 0; v < CPT; v++) {
-		if (v & 2)
-			continue; // (columns v and v + 2: the stores take lo[0], lo[2], lo[4], lo[6] / lo[1], lo[3], ... as consecutive registers)
-		constexpr int P = 2;
-		const f2 ov = f2{row[0][v], row[0][v + P]}, ev = f2{row[1][v], row[1][v + P]};
-		f2 s_[K], n_[K], lo2, hi2;
-#pragma unroll
-		for (int i = 0; i < K; i++)
-			s_[i] = f2{st[i][v], st[i][v + P]};
-		n_[0] = ev;
-		n_[1] = ov + kk(0) * (tap(0, s_[0]) + ev); // d1n
-		if constexpr (K == 4) {
-			n_[2] = s_[0] + kk(1) * (tap(1, s_[1]) + n_[1]); // s1n
-			n_[3] = s_[1] + kk(2) * (tap(2, s_[2]) + n_[2]); // d2n
-			const f2 s2n = s_[2] + kk(3) * (tap(3, s_[3]) + n_[3]);
-			lo2 = s2n * zl;
-			hi2 = n_[3] * zh;
-		} else {
-			const f2 s1n = s_[0] + kk(1) * (tap(1, s_[1]) + n_[1]);
-			lo2 = s1n * zl;
-			hi2 = n_[1] * zh;
-		}
-#pragma unroll
-		for (int i = 0; i < K; i++) {
-			st[i][v] = n_[i][0];
-			st[i][v + P] = n_[i][1];
-		}
-		lo[v] = lo2[0];
-		lo[v + P] = lo2[1];
-		hi[v] = hi2[0];
-		hi[v + P] = hi2[1];
-	}
-}
-
 // F01 (float 9/7 by selection, 8 columns per lane, Mallat): levels 0 AND 1 in this one sweep.  The tiles keep their 512
 // columns but start 480 apart (15 lines of 128 bytes: every row load stays line-aligned), so that each seam of level 1 is
 // computed twice, inside a wave, and nothing passes between waves:
@@ -229,33 +182,16 @@ static __device__ __forceinline__ void fwd_sweep_tile(const FwdLevelArgs &a, con
 	constexpr bool kPairRows = kIsSelEnds<W> && std::is_same<T, float>::value && has_coef_ends<W>::value && !std::is_base_of<Cdf97SFma, W>::value;
 	extern __shared__ __attribute__((aligned(16))) char smem[];
 
-	const int lane = threadIdx.x & 63, nwv = blockDim.x >> 6;
-	// wave-uniform on purpose: tile geometry, row indices and row pointers then live in SGPRs
-	const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-	const int bid = tile_block_id(g.swz, X ? g.first : 0, g.tile_blocks);
-	int tx, ty;
-	if constexpr (F01) {
-		// (consecutive waves take consecutive tiles across the rows' ends: a row of 17 tiles leaves no wave of a workgroup idle)
-		const int t = bid * nwv + wv;
-		tx = t % g.ntx;
-		ty = t / g.ntx;
-	} else
-	if (g.wave_horiz) {
-		const int ntxb = (g.ntx + nwv - 1) / nwv;
-		tx = (bid % ntxb) * nwv + wv;
-		ty = bid / ntxb;
-	} else {
-		tx = bid % g.ntx;
-		ty = (bid / g.ntx) * nwv + wv;
-	}
+	const int lane = threadIdx.x & 63;
+	const SweepTile tile = sweep_tile<F01>(a, g, X ? g.first : 0, g.tile_blocks);
+	if (!tile.live)
+		return;
+	if (a.pair_hi > 0 && (tile.A < a.pair_lo || tile.A >= a.pair_hi))
+		return; // this launch computes a band of the level only
+	const int wv = tile.wv, tx = tile.tx, A = tile.A, B = tile.B;
+	[[maybe_unused]] const int ty = tile.ty;
 	const int img = blockIdx.y;
 	const int Wd = (a.W + 1) >> 1, Hd = (a.H + 1) >> 1;
-	const int A = ty * g.tile_pairs;
-	if (A >= Hd || tx >= g.ntx)
-		return; // whole wave leaves; no barriers are used anywhere
-	if (a.pair_hi > 0 && (A < a.pair_lo || A >= a.pair_hi))
-		return; // this launch computes a band of the level only
-	const int B = min(A + g.tile_pairs, Hd);
 	const int c0 = tx * (F01 ? TW - 32 : TW);
 	const int warm = (F01 && A > 0) ? K : 0; // level 1's warm-up above the tile
 	const int n_iter = (B - A) + K + warm + (F01 ? 3 : 0);
@@ -356,6 +292,8 @@ static __device__ __forceinline__ void fwd_sweep_tile(const FwdLevelArgs &a, con
 		for (int v = 0; v < CPT; v++)
 			st[s][v] = 0;
 
+	// (the line-end state and its dispatch below are RowEnds of dwt_sweep2d.h written out: through the struct most of this
+	// file's kernels compile to other instruction counts, and the headline's kernels stay as they were measured)
 	// explicit line-end forms: which of the lane's columns c - K .. c + CPT + K - 1 are a row's ends -- only the tiles
 	// that hold column 0 or W - 1 have any (`h_any`, wave-uniform: the interior tiles run the plain lift) --; the rows that
 	// are a column's ends are found per iteration (wave-uniform as well)
@@ -394,6 +332,7 @@ static __device__ __forceinline__ void fwd_sweep_tile(const FwdLevelArgs &a, con
 		own0 = last_tile || lane < 60;
 		own1 = (tx == 0 || lane >= 1) && (last_tile || lane <= 60);
 	}
+	// (row_end_test of dwt_sweep2d.h written out, for the same reason)
 	// row r (any r the sweep meets) is an end of its column: r == 0 or r == H - 1 after reflection (one bounce when tall)
 	[[maybe_unused]] auto row_is_end = [&](int r) {
 		if (tall || kIsSelEnds<W>) // (SelEnds runs on levels of 64 rows or more)
@@ -534,50 +473,22 @@ static __device__ __forceinline__ void fwd_sweep_tile(const FwdLevelArgs &a, con
 			}
 		}
 		T lo[CPT], hi[CPT];
-		// `ENDS`: the iteration meets a column end -- the steps on that row take the end form
-		auto vertical = [&](auto ends_tag) {
-			constexpr bool ENDS = decltype(ends_tag)::value;
-			if constexpr (kPairRows && !ENDS && K != 1) { // (one step: the scalar form below keeps the state in registers)
+		// (fwd_vertical; the policies whose rows are lifted in pairs take two columns at once too -- but for a policy of one
+		// step: the scalar form keeps the state in registers)
+		auto vertical = [&](auto mode) {
+			if constexpr (kPairRows && K != 1) {
+				static_assert(decltype(mode)::value == kColNone, "the paired pass has no explicit end forms");
 				vertical_pairs<W, CPT>(row, st, lo, hi);
-				return;
-			}
-#pragma unroll
-			for (int v = 0; v < CPT; v++) {
-				const T ov = row[0][v], ev = row[1][v];
-				if constexpr (K == 1) {
-					// predict only (st[0]: the even row 2q-2, which leaves as it is)
-					const T d1n = fwd_step_at<W>(0, ENDS && vend[0], ov, st[0][v], ev);
-					lo[v] = W::fwd_scale(0, st[0][v]);
-					hi[v] = W::fwd_scale(1, d1n);
-					st[0][v] = ev;
-				} else if constexpr (K == 4) {
-					const T d1n = fwd_step_at<W>(0, ENDS && vend[0], ov, st[0][v], ev);
-					const T s1n = fwd_step_at<W>(1, ENDS && vend[1], st[0][v], st[1][v], d1n);
-					const T d2n = fwd_step_at<W>(2, ENDS && vend[2], st[1][v], st[2][v], s1n);
-					const T s2n = fwd_step_at<W>(3, ENDS && vend[3], st[2][v], st[3][v], d2n);
-					lo[v] = W::fwd_scale(0, s2n);
-					hi[v] = W::fwd_scale(1, d2n);
-					st[0][v] = ev;
-					st[1][v] = d1n;
-					st[2][v] = s1n;
-					st[3][v] = d2n;
-				} else {
-					const T d1n = fwd_step_at<W>(0, ENDS && vend[0], ov, st[0][v], ev);
-					const T s1n = fwd_step_at<W>(1, ENDS && vend[1], st[0][v], st[1][v], d1n);
-					lo[v] = W::fwd_scale(0, s1n);
-					hi[v] = W::fwd_scale(1, d1n);
-					st[0][v] = ev;
-					st[1][v] = d1n;
-				}
-			}
+			} else
+				fwd_vertical<W, decltype(mode)::value>(row, st, lo, hi, vend);
 		};
 		if constexpr (W::kEndForms) {
 			if (__builtin_expect(v_any, 0)) {
 				DWT_END_PATH();
-				vertical(std::true_type{});
+				vertical(ColTag<kColEnds>{});
 			}
 			else
-				vertical(std::false_type{});
+				vertical(ColTag<kColNone>{});
 		} else if constexpr (kIsSelEnds<W>) {
 			// step s acts on row 2q-1-s; where that row is an end of its column (wave-uniform, the top and bottom tiles'
 			// first / last iterations) the step's coefficient is doubled and its state tap -- the same values as the other
@@ -593,38 +504,10 @@ static __device__ __forceinline__ void fwd_sweep_tile(const FwdLevelArgs &a, con
 #pragma unroll
 				for (int s_ = 0; s_ < K; s_++)
 					kv[s_] = sel_coef<W, false>(s_, ve[s_]);
-				if constexpr (kPairRows && K != 1) {
+				if constexpr (kPairRows && K != 1)
 					vertical_pairs<W, CPT, true>(row, st, lo, hi, ve, kv);
-					return;
-				}
-#pragma unroll
-				for (int v = 0; v < CPT; v++) {
-					const T ov = row[0][v], ev = row[1][v];
-					if constexpr (K == 1) {
-						const T d1n = sel_step<W, false>(0, ve[0], kv[0], ov, st[0][v], ev);
-						lo[v] = W::fwd_scale(0, st[0][v]);
-						hi[v] = W::fwd_scale(1, d1n);
-						st[0][v] = ev;
-					} else if constexpr (K == 4) {
-						const T d1n = sel_step<W, false>(0, ve[0], kv[0], ov, st[0][v], ev);
-						const T s1n = sel_step<W, false>(1, ve[1], kv[1], st[0][v], st[1][v], d1n);
-						const T d2n = sel_step<W, false>(2, ve[2], kv[2], st[1][v], st[2][v], s1n);
-						const T s2n = sel_step<W, false>(3, ve[3], kv[3], st[2][v], st[3][v], d2n);
-						lo[v] = W::fwd_scale(0, s2n);
-						hi[v] = W::fwd_scale(1, d2n);
-						st[0][v] = ev;
-						st[1][v] = d1n;
-						st[2][v] = s1n;
-						st[3][v] = d2n;
-					} else {
-						const T d1n = sel_step<W, false>(0, ve[0], kv[0], ov, st[0][v], ev);
-						const T s1n = sel_step<W, false>(1, ve[1], kv[1], st[0][v], st[1][v], d1n);
-						lo[v] = W::fwd_scale(0, s1n);
-						hi[v] = W::fwd_scale(1, d1n);
-						st[0][v] = ev;
-						st[1][v] = d1n;
-					}
-				}
+				else
+					fwd_vertical<W, kColSel>(row, st, lo, hi, ve, kv);
 			};
 			// (shallow ring: the launches of a few rounds of waves, bound by the longest wave -- the top tiles', for whom a
 			// second body means instructions fetched cold from HBM, 1 us a launch; there every iteration selects)
@@ -634,9 +517,9 @@ static __device__ __forceinline__ void fwd_sweep_tile(const FwdLevelArgs &a, con
 				DWT_END_PATH();
 				vertical_sel();
 			} else
-				vertical(std::false_type{});
+				vertical(ColTag<kColNone>{});
 		} else {
-			vertical(std::false_type{});
+			vertical(ColTag<kColNone>{});
 		}
 
 		if constexpr (IL) {
@@ -943,7 +826,7 @@ static hipError_t fwd_level_t(const FwdLevelArgs &a, const SweepTuning &t, hipSt
 	g.swz = t.xcd_swizzle;
 	g.wave_horiz = 0;
 	const int Hd = (a.H + 1) / 2;
-	const int waves = t.waves >= 1 && t.waves <= 4 ? t.waves : 4;
+	const int waves = sweep_waves(t);
 	const int nty = (Hd + g.tile_pairs - 1) / g.tile_pairs;
 	// Ring depth (measured, scripts/sweep.py): when a launch has several rounds of tiles
 	// per CU, 4 waves/CU with a 16-row ring (7 iterations of DMA in flight per wave) and
@@ -956,11 +839,7 @@ static hipError_t fwd_level_t(const FwdLevelArgs &a, const SweepTuning &t, hipSt
 		tt.ring = (g.ntx >= waves && (long)g.ntx * nty * a.batch >= ((a.interleaved && a.batch == 1) ? 512 : 3072)) ? 16 : 8;
 	// deep ring: the waves of a workgroup take side-by-side tiles (+ 7 %); shallow: stacked tiles
 	g.wave_horiz = tt.ring == 16;
-	dim3 grid;
-	if (g.wave_horiz)
-		grid = dim3(((g.ntx + waves - 1) / waves) * nty, a.batch);
-	else
-		grid = dim3(g.ntx * ((nty + waves - 1) / waves), a.batch);
+	const dim3 grid = sweep_grid(g, nty, waves, a.batch);
 	if (a.sh.rows && (!a.interleaved || a.batch != 1 || a.out_step != 1 || g.tile_pairs != a.sh.tile_pairs))
 		return hipErrorInvalidValue; // the snapshot of an in-place level was taken for other tiles
 	if (a.ride && a.ride_hi > a.ride_lo && (a.interleaved || a.batch != 1 || waves != 4 || tt.ring != 8 || a.temporal || (tt.nt & 8)))
@@ -1017,7 +896,7 @@ hipError_t launch_fwd01(const FwdLevelArgs &a, const SweepTuning &t, hipStream_t
 {
 	if (!fwd01_can(kCdf97S, a.W, a.H) || a.batch < 1 || a.interleaved || a.ride || a.pair_hi > 0 || (t.tile_pairs & 1))
 		return hipErrorInvalidValue;
-	const int waves = t.waves >= 1 && t.waves <= 4 ? t.waves : 4;
+	const int waves = sweep_waves(t);
 	const int Hd = a.H >> 1;
 	SweepGeom g;
 	g.ntx = fwd01_tiles(a.W);

@@ -4,12 +4,13 @@
 // Same structure as k_fwd_sweep / k_inv_sweep -- one wave per tile marching down its rows, input
 // rows streamed HBM -> LDS by LDS-DMA into a wave-private ring, horizontal lift in registers,
 // vertical lift streaming with its state in registers, Mallat de-interleave in registers, 16 B
-// per lane stores -- with the byte layout of the float kernels kept: a lane owns 32 B of a row
+// per lane stores; tile origin, line-end state, vertical pass and grid are the shared pieces of
+// dwt_sweep2d.h -- with the byte layout of the float kernels kept: a lane owns 32 B of a row
 // (4 doubles where the float sweep has 8 floats; the inverse 16 B = 2 doubles for 4 floats), so
 // rows, DMA pieces and stores have the sizes those kernels were tuned for; only the halo is twice
 // as many bytes (4 samples = 32 B a side).  Arithmetic order as the reference (rows before
 // columns, unfused multiply-add in fp64): bit-identical coefficients.
-#include "dwt_device.h"
+#include "dwt_sweep2d.h"
 
 namespace dwt {
 
@@ -36,40 +37,25 @@ static __device__ __forceinline__ void lds_read6(unsigned a0, unsigned a1, unsig
 		: "memory");
 }
 
-struct SweepGeomD {
-	int tile_pairs, ntx, swz, wave_horiz;
-};
-
 } // namespace
 
 // ---- forward ---------------------------------------------------------------------------
 // LDS row slot (bytes): [main 2048 | left halo 32 | right halo 32]
 template <class W, int RING>
-static __device__ __forceinline__ void fwd_sweep_d_tile(const FwdLevelArgs &a, const SweepGeomD &g)
+static __device__ __forceinline__ void fwd_sweep_d_tile(const FwdLevelArgs &a, const SweepGeom &g)
 {
 	using T = double;
 	constexpr int K = W::K, CPT = 4, TW = 64 * CPT, RSB = TW * 8 + 64, NARR = CPT + 2 * K;
 	constexpr int kAhead = RING / 2 - 1, kDmaPerIter = 2 * 3;
 	extern __shared__ __attribute__((aligned(16))) char smem[];
 
-	const int lane = threadIdx.x & 63, nwv = blockDim.x >> 6;
-	const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-	const int bid = tile_block_id(g.swz);
-	int tx, ty;
-	if (g.wave_horiz) {
-		const int ntxb = (g.ntx + nwv - 1) / nwv;
-		tx = (bid % ntxb) * nwv + wv;
-		ty = bid / ntxb;
-	} else {
-		tx = bid % g.ntx;
-		ty = (bid / g.ntx) * nwv + wv;
-	}
+	const int lane = threadIdx.x & 63;
+	const SweepTile tile = sweep_tile(a, g);
+	if (!tile.live)
+		return;
+	const int wv = tile.wv, tx = tile.tx, A = tile.A, B = tile.B;
 	const int img = blockIdx.y;
 	const int Wd = (a.W + 1) >> 1, Hd = (a.H + 1) >> 1;
-	const int A = ty * g.tile_pairs;
-	if (A >= Hd || tx >= g.ntx)
-		return;
-	const int B = min(A + g.tile_pairs, Hd);
 	const int c0 = tx * TW;
 	const int n_iter = (B - A) + K;
 	const int q0 = A - K / 2;
@@ -94,30 +80,10 @@ static __device__ __forceinline__ void fwd_sweep_d_tile(const FwdLevelArgs &a, c
 
 	int islot = 0, rslot = 0;
 	const bool tall = kSel || a.H >= 64;
-	// line-end forms (dwt_lift.h; see k_fwd_sweep): the lane's columns c - K .. that are a row's ends, any in this tile,
-	// and the test for a row being a column's end
-	[[maybe_unused]] unsigned hends = 0;
-	[[maybe_unused]] bool h_any = false, h_simple = false;
-	constexpr unsigned kCand = (1u << K) | (1u << (K + CPT - 1)); // the two entries that meet a line end when W is a multiple of CPT
-	// (SelEnds) the same two entries by selection: the lane's flags and its coefficients for the steps that reach them
-	[[maybe_unused]] bool e0 = false, e1 = false;
-	[[maybe_unused]] T kh[K];
-	if constexpr (kSel) {
-		const unsigned m = end_mask_long<NARR>(c0 + lane * CPT - K, a.W);
-		e0 = (m >> K) & 1;
-		e1 = (m >> (K + CPT - 1)) & 1;
-		sel_coefs<W, false, K>(kh, e0, e1);
-	} else if constexpr (W::kEndForms) {
-		hends = end_mask<NARR>(c0 + lane * CPT - K, a.W);
-		h_any = __builtin_amdgcn_ballot_w64(hends != 0) != 0;
-		h_simple = __builtin_amdgcn_ballot_w64((hends & ~(kCand | 1u | (1u << (NARR - 1)))) != 0) == 0;
-	}
-	auto row_is_end = [&](int r) {
-		if (tall)
-			return r == 0 || r == a.H - 1;
-		const int rr = reflect(r, a.H);
-		return rr == 0 || rr == a.H - 1;
-	};
+	// the row ends among the lane's columns c - K .. c + CPT + K - 1
+	RowEnds<W, false, NARR, K, K + CPT - 1> he;
+	he.vote(he.init(c0 + lane * CPT - K, a.W), false);
+	const auto row_is_end = row_end_test(a, tall);
 	auto issue = [&](int it) {
 #pragma unroll
 		for (int rr = 0; rr < 2; rr++) {
@@ -185,17 +151,7 @@ static __device__ __forceinline__ void fwd_sweep_d_tile(const FwdLevelArgs &a, c
 			x[K + 1] = dbl(r[2][2], r[2][3]);
 			x[K + 2] = dbl(r[3][0], r[3][1]);
 			x[K + 3] = dbl(r[3][2], r[3][3]);
-			if constexpr (kSel) {
-				lift_regs_sel<W, NARR, false, K, K + CPT - 1>(x, e0, e1, kh);
-			} else if (__builtin_expect(!h_any, 1)) {
-				lift_fwd_regs<W, NARR>(x, 0u);
-			} else if (h_simple) {
-				DWT_END_PATH();
-				lift_fwd_regs<W, NARR, kCand>(x, hends);
-			} else {
-				DWT_END_PATH();
-				lift_fwd_regs<W, NARR>(x, hends);
-			}
+			he.lift(x);
 #pragma unroll
 			for (int v = 0; v < CPT; v++)
 				row[rr][v] = W::fwd_scale(v & 1, x[K + v]);
@@ -217,46 +173,11 @@ static __device__ __forceinline__ void fwd_sweep_d_tile(const FwdLevelArgs &a, c
 			for (int s_ = 0; s_ < K; s_++)
 				kv[s_] = sel_coef<W, false>(s_, vend[s_]);
 		}
-		auto vertical = [&](auto ends_tag) {
-			constexpr bool ENDS = decltype(ends_tag)::value;
-			auto vstep = [&](int s_, T c, T l, T r) {
-				if constexpr (kSel && ENDS)
-					return sel_step<W, false>(s_, vend[s_], kv[s_], c, l, r);
-				else if constexpr (kSel)
-					return W::fwd_step(s_, c, l, r);
-				else
-					return fwd_step_at<W>(s_, ENDS && vend[s_], c, l, r);
-			};
-#pragma unroll
-			for (int v = 0; v < CPT; v++) {
-				const T ov = row[0][v], ev = row[1][v];
-				if constexpr (K == 4) {
-					const T d1n = vstep(0, ov, st[0][v], ev);
-					const T s1n = vstep(1, st[0][v], st[1][v], d1n);
-					const T d2n = vstep(2, st[1][v], st[2][v], s1n);
-					const T s2n = vstep(3, st[2][v], st[3][v], d2n);
-					lo[v] = W::fwd_scale(0, s2n);
-					hi[v] = W::fwd_scale(1, d2n);
-					st[0][v] = ev;
-					st[1][v] = d1n;
-					st[2][v] = s1n;
-					st[3][v] = d2n;
-				} else {
-					const T d1n = vstep(0, ov, st[0][v], ev);
-					const T s1n = vstep(1, st[0][v], st[1][v], d1n);
-					lo[v] = W::fwd_scale(0, s1n);
-					hi[v] = W::fwd_scale(1, d1n);
-					st[0][v] = ev;
-					st[1][v] = d1n;
-				}
-			}
-		};
 		if (__builtin_expect(v_any, 0)) {
 			DWT_END_PATH();
-			vertical(std::true_type{});
-		}
-		else
-			vertical(std::false_type{});
+			fwd_vertical<W, kSel ? kColSel : kColEnds>(row, st, lo, hi, vend, kv);
+		} else
+			fwd_vertical<W, kColNone>(row, st, lo, hi);
 		if (it >= K) {
 			const int k = A + it - K;
 			// each quarter row of the Mallat layout is a buffer of its own
@@ -275,7 +196,7 @@ static __device__ __forceinline__ void fwd_sweep_d_tile(const FwdLevelArgs &a, c
 
 // the tile by the instantiation of the policy's line ends the level needs (dwt_lift.h; see fwd_sweep_any_tile)
 template <class W, int RING>
-__global__ __launch_bounds__(256) void k_fwd_sweep_d(FwdLevelArgs a, SweepGeomD g)
+__global__ __launch_bounds__(256) void k_fwd_sweep_d(FwdLevelArgs a, SweepGeom g)
 {
 	if constexpr (W::kEndForms) {
 		if (a.W % 4 == 0 && a.W >= 64 && a.H >= 64)
@@ -287,7 +208,7 @@ __global__ __launch_bounds__(256) void k_fwd_sweep_d(FwdLevelArgs a, SweepGeomD 
 }
 
 template <class W, int RING>
-static hipError_t fwd_launch_d(const FwdLevelArgs &a, const SweepGeomD &g, dim3 grid, int waves, hipStream_t s)
+static hipError_t fwd_launch_d(const FwdLevelArgs &a, const SweepGeom &g, dim3 grid, int waves, hipStream_t s)
 {
 	const size_t lds = (size_t)waves * RING * (256 * 8 + 64);
 	if (hipError_t e = allow_lds((const void *)k_fwd_sweep_d<W, RING>, lds))
@@ -302,7 +223,7 @@ static hipError_t fwd_level_d_t(const FwdLevelArgs &a, const SweepTuning &t, hip
 	if (a.W < 2 || a.H < 2 || a.batch < 1)
 		return hipErrorInvalidValue;
 	constexpr int TW = 256;
-	SweepGeomD g;
+	SweepGeom g;
 	const int Hd = (a.H + 1) / 2;
 	g.ntx = (a.W + TW - 1) / TW;
 	// tile heights as the float sweep picks them for the same number of BYTES per row
@@ -316,15 +237,11 @@ static hipError_t fwd_level_d_t(const FwdLevelArgs &a, const SweepTuning &t, hip
 	}
 	g.tile_pairs = tp;
 	g.swz = t.xcd_swizzle;
-	const int waves = t.waves >= 1 && t.waves <= 4 ? t.waves : 4;
+	const int waves = sweep_waves(t);
 	const int nty = (Hd + tp - 1) / tp;
 	const int ring = (t.ring == 8 || t.ring == 16) ? t.ring : ((g.ntx >= waves && (long)g.ntx * nty * a.batch >= 3072) ? 16 : 8);
 	g.wave_horiz = ring == 16;
-	dim3 grid;
-	if (g.wave_horiz)
-		grid = dim3(((g.ntx + waves - 1) / waves) * nty, a.batch);
-	else
-		grid = dim3(g.ntx * ((nty + waves - 1) / waves), a.batch);
+	const dim3 grid = sweep_grid(g, nty, waves, a.batch);
 	return ring == 16 ? fwd_launch_d<W, 16>(a, g, grid, waves, s) : fwd_launch_d<W, 8>(a, g, grid, waves, s);
 }
 
@@ -345,31 +262,20 @@ hipError_t launch_fwd_level_d(Wavelet w, const FwdLevelArgs &a, const SweepTunin
 // [L main 512 | H main 512 | L halo 64 | H halo 64]; a halo block is [4 columns left of the tile |
 // 4 columns right of it].  A lane needs the 5 subband columns around its own of each half.
 template <class W, int RING>
-static __device__ __forceinline__ void inv_sweep_d_tile(const InvLevelArgs &a, const SweepGeomD &g)
+static __device__ __forceinline__ void inv_sweep_d_tile(const InvLevelArgs &a, const SweepGeom &g)
 {
 	using T = double;
 	constexpr int K = W::K, CPT = 2, TW = 64 * CPT, M = TW / 2, RSB = 2 * M * 8 + 128, NARR = CPT + 2 * K - 1;
 	constexpr int kAhead = RING / 2 - 1, kDmaPerIter = 2 * 2;
 	extern __shared__ __attribute__((aligned(16))) char smem[];
 
-	const int lane = threadIdx.x & 63, nwv = blockDim.x >> 6;
-	const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-	const int bid = tile_block_id(g.swz);
-	int tx, ty;
-	if (g.wave_horiz) {
-		const int ntxb = (g.ntx + nwv - 1) / nwv;
-		tx = (bid % ntxb) * nwv + wv;
-		ty = bid / ntxb;
-	} else {
-		tx = bid % g.ntx;
-		ty = (bid / g.ntx) * nwv + wv;
-	}
+	const int lane = threadIdx.x & 63;
+	const SweepTile tile = sweep_tile(a, g);
+	if (!tile.live)
+		return;
+	const int wv = tile.wv, tx = tile.tx, A = tile.A, B = tile.B;
 	const int img = blockIdx.y;
 	const int Wd = (a.W + 1) >> 1, Hd = (a.H + 1) >> 1;
-	const int A = ty * g.tile_pairs;
-	if (A >= Hd || tx >= g.ntx)
-		return;
-	const int B = min(A + g.tile_pairs, Hd);
 	const int c0 = tx * TW, cl0 = c0 >> 1;
 	const int n_iter = (B - A) + K;
 	const int p0 = A - K / 2;
@@ -394,30 +300,12 @@ static __device__ __forceinline__ void inv_sweep_d_tile(const InvLevelArgs &a, c
 	const int hd = (lane >> 1) & 7, hs = (lane >> 4) & 1;
 	const int hsub = hd < 4 ? cl0 - 4 + hd : cl0 + M + (hd - 4);
 	const int halo_col = (kSel ? reflect_near(2 * hsub + hs, a.W) : reflect(2 * hsub + hs, a.W)) >> 1;
-	// line-end forms (dwt_lift.h; see k_inv_sweep): the lane's samples c - K + 1 .. that are a row's ends, any in this
-	// tile, and the test for a row being a column's end
-	[[maybe_unused]] unsigned hends = 0;
-	[[maybe_unused]] bool h_any = false, h_simple = false;
-	constexpr unsigned kCand = (1u << (K - 1)) | (1u << (K + CPT - 2)); // the two entries that meet a line end when W is a multiple of CPT
-	[[maybe_unused]] bool e0 = false, e1 = false;
-	[[maybe_unused]] T kh[K];
-	if constexpr (kSel) {
-		const unsigned m = end_mask_long<NARR>(c0 + lane * CPT - K + 1, a.W);
-		e0 = (m >> (K - 1)) & 1;
-		e1 = (m >> (K + CPT - 2)) & 1;
-		sel_coefs<W, true, K - 1>(kh, e0, e1);
-	} else if constexpr (W::kEndForms) {
-		hends = end_mask<NARR>(c0 + lane * CPT - K + 1, a.W);
-		h_any = __builtin_amdgcn_ballot_w64(hends != 0) != 0;
-		h_simple = __builtin_amdgcn_ballot_w64((hends & ~(kCand | 1u | (1u << (NARR - 1)))) != 0) == 0;
-	}
+	// the row ends among the lane's samples c - K + 1 .. c + CPT + K - 1
+	RowEnds<W, true, NARR, K - 1, K + CPT - 2> he;
+	if constexpr (W::kEndForms || kSel) // (the build without end forms: not even the arguments -- one instruction of the prologue)
+		he.vote(he.init(c0 + lane * CPT - K + 1, a.W), false);
 	const bool tall = kSel || a.H >= 64;
-	auto row_is_end = [&](int r) {
-		if (tall)
-			return r == 0 || r == a.H - 1;
-		const int rr = reflect(r, a.H);
-		return rr == 0 || rr == a.H - 1;
-	};
+	const auto row_is_end = row_end_test(a, tall);
 
 	auto issue = [&](int it) {
 		const int p = p0 + it;
@@ -453,12 +341,12 @@ static __device__ __forceinline__ void inv_sweep_d_tile(const InvLevelArgs &a, c
 		}
 	};
 
-	T st[K][CPT];
+	T st[K][1][CPT];
 #pragma unroll
 	for (int s = 0; s < K; s++)
 #pragma unroll
 		for (int v = 0; v < CPT; v++)
-			st[s][v] = 0;
+			st[s][0][v] = 0;
 
 	for (int it = 0; it < kAhead && it < n_iter; it++)
 		issue(it);
@@ -513,17 +401,7 @@ static __device__ __forceinline__ void inv_sweep_d_tile(const InvLevelArgs &a, c
 		T val[2][CPT];
 #pragma unroll
 		for (int rr = 0; rr < 2; rr++) {
-			if constexpr (kSel) {
-				lift_regs_sel<W, NARR, true, K - 1, K + CPT - 2>(x[rr], e0, e1, kh);
-			} else if (__builtin_expect(!h_any, 1)) {
-				lift_inv_regs<W, NARR>(x[rr], 0u);
-			} else if (h_simple) {
-				DWT_END_PATH();
-				lift_inv_regs<W, NARR, kCand>(x[rr], hends);
-			} else {
-				DWT_END_PATH();
-				lift_inv_regs<W, NARR>(x[rr], hends);
-			}
+			he.lift(x[rr]);
 #pragma unroll
 			for (int v = 0; v < CPT; v++)
 				val[rr][v] = W::inv_scale(rr, x[rr][K - 1 + v]);
@@ -542,46 +420,11 @@ static __device__ __forceinline__ void inv_sweep_d_tile(const InvLevelArgs &a, c
 			for (int s_ = 0; s_ < K; s_++)
 				kv[s_] = sel_coef<W, true>(s_, vend[s_]);
 		}
-		auto vertical = [&](auto ends_tag) {
-			constexpr bool ENDS = decltype(ends_tag)::value;
-			auto vstep = [&](int s_, T c, T l, T r) {
-				if constexpr (kSel && ENDS)
-					return sel_step<W, true>(s_, vend[s_], kv[s_], c, l, r);
-				else if constexpr (kSel)
-					return W::inv_step(s_, c, l, r);
-				else
-					return inv_step_at<W>(s_, ENDS && vend[s_], c, l, r);
-			};
-#pragma unroll
-			for (int v = 0; v < CPT; v++) {
-				const T s2 = val[0][v], d2 = val[1][v];
-				if constexpr (K == 4) {
-					const T s1n = vstep(0, s2, st[0][v], d2);
-					const T d1n = vstep(1, st[0][v], st[1][v], s1n);
-					const T en = vstep(2, st[1][v], st[2][v], d1n);
-					const T on = vstep(3, st[2][v], st[3][v], en);
-					odd_row[v] = on;
-					even_row[v] = en;
-					st[0][v] = d2;
-					st[1][v] = s1n;
-					st[2][v] = d1n;
-					st[3][v] = en;
-				} else {
-					const T en = vstep(0, s2, st[0][v], d2);
-					const T on = vstep(1, st[0][v], st[1][v], en);
-					odd_row[v] = on;
-					even_row[v] = en;
-					st[0][v] = d2;
-					st[1][v] = en;
-				}
-			}
-		};
 		if (__builtin_expect(v_any, 0)) {
 			DWT_END_PATH();
-			vertical(std::true_type{});
-		}
-		else
-			vertical(std::false_type{});
+			inv_vertical<W, kSel ? kColSel : kColEnds>(val[0], val[1], st, 0, odd_row, even_row, vend, kv);
+		} else
+			inv_vertical<W, kColNone>(val[0], val[1], st, 0, odd_row, even_row);
 		const int pe = (K == 4) ? p - 1 : p;
 		const int po = (K == 4) ? p - 2 : p - 1;
 		const bool ve = pe >= A && pe < B;
@@ -595,7 +438,7 @@ static __device__ __forceinline__ void inv_sweep_d_tile(const InvLevelArgs &a, c
 }
 
 template <class W, int RING>
-__global__ __launch_bounds__(256) void k_inv_sweep_d(InvLevelArgs a, SweepGeomD g)
+__global__ __launch_bounds__(256) void k_inv_sweep_d(InvLevelArgs a, SweepGeom g)
 {
 	if constexpr (W::kEndForms) {
 		if (a.W % 2 == 0 && a.W >= 64 && a.H >= 64)
@@ -607,7 +450,7 @@ __global__ __launch_bounds__(256) void k_inv_sweep_d(InvLevelArgs a, SweepGeomD 
 }
 
 template <class W, int RING>
-static hipError_t inv_launch_d(const InvLevelArgs &a, const SweepGeomD &g, dim3 grid, int waves, hipStream_t s)
+static hipError_t inv_launch_d(const InvLevelArgs &a, const SweepGeom &g, dim3 grid, int waves, hipStream_t s)
 {
 	const size_t lds = (size_t)waves * RING * (2 * 64 * 8 + 128);
 	if (hipError_t e = allow_lds((const void *)k_inv_sweep_d<W, RING>, lds))
@@ -622,7 +465,7 @@ static hipError_t inv_level_d_t(const InvLevelArgs &a, const SweepTuning &t, hip
 	if (a.W < 2 || a.H < 2 || a.batch < 1)
 		return hipErrorInvalidValue;
 	constexpr int TW = 128;
-	SweepGeomD g;
+	SweepGeom g;
 	const int Hd = (a.H + 1) / 2;
 	g.ntx = (a.W + TW - 1) / TW;
 	int tp = t.tile_pairs > 0 ? t.tile_pairs : 32;
@@ -635,14 +478,9 @@ static hipError_t inv_level_d_t(const InvLevelArgs &a, const SweepTuning &t, hip
 	}
 	g.tile_pairs = tp;
 	g.swz = t.xcd_swizzle;
-	const int waves = t.waves >= 1 && t.waves <= 4 ? t.waves : 4;
-	const int nty = (Hd + tp - 1) / tp;
-	g.wave_horiz = 0;
-	dim3 grid;
-	if (g.wave_horiz)
-		grid = dim3(((g.ntx + waves - 1) / waves) * nty, a.batch);
-	else
-		grid = dim3(g.ntx * ((nty + waves - 1) / waves), a.batch);
+	const int waves = sweep_waves(t);
+	g.wave_horiz = 0; // stacked tiles
+	const dim3 grid = sweep_grid(g, (Hd + tp - 1) / tp, waves, a.batch);
 	return t.ring_inv == 16 ? inv_launch_d<W, 16>(a, g, grid, waves, s) : inv_launch_d<W, 8>(a, g, grid, waves, s);
 }
 

@@ -1,5 +1,6 @@
 // dwt_sweep2d_inv.hip -- the inverse tile sweep of the 2-D lifting DWT (see dwt_sweep2d.hip for the scheme) and its
-// launchers.  A translation unit of its own: the two sweeps compile side by side.
+// launchers.  A translation unit of its own: the two sweeps compile side by side.  Tile origin, vertical pass and grid
+// are the shared pieces of dwt_sweep2d.h.
 #include "dwt_sweep2d.h"
 
 namespace dwt {
@@ -41,27 +42,16 @@ static __device__ __forceinline__ void inv_sweep_tile(const InvLevelArgs &a, con
 	constexpr int kDmaPerIter = SP ? 4 + kDmaMain + 1 : 2 * (kDmaMain + 1);
 	extern __shared__ __attribute__((aligned(16))) char smem[];
 
-	const int lane = threadIdx.x & 63, nwv = blockDim.x >> 6;
-	// wave-uniform on purpose: tile geometry, row indices and row pointers then live in SGPRs
-	const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-	const int bid = tile_block_id(g.swz, X ? g.first : 0, g.tile_blocks);
-	int tx, ty;
-	if (g.wave_horiz) {
-		const int ntxb = (g.ntx + nwv - 1) / nwv;
-		tx = (bid % ntxb) * nwv + wv;
-		ty = bid / ntxb;
-	} else {
-		tx = bid % g.ntx;
-		ty = (bid / g.ntx) * nwv + wv;
-	}
+	const int lane = threadIdx.x & 63;
+	const SweepTile tile = sweep_tile(a, g, X ? g.first : 0, g.tile_blocks);
+	if (!tile.live)
+		return;
+	if (a.pair_hi > 0 && (tile.A < a.pair_lo || tile.A >= a.pair_hi))
+		return; // this launch computes a band of the level only
+	const int wv = tile.wv, tx = tile.tx, A = tile.A, B = tile.B;
+	[[maybe_unused]] const int ty = tile.ty;
 	const int img = blockIdx.y;
 	const int Wd = (a.W + 1) >> 1, Hd = (a.H + 1) >> 1;
-	const int A = ty * g.tile_pairs;
-	if (A >= Hd || tx >= g.ntx)
-		return;
-	if (a.pair_hi > 0 && (A < a.pair_lo || A >= a.pair_hi))
-		return; // this launch computes a band of the level only
-	const int B = min(A + g.tile_pairs, Hd);
 	const int c0 = tx * TW;
 	const int cl0 = c0 >> 1;
 	const int n_iter = (B - A) + K;
@@ -248,6 +238,8 @@ static __device__ __forceinline__ void inv_sweep_tile(const InvLevelArgs &a, con
 			for (int v = 0; v < NVG; v++)
 				st[s][gi][v] = 0;
 
+	// (the line-end state and its dispatch below are RowEnds of dwt_sweep2d.h written out per column group: through the
+	// struct nine of this file's kernels compile to other instruction counts)
 	// explicit line-end forms: the ends of a row among each group's samples c - K + 1 .. c + CG + K - 1 -- only the tiles
 	// that hold column 0 or W - 1 have any (`h_any`, wave-uniform: the interior tiles run the plain lift) --; the rows that
 	// are a column's ends are found per iteration (wave-uniform as well)
@@ -278,6 +270,7 @@ static __device__ __forceinline__ void inv_sweep_tile(const InvLevelArgs &a, con
 			sel_coefs<W, true, K - 1>(kh[gi], e0[gi], e1[gi]);
 		}
 	}
+	// (row_end_test of dwt_sweep2d.h written out: through it the split-row 5/3 kernel compiles to other counts)
 	[[maybe_unused]] auto row_is_end = [&](int r) {
 		if (tall || kIsSelEnds<W>) // (SelEnds runs on levels of 64 rows or more)
 			return r == 0 || r == a.H - 1;
@@ -426,8 +419,7 @@ static __device__ __forceinline__ void inv_sweep_tile(const InvLevelArgs &a, con
 			}
 		}
 
-		// vertical inverse, streaming.  K == 4: at step p the rows 2p-3 (odd) and
-		// 2p-2 (even) are final; K == 2: rows 2p-1 and 2p.
+		// vertical inverse, streaming (inv_vertical).
 		// step s of this iteration acts on row 2p-s (a policy of one step: its step 0 on the odd row 2p-1): which of them are
 		// column ends (wave-uniform; almost never any)
 		const int r0 = K == 1 ? 2 * p - 1 : 2 * p;
@@ -441,108 +433,39 @@ static __device__ __forceinline__ void inv_sweep_tile(const InvLevelArgs &a, con
 			}
 		}
 		T odd_row[G][NVG], even_row[G][NVG];
-		auto vertical = [&](auto ends_tag) {
-			constexpr bool ENDS = decltype(ends_tag)::value;
+		auto vertical = [&](auto mode, const bool *ve = nullptr, const T *kv = nullptr) {
 #pragma unroll
 			for (int gi = 0; gi < G; gi++)
-#pragma unroll
-			for (int v = 0; v < NVG; v++) {
-				const T s2 = val[0][gi][v], d2 = val[1][gi][v];
-				if constexpr (K == 1) {
-					// st: [0] d[p-1], [1] e[p-1]; the even row p is final as it comes
-					const T on = inv_step_at<W>(0, ENDS && vend[0], st[0][gi][v], st[1][gi][v], s2);      // o[p-1]
-					odd_row[gi][v] = on;
-					even_row[gi][v] = s2;
-					st[0][gi][v] = d2;
-					st[1][gi][v] = s2;
-				} else if constexpr (K == 4) {
-					// st: [0] d2[p-1], [1] s1[p-1], [2] d1[p-2], [3] e[p-2]
-					const T s1n = inv_step_at<W>(0, ENDS && vend[0], s2, st[0][gi][v], d2);               // s1[p]
-					const T d1n = inv_step_at<W>(1, ENDS && vend[1], st[0][gi][v], st[1][gi][v], s1n);    // d1[p-1]
-					const T en = inv_step_at<W>(2, ENDS && vend[2], st[1][gi][v], st[2][gi][v], d1n);     // e[p-1]
-					const T on = inv_step_at<W>(3, ENDS && vend[3], st[2][gi][v], st[3][gi][v], en);      // o[p-2]
-					odd_row[gi][v] = on;
-					even_row[gi][v] = en;
-					st[0][gi][v] = d2;
-					st[1][gi][v] = s1n;
-					st[2][gi][v] = d1n;
-					st[3][gi][v] = en;
-				} else {
-					// st: [0] d[p-1], [1] e[p-1]
-					const T en = inv_step_at<W>(0, ENDS && vend[0], s2, st[0][gi][v], d2);                // e[p]
-					const T on = inv_step_at<W>(1, ENDS && vend[1], st[0][gi][v], st[1][gi][v], en);      // o[p-1]
-					odd_row[gi][v] = on;
-					even_row[gi][v] = en;
-					st[0][gi][v] = d2;
-					st[1][gi][v] = en;
-				}
-			}
+				inv_vertical<W, decltype(mode)::value>(val[0][gi], val[1][gi], st, gi, odd_row[gi], even_row[gi], ve, kv);
 		};
 		if constexpr (W::kEndForms) {
 			if (__builtin_expect(v_any, 0)) {
 				DWT_END_PATH();
-				vertical(std::true_type{});
+				vertical(ColTag<kColEnds>{}, vend);
 			}
 			else
-				vertical(std::false_type{});
+				vertical(ColTag<kColNone>{});
 		} else if constexpr (kIsSelEnds<W>) {
 			// step s acts on row 2p-s; where that row is an end of its column (wave-uniform, the top and bottom tiles' first /
 			// last iterations) the step's coefficient is doubled and its state tap -- the same values as the other tap
-			// there -- gives way to -0.0.  Deep ring: the iterations that meet no end take the plain body.
+			// there -- gives way to -0.0.  The iterations that meet no end take the plain body.
 			bool ve[K], any = false;
 #pragma unroll
 			for (int s_ = 0; s_ < K; s_++) {
 				ve[s_] = row_is_end(r0 - s_);
 				any = any || ve[s_];
 			}
-			auto vertical_sel = [&]() {
+			if (__builtin_expect(any, 0)) {
+				DWT_END_PATH();
 				T kv[K];
 #pragma unroll
 				for (int s_ = 0; s_ < K; s_++)
 					kv[s_] = sel_coef<W, true>(s_, ve[s_]);
-#pragma unroll
-				for (int gi = 0; gi < G; gi++)
-#pragma unroll
-				for (int v = 0; v < NVG; v++) {
-					const T s2 = val[0][gi][v], d2 = val[1][gi][v];
-					if constexpr (K == 1) {
-						const T on = sel_step<W, true>(0, ve[0], kv[0], st[0][gi][v], st[1][gi][v], s2);
-						odd_row[gi][v] = on;
-						even_row[gi][v] = s2;
-						st[0][gi][v] = d2;
-						st[1][gi][v] = s2;
-					} else if constexpr (K == 4) {
-						const T s1n = sel_step<W, true>(0, ve[0], kv[0], s2, st[0][gi][v], d2);
-						const T d1n = sel_step<W, true>(1, ve[1], kv[1], st[0][gi][v], st[1][gi][v], s1n);
-						const T en = sel_step<W, true>(2, ve[2], kv[2], st[1][gi][v], st[2][gi][v], d1n);
-						const T on = sel_step<W, true>(3, ve[3], kv[3], st[2][gi][v], st[3][gi][v], en);
-						odd_row[gi][v] = on;
-						even_row[gi][v] = en;
-						st[0][gi][v] = d2;
-						st[1][gi][v] = s1n;
-						st[2][gi][v] = d1n;
-						st[3][gi][v] = en;
-					} else {
-						const T en = sel_step<W, true>(0, ve[0], kv[0], s2, st[0][gi][v], d2);
-						const T on = sel_step<W, true>(1, ve[1], kv[1], st[0][gi][v], st[1][gi][v], en);
-						odd_row[gi][v] = on;
-						even_row[gi][v] = en;
-						st[0][gi][v] = d2;
-						st[1][gi][v] = en;
-					}
-				}
-			};
-			// (shallow ring: the launches of a few rounds of waves, bound by the longest wave -- the top tiles', for whom a
-			// second body means instructions fetched cold from HBM, 1 us a launch; there every iteration selects)
-			if constexpr (RING == 0)
-				vertical_sel();
-			else if (__builtin_expect(any, 0)) {
-				DWT_END_PATH();
-				vertical_sel();
+				vertical(ColTag<kColSel>{}, ve, kv);
 			} else
-				vertical(std::false_type{});
+				vertical(ColTag<kColNone>{});
 		} else {
-			vertical(std::false_type{});
+			vertical(ColTag<kColNone>{});
 		}
 		// output rows and their validity inside this tile
 		const int pe = (K == 4) ? p - 1 : p;     // pair index of even_row (K == 1 and 2: the row p)
@@ -714,17 +637,13 @@ static hipError_t inv_level_t(const InvLevelArgs &a, const SweepTuning &t, hipSt
 	g.ntx = (a.W + TW - 1) / TW;
 	g.swz = t.xcd_swizzle;
 	const int Hd = (a.H + 1) / 2;
-	const int waves = t.waves >= 1 && t.waves <= 4 ? t.waves : 4;
+	const int waves = sweep_waves(t);
 	const int nty = (Hd + g.tile_pairs - 1) / g.tile_pairs;
 	int ring = t.ring_inv == 16 ? 16 : 8;
 	// the waves of a workgroup side by side where the row of tiles has room for them (round 4, tile heights tuned for
 	// either layout: 32 images + 0.2 %, 8 images + 1.5 %, one image 168.7 -> 164.5 us)
 	g.wave_horiz = g.ntx >= waves;
-	dim3 grid;
-	if (g.wave_horiz)
-		grid = dim3(((g.ntx + waves - 1) / waves) * nty, a.batch);
-	else
-		grid = dim3(g.ntx * ((nty + waves - 1) / waves), a.batch);
+	const dim3 grid = sweep_grid(g, nty, waves, a.batch);
 	if (a.sh.rows && (!a.interleaved || a.batch != 1 || a.in_step != 1 || g.tile_pairs != a.sh.tile_pairs))
 		return hipErrorInvalidValue; // the snapshot of an in-place level was taken for other tiles
 	if (a.interleaved) {

@@ -174,7 +174,7 @@ def test_padded_device_pitch(dwt, oracle):
 
 
 # ---- every tile geometry gives the same bits --------------------------------------------
-@pytest.mark.parametrize("wname", ["cdf97_s", "cdf53_i", "cdf97_i"])
+@pytest.mark.parametrize("wname", ["cdf97_s", "cdf53_i", "cdf97_i", "cdf53_s"])
 def test_tile_variants_agree(dwt, oracle, wname):
     ff, fi, dt = NAMES[wname]
     h, w = 1100, 1300
@@ -205,6 +205,41 @@ def test_tile_variants_agree(dwt, oracle, wname):
                         b.free()
     finally:
         for k, v in (("cpt", 0), ("tile_pairs", 0), ("waves", 4), ("xcd_swizzle", 1)):
+            dwt.set_option(k, v)
+
+
+@pytest.mark.parametrize("wname", ["cdf97_d", "cdf53_d"])
+def test_double_tile_variants_agree(dwt, oracle, wname):
+    """The double-precision sweeps under every tile height, wave count, ring depth and block order give the oracle's
+    bits.  132 x 520: the select form at both levels, three forward tiles (the last 8 columns wide), five inverse
+    tiles, several tile rows; 67 x 259: odd both ways (the general end forms), level 1 below 64 rows (reflection
+    with more than one bounce); 40 x 300: fewer than 64 rows at level 0."""
+    ff, fi, dt = NAMES[wname]
+    wid = dwt.WAVELET_ID[wname]
+    try:
+        for h, w in ((132, 520), (67, 259), (40, 300)):
+            rng = np.random.default_rng(h * 31 + w)
+            img = rand_img(rng, h, w, dt)
+            want = img.copy()
+            jw = oracle.fwd(ff, want, 2)
+            rec_want = want.copy()
+            oracle.inv(fi, rec_want, jw)
+            for tp in (2, 8):
+                for waves in (1, 4):
+                    for ring in (8, 16):
+                        for swz in (0, 1):
+                            for k, v in (("tile_pairs", tp), ("waves", waves), ("ring", ring), ("ring_inv", ring), ("xcd_swizzle", swz)):
+                                dwt.set_option(k, v)
+                            a = dwt.DeviceImage(h, w, itemsize=8).upload(img)
+                            b = dwt.DeviceImage(h, w, itemsize=8).upload(np.zeros_like(img))
+                            j = dwt._fwd(wid, a.ptr, b.ptr, a.stride_x, 8, w, h, w, h, 2, 0, 0, "fwd")
+                            assert j == jw and np.array_equal(bits(b.download(dt)), bits(want)), (h, w, tp, waves, ring, swz)
+                            dwt._inv(wid, b.ptr, a.ptr, a.stride_x, 8, w, h, w, h, j, 0, 0, "inv")
+                            assert np.array_equal(bits(a.download(dt)), bits(rec_want)), (h, w, tp, waves, ring, swz)
+                            a.free()
+                            b.free()
+    finally:
+        for k, v in (("tile_pairs", 0), ("waves", 4), ("ring", 0), ("ring_inv", 8), ("xcd_swizzle", 1)):
             dwt.set_option(k, v)
 
 
