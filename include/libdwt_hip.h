@@ -481,6 +481,32 @@ int dwt_hip_swt1d_batch(int wavelet, const void *src, size_t line_stride, size_t
 /* ONE level at dilation 1 << level of one line, as the reference's entry takes it (include/swt.h): src, dst_l and dst_h
  * have N elements `stride` bytes apart; level 0 .. DWT_HIP_SWT_MAX_LEVELS-1 */
 int dwt_hip_swt1d_level(int wavelet, const void *src, void *dst_l, void *dst_h, int N, int stride, int level);
+/* The stationary wavelet transform of image batches: the two functions above applied separably.  Level l
+ * (0-based, dilation 1 << l) filters its input A -- the image at level 0, LL of level l-1 after that -- along x for every
+ * row, Lr = conv_x(A, low), Hr = conv_x(A, high), and then along y for every column: LL = conv_y(Lr, low), LH =
+ * conv_y(Lr, high), HL = conv_y(Hr, low), HH = conv_y(Hr, high); borders replicated, no direction ever skipped (a 1-row
+ * image takes its column pass with N = 1), every plane size_x x size_y.  Band names as enum dwt_subbands: HL is high-pass
+ * along a row.  Forward only.  stride_x is the row pitch and stride_y the element pitch of src in bytes; images are
+ * batch_stride bytes apart.  Detail band k (HL = 1, LH = 2, HH = 3) of level l of image b goes to
+ *     dst_h + b*dst_batch_stride + (3*l + k-1)*plane_stride + y*dst_stride_x + 4*x.
+ * l_mode 0: no LL is written (dst_l may be NULL); 1: the last level's LL, to plane 0 of dst_l + b*dst_batch_stride;
+ * 2: level l's LL to plane l there.  `levels` runs from 0 (nothing is written) to DWT_HIP_SWT_MAX_LEVELS; dilations beyond
+ * either size are legal.  dst_h and dst_l share dst_batch_stride: dst_l needs batch * dst_batch_stride bytes of its own, or
+ * lies in the gap behind every image's detail planes.  All pointers are host memory or all device memory.  src is never written; src, dst_h and dst_l
+ * must not overlap, planes and images must be apart, a pitch must hold its row, batch and both sizes are at least 1
+ * (errors otherwise).  Dense device images (stride_y 4) take ONE kernel launch per level for the whole batch on levels
+ * 0 .. DWT_HIP_SWT2D_FUSED_LEVELS-1; strided elements, deeper levels and every call under option "swt2d_fused" = 0 take
+ * two (a row pass and a column pass through library scratch).  Output is bit-identical to the reference's functions run
+ * over the rows and then over the columns, over the whole float range. */
+#define DWT_HIP_SWT2D_FUSED_LEVELS 5
+#define DWT_HIP_SWT2D_TILE_W 256 /* the fused kernel's tile: columns, and rows of the level's row lattice y0 + (i << l) */
+#define DWT_HIP_SWT2D_TILE_H 32
+int dwt_hip_swt2d_batch(int wavelet, const void *src, size_t batch_stride, int batch, int stride_x, int stride_y, int size_x, int size_y,
+	int levels, void *dst_h, void *dst_l, int l_mode, size_t dst_batch_stride, size_t plane_stride, int dst_stride_x);
+/* ONE level at dilation 1 << level of one image: the four planes have rows dst_stride_x and elements dst_stride_y bytes
+ * apart; level 0 .. DWT_HIP_SWT_MAX_LEVELS-1.  src and the four planes must not overlap. */
+int dwt_hip_swt2d_level(int wavelet, const void *src, int stride_x, int stride_y, int size_x, int size_y, int level, void *dst_ll,
+	void *dst_hl, void *dst_lh, void *dst_hh, int dst_stride_x, int dst_stride_y);
 /* The feature statistics of the transform's planes without the planes: feature k of the mask (enum order) of level l of
  * line y at fv[y*fv_line_stride + k*levels + l] (floats).  band 0: the H planes, 1: the L planes.  Each value is what
  * dwt_util_band_<name>_s(plane, 0, sizeof(float), N, 1[, p]) gives for that plane, wps with j = l.  fv lies where src

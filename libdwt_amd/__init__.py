@@ -1156,6 +1156,47 @@ swt_cdf97_f_ex_stride_s = _swt_entry("swt_cdf97_f_ex_stride_s", CDF97_S)
 swt_cdf53_f_ex_stride_s = _swt_entry("swt_cdf53_f_ex_stride_s", CDF53_S)
 
 
+# ---- stationary wavelet transform of image batches (include/libdwt_hip.h) ------------------------------
+SWT2D_FUSED_LEVELS = 5  # DWT_HIP_SWT2D_FUSED_LEVELS: dense device images take one launch per level on levels 0 .. 4
+SWT2D_TILE_W, SWT2D_TILE_H = 256, 32  # DWT_HIP_SWT2D_TILE_W / _H: the fused kernel's tile (columns, rows of the row lattice)
+lib.dwt_hip_swt2d_batch.argtypes = [_I, _P, _S, _I, _I, _I, _I, _I, _I, _P, _P, _I, _S, _S, _I]
+lib.dwt_hip_swt2d_batch.restype = _I
+lib.dwt_hip_swt2d_level.argtypes = [_I, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _I, _I]
+lib.dwt_hip_swt2d_level.restype = _I
+
+
+def swt2d_batch(wavelet, src, batch_stride, batch, stride_x, stride_y, size_x, size_y, levels, dst_h, dst_l=None, l_mode=0,
+                dst_batch_stride=0, plane_stride=0, dst_stride_x=0):
+    """dwt_hip_swt2d_batch: every level of the stationary transform of a batch of images, rows then columns.  Detail band
+    k (HL = 1, LH = 2, HH = 3) of level l of image b at dst_h + b*dst_batch_stride + (3*l + k-1)*plane_stride +
+    y*dst_stride_x + 4*x bytes; l_mode 0: no LL, 1: the last level's at plane 0 of dst_l, 2: level l's at plane l.  Dense
+    device images take one launch per level on levels 0 .. SWT2D_FUSED_LEVELS-1, two otherwise."""
+    w = _swt_wavelet(wavelet)
+    if batch < 1 or size_x < 1 or size_y < 1 or levels < 0 or levels > SWT_MAX_LEVELS:
+        raise DwtError("swt2d_batch: bad arguments (%d images of %d x %d samples, %d levels of at most %d)"
+                       % (batch, size_x, size_y, levels, SWT_MAX_LEVELS))
+    if l_mode not in (0, 1, 2):
+        raise DwtError("swt2d_batch: l_mode %r" % (l_mode,))
+    if l_mode and dst_l is None:
+        raise DwtError("swt2d_batch: l_mode %d needs dst_l" % l_mode)
+    if min(batch_stride, stride_x, stride_y, dst_batch_stride, plane_stride, dst_stride_x) < 0:
+        raise DwtError("swt2d_batch: negative stride")
+    _check(lib.dwt_hip_swt2d_batch(w, _addr(src), batch_stride, batch, stride_x, stride_y, size_x, size_y, levels, _addr(dst_h),
+                                   0 if dst_l is None else _addr(dst_l), l_mode, dst_batch_stride, plane_stride, dst_stride_x),
+           "dwt_hip_swt2d_batch")
+
+
+def swt2d_level(wavelet, src, stride_x, stride_y, size_x, size_y, level, dst_ll, dst_hl, dst_lh, dst_hh, dst_stride_x,
+                dst_stride_y=4):
+    """dwt_hip_swt2d_level: one level at dilation 1 << level of one image into four planes whose rows are dst_stride_x and
+    elements dst_stride_y bytes apart; host or device memory."""
+    w = _swt_wavelet(wavelet)
+    if size_x < 1 or size_y < 1 or level < 0 or level >= SWT_MAX_LEVELS:
+        raise DwtError("swt2d_level: bad arguments (%d x %d samples, level %d)" % (size_x, size_y, level))
+    _check(lib.dwt_hip_swt2d_level(w, _addr(src), stride_x, stride_y, size_x, size_y, level, _addr(dst_ll), _addr(dst_hl),
+                                   _addr(dst_lh), _addr(dst_hh), dst_stride_x, dst_stride_y), "dwt_hip_swt2d_level")
+
+
 # ---- time-frequency planes (include/libdwt_hip.h, include/gabor.h; DESIGN.md s14) -------------------------------------
 TIMEFREQ_KINDS = {"ft": 0, "wt": 1, "st": 2}
 TIMEFREQ_OUT = {"complex": 0, "abs": 1, "arg": 2}

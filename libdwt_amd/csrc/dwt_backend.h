@@ -50,7 +50,7 @@ struct Ctx {
 	Buf vol_host[2]; // device staging of host volumes (struct volume_t entries)
 	Buf eaw_w, eaw_ll[2]; // EAW: device weights of a host-pointer call, LL ping-pong of the fused levels
 	Buf feat_ws; // feature statistics: records, slab partials, band table, select histograms (dwt_backend_features.hip)
-	Buf swt_ws;  // SWT level by level: the L chain's two dense images (dwt_backend_swt.hip)
+	Buf swt_ws;  // SWT level by level: the L chain's two dense images (dwt_backend_swt.hip); 2-D: the LL chain and the passes' Lr, Hr (dwt_backend_swt2d.hip)
 	Buf cond_ws; // row conditioning: per-row medians, extrema, centres, moves, records (dwt_backend_condition.hip)
 	Buf band_ws; // band operators: the per-image operator tables of a batch (dwt_backend_bandops.hip)
 	// every device scratch buffer above: a new one is declared there, listed here, and named nowhere else for freeing
@@ -69,6 +69,7 @@ struct Ctx {
 	int feat_groups = 0; // workgroups of the feature slab passes (0: the launcher's rule); results do not depend on it
 	int tf_tiled = 1;  // time-frequency planes of dense lines through the LDS-tiled kernel (0: one thread per output, the cross-check)
 	int cond_fused = -1; // conditioning of dense rows of up to N1D_MAX samples: 1 in one launch, 0 one kernel per operation (the cross-check), -1 by batch size
+	int swt2d_fused = 1; // SWT levels of dense device images below SWT2D_FUSED_LEVELS in one launch each (0: a row pass and a column pass, the cross-check)
 	int swt_fused = 1; // SWT lines of up to N1D_MAX samples in one launch (0: one launch per level, the cross-check)
 	// options
 	SweepTuning tune;

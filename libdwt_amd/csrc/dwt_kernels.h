@@ -447,6 +447,25 @@ struct SwtLevelArgs {
 };
 hipError_t launch_swt_level(Wavelet w, const SwtLevelArgs &a, hipStream_t s);
 
+// The stationary wavelet transform of image batches (dwt_swt2d.hip): one level at dilation 1 << level,
+// the row pass (Lr, Hr along x) and then the column pass (LL, LH from Lr; HL, HH from Hr along y).  Every plane is W x H.
+constexpr int SWT2D_TILE_W = 256, SWT2D_TILE_H = 32; // the fused kernel's tile: columns, rows of the level's row lattice
+constexpr int SWT2D_FUSED_LEVELS = 5;                // ... which runs levels 0 .. 4 (dilations 1 .. 16)
+struct Swt2dLevelArgs {
+	const char *src; // element (x, y) of image b at src + b*src_bs + y*src_sx + x*src_sy (bytes)
+	long src_bs, src_sx, src_sy;
+	int W, H, batch, level;
+	char *ll, *hl, *lh, *hh; // ll may be null (no LL stored)
+	long ll_bs, ll_sx;       // LL has its own batch stride and pitch (the chain's scratch image, or the caller's plane)
+	long d_bs, d_sx;         // HL, LH, HH
+	long d_sy;               // the element stride of all four outputs
+	char *lr, *hr;           // the two passes: dense scratch planes, pitch 4*W, image b at + b*H*4*W
+};
+bool swt2d_fused_fits(const Swt2dLevelArgs &a); // dense elements, level below SWT2D_FUSED_LEVELS, a grid the launch can take
+hipError_t launch_swt2d_fused(Wavelet w, const Swt2dLevelArgs &a, hipStream_t s); // one launch: src read once, four planes written once
+hipError_t launch_swt2d_rows(Wavelet w, const Swt2dLevelArgs &a, hipStream_t s);  // src -> lr, hr; one thread per sample, any strides
+hipError_t launch_swt2d_cols(Wavelet w, const Swt2dLevelArgs &a, hipStream_t s);  // lr, hr -> ll, hl, lh, hh
+
 // Time-frequency planes (dwt_timefreq.hip): every line of a batch correlated with a bank of complex kernels,
 //   out(line, bin, t) = sum over the kernel's taps i, ascending, of x[t - center + i] * conj(k[i])   (taps inside [0, N) only),
 // from +0, product and sum rounded separately.  The device bank holds the taps already conjugated.

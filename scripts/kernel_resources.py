@@ -24,9 +24,9 @@ for ln in out.splitlines():
     elif "error" in ln or "warning:" in ln:
         print(ln, file=sys.stderr)
 for r in rows:
-    n = subprocess.run(["c++filt", r["name"]], capture_output=True, text=True).stdout.strip().split("(")[0]
+    n = subprocess.run(["c++filt", r["name"]], capture_output=True, text=True).stdout.strip().replace("(anonymous namespace)::", "").split("(")[0]
     if not re.search(pat, n):
         continue
     g = r.get
     print(f"{n:72s} vgpr {g('VGPRs')} agpr {g('AGPRs')} sgpr {g('SGPRs')} spill s{g('SGPRs Spill')}/v{g('VGPRs Spill')} "
-          f"scratch {g('ScratchSize [bytes/lane]')} occ {g('Occupancy [waves/SIMD]')}")
+          f"scratch {g('ScratchSize [bytes/lane]')} occ {g('Occupancy [waves/SIMD]')} lds {g('LDS Size [bytes/block]')}")
