@@ -464,6 +464,46 @@ int dwt_hip_map_batch(int op, void *ptr, size_t batch_stride, int batch, int str
 int dwt_hip_universal_threshold_batch(const void *ptr, size_t batch_stride, int batch, int stride_x, int size_x, int size_y,
 	float *lambda);
 
+/* N-term approximation: keep the coefficients of the N largest magnitudes, zero the rest -- the non-linear branch of the
+ * reference's examples/displ-vectors/vectors.c (:254-297), on coefficients that stay where they lie.
+ * A GROUP is `channels` (1 .. 4) dense float frames of size_x x size_y, the transforms of the channels of one image:
+ * channel c of group g at ptr + g*batch_stride + c*channel_stride, rows stride_x bytes apart.  Groups may follow each
+ * other (batch_stride spans a group) or every channel's frames may (channel_stride spans the batch).
+ *   SCOPE      FRAME: every position of the frame (what vectors.c does; j_max is ignored).  DETAILS: every position
+ *              outside the coarsest approximation band, the rectangle x < ceil(size_x / 2^J) && y < ceil(size_y / 2^J)
+ *              with J = dwt_hip_band_levels(size_x, size_y, j_max).  M positions are in scope.
+ *   MAGNITUDE  of a position, in float, every product and sum rounded on its own (no FMA), summed left to right, the
+ *              root correctly rounded: fabsf(c0) for one channel; sqrtf(c0*c0 + c1*c1) for two (vectors.c:261-264);
+ *              sqrtf((c0*c0 + c1*c1) + c2*c2) for three; one more term, added the same way, for four.
+ *   THRESHOLD  n = keep[g], and n = M where n < 1 or n > M (:281-283); thr is element n-1 of the scope's magnitudes
+ *              sorted in descending order (:279, :285).
+ *   APPLY      every position in scope with magnitude < thr gets +0.0f in every channel (:292-296); every other
+ *              coefficient keeps its bits.  Ties at thr are all kept: kept[g], the positions in scope with magnitude
+ *              >= thr, can exceed n.  Positions outside the scope and the bytes between a row's end and its pitch are
+ *              neither read for the decision nor written.
+ * M == 0 (DETAILS with J == 0, an empty frame) gives thr = 0, kept = 0, launches nothing and writes nothing.  A group
+ * that holds a NaN is not pinned (the reference's comparator is no order there); the call returns normally and the
+ * other groups of the batch are exact.  Infinities, overflowing squares and subnormals follow from the arithmetic.
+ * `ptr` may be host or device memory; `keep`, `thr` and `kept` are HOST arrays of `batch` entries, thr and kept may be
+ * NULL.  Dense device frames run where they lie, in at most 5 kernel launches whatever batch, channels and n; host
+ * frames and other element strides are staged through a dense device image and only the frames' own elements are
+ * written back.  Calls are ordered on the context's stream; with thr == NULL && kept == NULL a call on device frames
+ * does not wait for the device.  A null pointer, channels outside 1 .. 4, an unknown scope, negative sizes, more than
+ * INT_MAX positions in a frame, a pitch below its row, frames or channels closer than they span, thr or kept in device
+ * memory or a device address or stride that is no multiple of 4 return an error, launch nothing and write nothing. */
+enum dwt_hip_nterm_scope { DWT_HIP_NTERM_FRAME = 0, DWT_HIP_NTERM_DETAILS = 1 };
+int dwt_hip_keep_largest_batch(void *ptr, size_t batch_stride, int batch, int channels, size_t channel_stride, int stride_x,
+	int size_x, int size_y, int j_max, int scope, const int *keep, float *thr, int *kept);
+/* one frame of one channel, element (y, x) at ptr + y*stride_x + x*stride_y (host or device): the calling convention of
+ * dwt_hip_bands_apply */
+int dwt_hip_keep_largest(void *ptr, int stride_x, int stride_y, int size_x, int size_y, int j_max, int scope, int keep, float *thr,
+	int *kept);
+/* The magnitude map alone (vectors.c's `map`), one launch; the frames are only read.  The map of group g goes to
+ * map + g*map_batch_stride, rows map_stride_x bytes apart, dense elements.  Frames and map lie both in host or both in
+ * device memory and must not overlap. */
+int dwt_hip_magnitude_batch(const void *ptr, size_t batch_stride, int batch, int channels, size_t channel_stride, int stride_x,
+	int size_x, int size_y, void *map, size_t map_batch_stride, int map_stride_x);
+
 /* The stationary (undecimated) wavelet transform of rows: swt_cdf97_f_ex_stride_s / swt_cdf53_f_ex_stride_s (src/swt.c),
  * every level of a batch of lines in one call.  Level l (0-based) filters the low-pass plane of level
  * l-1 (level 0: the input) with the low-pass and the high-pass filter dilated by 1 << l, borders replicated; every plane

@@ -1088,6 +1088,50 @@ def universal_threshold_batch(ptr, batch_stride, batch, stride_x, size_x, size_y
     return lam
 
 
+# ---- N-term approximation: keep the N largest magnitudes (include/libdwt_hip.h) -------------------------
+NTERM_FRAME, NTERM_DETAILS = 0, 1  # enum dwt_hip_nterm_scope
+lib.dwt_hip_keep_largest_batch.argtypes = [_P, _S, _I, _I, _S, _I, _I, _I, _I, _I, _P, _P, _P]
+lib.dwt_hip_keep_largest_batch.restype = _I
+lib.dwt_hip_keep_largest.argtypes = [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P]
+lib.dwt_hip_keep_largest.restype = _I
+lib.dwt_hip_magnitude_batch.argtypes = [_P, _S, _I, _I, _S, _I, _I, _I, _P, _S, _I]
+lib.dwt_hip_magnitude_batch.restype = _I
+
+
+def keep_largest_batch(ptr, batch_stride, batch, channels, channel_stride, stride_x, size_x, size_y, keep, j_max=-1,
+                       scope=NTERM_FRAME):
+    """dwt_hip_keep_largest_batch: in every group of `channels` frames (host or device) the positions of the keep[g]
+    largest magnitudes stay, every other position in scope gets +0 in every channel.  `keep` is one number for every
+    group or a sequence of `batch` numbers.  -> (thr, kept): float32 and int32 host arrays, one entry per group."""
+    import numpy as np
+
+    n = max(batch, 0)
+    k = np.full(n, keep, dtype=np.int32) if np.isscalar(keep) else np.ascontiguousarray(keep, dtype=np.int32)
+    if k.size < n:
+        raise DwtError("dwt_hip_keep_largest_batch: %d keep counts for %d groups" % (k.size, batch))
+    thr, kept = np.zeros(n, dtype=np.float32), np.zeros(n, dtype=np.int32)
+    _check(lib.dwt_hip_keep_largest_batch(_addr(ptr), batch_stride, batch, channels, channel_stride, stride_x, size_x, size_y,
+                                          j_max, scope, k.ctypes.data, thr.ctypes.data, kept.ctypes.data),
+           "dwt_hip_keep_largest_batch")
+    return thr, kept
+
+
+def keep_largest(ptr, stride_x, stride_y, size_x, size_y, keep, j_max=-1, scope=NTERM_FRAME):
+    """dwt_hip_keep_largest: one frame of one channel with any element stride -> (thr, kept)."""
+    thr, kept = C.c_float(0), C.c_int(0)
+    _check(lib.dwt_hip_keep_largest(_addr(ptr), stride_x, stride_y, size_x, size_y, j_max, scope, keep, C.addressof(thr),
+                                    C.addressof(kept)), "dwt_hip_keep_largest")
+    return thr.value, kept.value
+
+
+def magnitude_batch(ptr, batch_stride, batch, channels, channel_stride, stride_x, size_x, size_y, map_ptr, map_batch_stride,
+                    map_stride_x):
+    """dwt_hip_magnitude_batch: the magnitude map of every group -> map_ptr (where the frames lie: host or device), one
+    launch; the frames are only read."""
+    _check(lib.dwt_hip_magnitude_batch(_addr(ptr), batch_stride, batch, channels, channel_stride, stride_x, size_x, size_y,
+                                       _addr(map_ptr), map_batch_stride, map_stride_x), "dwt_hip_magnitude_batch")
+
+
 # ---- stationary wavelet transform of rows (include/libdwt_hip.h, include/swt.h; DESIGN.md s13) -------------------------
 SWT_MAX_LEVELS = 24
 lib.dwt_hip_swt1d_batch.argtypes = [_I, _P, _S, _S, _I, _I, _I, _P, _P, _I, _S, _S]

@@ -53,10 +53,11 @@ struct Ctx {
 	Buf swt_ws;  // SWT level by level: the L chain's two dense images (dwt_backend_swt.hip); 2-D: the LL chain and the passes' Lr, Hr (dwt_backend_swt2d.hip)
 	Buf cond_ws; // row conditioning: per-row medians, extrema, centres, moves, records (dwt_backend_condition.hip)
 	Buf band_ws; // band operators: the per-image operator tables of a batch (dwt_backend_bandops.hip)
+	Buf nterm_ws; // N-term approximation: ranks, select histograms, records (dwt_backend_nterm.hip)
 	// every device scratch buffer above: a new one is declared there, listed here, and named nowhere else for freeing
 	auto bufs()
 	{
-		return std::array{&stage_img, &ll[0], &ll[1], &frame_a, &frame_b, &vol_out, &vol_host[0], &vol_host[1], &eaw_w, &eaw_ll[0], &eaw_ll[1], &feat_ws, &swt_ws, &cond_ws, &band_ws};
+		return std::array{&stage_img, &ll[0], &ll[1], &frame_a, &frame_b, &vol_out, &vol_host[0], &vol_host[1], &eaw_w, &eaw_ll[0], &eaw_ll[1], &feat_ws, &swt_ws, &cond_ws, &band_ws, &nterm_ws};
 	}
 	hipEvent_t dl_ev[8] = {}; // strip events of the host downloads (dwt_host_xfer.hip), created once
 	hipEvent_t switch_ev = nullptr; // dwt_hip_set_stream: orders a newly set stream behind the old one's work

@@ -381,6 +381,34 @@ struct BandOpsArgs {
 };
 hipError_t launch_band_ops(const BandOpsArgs &a, hipStream_t s);
 
+// N-term approximation (dwt_nterm.hip): keep the coefficients of the n largest magnitudes of every group
+// of 1 .. 4 dense frames, zero the rest.  The key of a position is the uint32 image of its float magnitude (sign bit 0:
+// unsigned order is float order); a radix select over 11 + 10 + 10 bits finds the key of descending rank n, one
+// histogram launch per digit, and the apply launch zeroes what lies below it.  Per group the workspace holds
+// NTERM_HIST counters (the three digits' histograms one after the other, cleared before the call) and NTERM_REC words:
+// digit and remaining rank after the first and after the second narrowing, then the threshold's bits and the kept count.
+constexpr int NTERM_MAX_CH = 4;
+constexpr int NTERM_BINS0 = 2048, NTERM_BINS1 = 1024, NTERM_BINS2 = 1024, NTERM_HIST = NTERM_BINS0 + NTERM_BINS1 + NTERM_BINS2;
+constexpr int NTERM_REC = 8;
+constexpr int NTERM_SLAB = 16384; // elements of one channel per slab of rows, about
+struct NtermArgs {
+	char *img;                    // channel c of group g at img + g*bstride + c*cstride, rows `pitch` bytes apart
+	long pitch, bstride, cstride; // bytes
+	int batch, channels, w, h;
+	int lx, ly;           // positions x < lx && y < ly are outside the scope (0, 0: the whole frame is inside)
+	int slab_rows, slabs; // rows per slab, slabs per group
+	int bpg;              // workgroups per group: workgroup i walks slabs i % bpg, i % bpg + bpg, .. of group i / bpg
+	int vec;              // every base, pitch and stride is a multiple of 16 bytes: whole quads as 16-byte accesses
+	const unsigned *rank; // per group: the descending rank asked for, 1 .. positions in scope
+	unsigned *hist;       // batch * NTERM_HIST
+	unsigned *rec;        // batch * NTERM_REC
+	char *map;            // magnitude launch only: the map of group g at map + g*map_bstride
+	long map_pitch, map_bstride;
+};
+hipError_t launch_nterm_hist(const NtermArgs &a, int pass, hipStream_t s); // pass 0, 1, 2
+hipError_t launch_nterm_apply(const NtermArgs &a, hipStream_t s);
+hipError_t launch_nterm_magnitude(const NtermArgs &a, hipStream_t s);
+
 // Conditioning of rows (dwt_condition.hip): median shift, centring, range scaling.  The bits are those of
 // enum dwt_hip_rows_op; a row's record is 4 ints: net offset, moves made, last centre found (-1: none), SCALE skipped it.
 enum CondOp { kCondMedShift = 1, kCondCenter = 2, kCondScale = 4 };
