@@ -60,6 +60,18 @@ void dwt_cdf53_2i_i(void *ptr, int stride_x, int stride_y,
 	int size_o_big_x, int size_o_big_y, int size_i_big_x, int size_i_big_y,
 	int j_max, int decompose_one, int zero_padding);
 
+/* EXTENSION: reversible int16 CDF 5/3 in JPEG 2000 order (ITU-T T.800 F.3.8.1 reversible 1-D filtering, F.3.2 2D_SD:
+ * every level lifts its columns, then its rows; the inverse the rows, then the columns).  The reference has this
+ * transform only as a single-level core (examples/cores/cores.c: cores2f_cdf53_v2x2_i16 / cores2i_cdf53_v2x2_i16); these
+ * entries take the parameter list of dwt_cdf53_2f_i / dwt_cdf53_2i_i, int16_t samples (stride_y >= 2), the same Mallat
+ * layout and j_max rules.  The inverse restores every int16 image bit for bit.  DESIGN.md s20. */
+void dwt_cdf53_2f_i16(void *ptr, int stride_x, int stride_y,
+	int size_o_big_x, int size_o_big_y, int size_i_big_x, int size_i_big_y,
+	int *j_max_ptr, int decompose_one, int zero_padding);
+void dwt_cdf53_2i_i16(void *ptr, int stride_x, int stride_y,
+	int size_o_big_x, int size_o_big_y, int size_i_big_x, int size_i_big_y,
+	int j_max, int decompose_one, int zero_padding);
+
 /* Float CDF 5/3.  src/libdwt.h:722, 1053. */
 void dwt_cdf53_2f_s(void *ptr, int stride_x, int stride_y,
 	int size_o_big_x, int size_o_big_y, int size_i_big_x, int size_i_big_y,
@@ -236,6 +248,8 @@ void dwt_util_test_image_fill_i(void *ptr, int stride_x, int stride_y, int size_
 /* the other synthetic patterns, selected by `type` (src/libdwt.h:1438, 1421; src/libdwt.c:1201-1244) */
 void dwt_util_test_image_fill2_s(void *ptr, int stride_x, int stride_y, int size_i_big_x, int size_i_big_y, int rand, int type);
 void dwt_util_test_image_fill2_i(void *ptr, int stride_x, int stride_y, int size_i_big_x, int size_i_big_y, int rand, int type);
+/* the int patterns (types 0 and 2) in int16_t samples, src/libdwt.h:1325 */
+void dwt_util_test_image_fill2_i16(void *ptr, int stride_x, int stride_y, int size_i_big_x, int size_i_big_y, int rand, int type);
 /* src/libdwt.c:21154, 21235 */
 void dwt_util_copy_s(const void *src, void *dst, int stride_x, int stride_y, int size_i_big_x, int size_i_big_y);
 void dwt_util_copy_i(const void *src, void *dst, int stride_x, int stride_y, int size_i_big_x, int size_i_big_y);
@@ -246,6 +260,8 @@ int dwt_util_compare_i(void *ptr1, void *ptr2, int stride_x, int stride_y, int s
 /* log-magnitude view of a transform, src/libdwt.c:21075, 21020 */
 void dwt_util_conv_show_s(const void *src, void *dst, int stride_x, int stride_y, int size_i_big_x, int size_i_big_y);
 void dwt_util_conv_show_i(const void *src, void *dst, int stride_x, int stride_y, int size_i_big_x, int size_i_big_y);
+/* |x| of int16_t samples, stored as int16_t, src/libdwt.h:2460 */
+void dwt_util_conv_show_i16(const void *src, void *dst, int stride_x, int stride_y, int size_i_big_x, int size_i_big_y);
 /* double-precision twins (examples/simple-double): pattern with 0-based x, y
  * (src/libdwt.c:1112-1125), copy, compare within 1e-6 absolute, view, PGM writer */
 void dwt_util_test_image_fill_d(void *ptr, int stride_x, int stride_y, int size_i_big_x, int size_i_big_y, int rand);
@@ -259,6 +275,9 @@ int dwt_util_save_to_pgm_s(const char *filename, float max_value, const void *pt
 	int size_i_big_x, int size_i_big_y);
 int dwt_util_save_to_pgm_i(const char *filename, int max_value, const void *ptr, int stride_x, int stride_y,
 	int size_i_big_x, int size_i_big_y);
+/* int16_t samples, src/libdwt.h:1765 */
+int dwt_util_save_to_pgm_i16(const char *filename, int16_t max_value, const void *ptr, int stride_x, int stride_y,
+	int size_i_big_x, int size_i_big_y);
 /* src/libdwt.h:1799 (src/libdwt.c:19727-19792): log(1 + |x|) of every sample (dwt_util_conv_show_s), scaled
  * to the largest of them, as an ASCII PGM; returns 0 */
 int dwt_util_save_log_to_pgm_s(const char *path, const void *ptr, int stride_x, int stride_y, int size_x, int size_y);
@@ -267,6 +286,9 @@ int dwt_util_save_log_to_pgm_s(const char *path, const void *ptr, int stride_x, 
 int dwt_util_load_from_pgm_s(const char *filename, float max_value, void **pptr, int *pstride_x, int *pstride_y,
 	int *psize_x, int *psize_y);
 int dwt_util_load_from_pgm_i(const char *filename, int max_value, void **pptr, int *pstride_x, int *pstride_y,
+	int *psize_x, int *psize_y);
+/* int16_t samples (stride_y 2), src/libdwt.h:1936 */
+int dwt_util_load_from_pgm_i16(const char *filename, int16_t max_value, void **pptr, int *pstride_x, int *pstride_y,
 	int *psize_x, int *psize_y);
 /* text matrices ("MAT": one row per line, comma separated), src/libdwt.h:1829, 1909, 1951 */
 int dwt_util_save_to_mat_s(const char *path, const void *ptr, int size_x, int size_y, int stride_x, int stride_y);

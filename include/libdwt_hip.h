@@ -49,6 +49,10 @@ enum dwt_hip_wavelet {
 	DWT_HIP_CDF97_D = 3, /* double CDF 9/7: dwt_cdf97_2f_d / dwt_cdf97_2i_d (src/libdwt.c:12451, 16884) */
 	DWT_HIP_CDF53_D = 4, /* double CDF 5/3: dwt_cdf53_2f_d / dwt_cdf53_2i_d (src/libdwt.c:12535, 16962) */
 	DWT_HIP_CDF97_I = 5, /* int32 fixed-point CDF 9/7: dwt_cdf97_2f_i / dwt_cdf97_2i_i (src/libdwt.c:16387, 18219) */
+	/* (7 stays unassigned: earlier releases document it as an unknown id that every entry refuses) */
+	DWT_HIP_CDF53_I16 = 8, /* reversible int16 CDF 5/3 in JPEG 2000 order (columns before rows, ITU-T T.800 F.3.2 / F.3.8.1):
+	                          dwt_cdf53_2f_i16 / dwt_cdf53_2i_i16; 2-byte elements; dwt_hip_transform2d, _transform2d_batch,
+	                          dwt_hip_alloc_batch and dwt_hip_tune only */
 	DWT_HIP_INTERP53_S = 6 /* float interpolating 5/3 (CDF 5/3 predict step, no update): dwt_interp53_2f_s / dwt_interp53_2i_s
 	                          (src/libdwt.c:16801, 18457), 1-D dwt_interp53_1f_s / _1i_s (:16166, :15900); not in the
 	                          interleaved layout */

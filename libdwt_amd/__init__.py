@@ -28,6 +28,7 @@ LIB_PATH = os.environ.get("DWT_HIP_LIB") or os.path.join(_HERE, "libdwt_hip.so")
 
 CDF97_S, CDF53_I, CDF53_S, CDF97_D, CDF53_D, CDF97_I = 0, 1, 2, 3, 4, 5
 INTERP53_S = 6  # interpolating 5/3 float: the CDF 5/3 predict step alone (DWT_HIP_INTERP53_S)
+CDF53_I16 = 8  # reversible int16 CDF 5/3 in JPEG 2000 order, 2-byte elements (DWT_HIP_CDF53_I16)
 
 
 class DwtError(RuntimeError):
@@ -55,7 +56,7 @@ for _n, _sig in (("dwt_cdf97_2f_s", _FWD), ("dwt_cdf97_2i_s", _INV), ("dwt_cdf97
                  ("dwt_cdf97_2i_s2", _INV2), ("dwt_cdf53_2f_i", _FWD), ("dwt_cdf53_2i_i", _INV),
                  ("dwt_cdf53_2f_s", _FWD), ("dwt_cdf53_2i_s", _INV), ("dwt_cdf97_2f_d", _FWD), ("dwt_cdf97_2i_d", _INV),
                  ("dwt_cdf53_2f_d", _FWD), ("dwt_cdf53_2i_d", _INV), ("dwt_cdf97_2f_i", _FWD), ("dwt_cdf97_2i_i", _INV),
-                 ("dwt_interp53_2f_s", _FWD), ("dwt_interp53_2i_s", _INV)):
+                 ("dwt_interp53_2f_s", _FWD), ("dwt_interp53_2i_s", _INV), ("dwt_cdf53_2f_i16", _FWD), ("dwt_cdf53_2i_i16", _INV)):
     getattr(lib, _n).argtypes = _sig
     getattr(lib, _n).restype = None
 
@@ -355,14 +356,29 @@ def dwt_interp53_2i_s(ptr, stride_x, stride_y, size_o_big_x, size_o_big_y, size_
          j_max, decompose_one, zero_padding, "dwt_interp53_2i_s")
 
 
+def dwt_cdf53_2f_i16(ptr, stride_x, stride_y, size_o_big_x, size_o_big_y, size_i_big_x, size_i_big_y,
+                     j_max=-1, decompose_one=0, zero_padding=0):
+    """Reversible int16 CDF 5/3 in JPEG 2000 order (columns before rows; int16 samples, stride_y >= 2).  An extension: the
+    reference has the transform as a core only (examples/cores/cores.c)."""
+    return _fwd(CDF53_I16, ptr, ptr, stride_x, stride_y, size_o_big_x, size_o_big_y, size_i_big_x, size_i_big_y,
+                j_max, decompose_one, zero_padding, "dwt_cdf53_2f_i16")
+
+
+def dwt_cdf53_2i_i16(ptr, stride_x, stride_y, size_o_big_x, size_o_big_y, size_i_big_x, size_i_big_y,
+                     j_max=-1, decompose_one=0, zero_padding=0):
+    """The inverse of dwt_cdf53_2f_i16: rows before columns; restores every int16 image bit for bit."""
+    _inv(CDF53_I16, ptr, ptr, stride_x, stride_y, size_o_big_x, size_o_big_y, size_i_big_x, size_i_big_y,
+         j_max, decompose_one, zero_padding, "dwt_cdf53_2i_i16")
+
+
 FORWARD = {"cdf97_s": dwt_cdf97_2f_s, "cdf53_i": dwt_cdf53_2f_i, "cdf53_s": dwt_cdf53_2f_s,
            "cdf97_d": dwt_cdf97_2f_d, "cdf53_d": dwt_cdf53_2f_d, "cdf97_i": dwt_cdf97_2f_i,
-           "interp53_s": dwt_interp53_2f_s}
+           "interp53_s": dwt_interp53_2f_s, "cdf53_i16": dwt_cdf53_2f_i16}
 INVERSE = {"cdf97_s": dwt_cdf97_2i_s, "cdf53_i": dwt_cdf53_2i_i, "cdf53_s": dwt_cdf53_2i_s,
            "cdf97_d": dwt_cdf97_2i_d, "cdf53_d": dwt_cdf53_2i_d, "cdf97_i": dwt_cdf97_2i_i,
-           "interp53_s": dwt_interp53_2i_s}
+           "interp53_s": dwt_interp53_2i_s, "cdf53_i16": dwt_cdf53_2i_i16}
 WAVELET_ID = {"cdf97_s": CDF97_S, "cdf53_i": CDF53_I, "cdf53_s": CDF53_S, "cdf97_d": CDF97_D, "cdf53_d": CDF53_D,
-              "cdf97_i": CDF97_I, "interp53_s": INTERP53_S}
+              "cdf97_i": CDF97_I, "interp53_s": INTERP53_S, "cdf53_i16": CDF53_I16}
 
 
 # ---- interleaved (in-place lifting) layout ------------------------------------------------

@@ -355,7 +355,7 @@ int dwt_hip_transform2d(int wavelet, int inverse, const void *src, void *dst, in
 	if (!src || !dst || !j)
 		return fail("null pointer argument");
 	const int es = elem_size(w);
-	g_elems_are_32bit = (es == 4);
+	call_elems(es, {src, dst}, {(long)stride_x});
 	if (sox <= 0 || soy <= 0 || six < 0 || siy < 0 || six > sox || siy > soy)
 		return fail("bad sizes: outer %dx%d inner %dx%d", sox, soy, six, siy);
 	const Geom ge{sox, soy, six, siy};
@@ -391,6 +391,7 @@ int dwt_hip_transform2d(int wavelet, int inverse, const void *src, void *dst, in
 		return 1;
 	const long pitch = A.sx;
 	const Img B{(char *)g.frame_b.p, pitch, es};
+	call_elems(es, {A.p, B.p}, {pitch}); // (the transform runs on the staged images)
 	// B receives the result.  It starts as a copy of what the destination holds so
 	// that every element the reference leaves untouched keeps its value -- unless the call
 	// writes every element of the frame anyway (a dense frame, at least one level: no second
@@ -457,7 +458,7 @@ int dwt_hip_transform2d_batch(int wavelet, int inverse, const void *src, void *d
 	if (!wavelet_of(wavelet, &w))
 		return fail("unknown wavelet %d", wavelet);
 	const int es = elem_size(w);
-	g_elems_are_32bit = es == 4;
+	call_elems(es, {src, dst}, {(long)stride_x, (long)batch_stride});
 	if (!src || !dst || !j || batch < 1 || batch > 65535)
 		return fail("bad argument (batch must be 1..65535)");
 	if (!dwt_hip_is_device_pointer(src) || !dwt_hip_is_device_pointer(dst))
@@ -468,6 +469,17 @@ int dwt_hip_transform2d_batch(int wavelet, int inverse, const void *src, void *d
 		return fail("in-place batches are not supported; use distinct src and dst");
 	const Geom ge{size_x, size_y, size_x, size_y};
 	Img s{(char *)src, stride_x, es}, d{(char *)dst, stride_x, es};
+	if (g_i16_call == 1 && batch > 1) {
+		// int16 images that the fused sweeps do not take: the line passes, which run image by image
+		const int j_in = *j;
+		for (int b = 0; b < batch; b++) {
+			const Img sb{s.p + (size_t)b * batch_stride, stride_x, es}, db{d.p + (size_t)b * batch_stride, stride_x, es};
+			*j = j_in;
+			if (inverse ? inverse2d(w, sb, db, ge, *j, 0, 0, 1, 0, 0) : forward2d(w, sb, db, ge, j, 0, 0, 1, 0, 0))
+				return 1;
+		}
+		return 0;
+	}
 	if (!inverse && (*j < 0 || *j >= 2) && place_ll_scratch(w, s, d, ge, *j, batch, (long)batch_stride, (long)batch_stride))
 		return 1;
 	return inverse ? inverse2d(w, s, d, ge, *j, 0, 0, batch, (long)batch_stride, (long)batch_stride)

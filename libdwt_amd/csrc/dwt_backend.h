@@ -122,6 +122,12 @@ struct Ctx {
 extern thread_local Ctx g;
 extern thread_local char g_err[512];
 extern thread_local bool g_elems_are_32bit; // set per call: the fused sweeps exist for 4-byte elements only
+// set with it by every call that takes a wavelet of any element size (call_elems): 0 -- no int16 call --, 1 -- an int16 call
+// whose levels all take the exact line passes --, 2 -- an int16 call on the fused sweeps of dwt_sweep2d_i16.hip
+extern thread_local int g_i16_call;
+// The route rule of the int16 5/3: the fused sweeps take images whose bases, pitches and batch strides are all multiples
+// of 4 bytes (a lane's own bytes of a row are then dword-aligned); anything else takes the line passes.
+void call_elems(int es, std::initializer_list<const void *> ptrs, std::initializer_list<long> strides);
 
 int fail(const char *fmt, ...);
 // the tail of a kernel launch that this context counts (stat_launches): 0, or fail("<family> <what> launch failed: ...")
@@ -136,7 +142,8 @@ inline bool overlap(const void *a, size_t na, const void *b, size_t nb)
 }
 
 // The public wavelet id of a C-ABI call (enum dwt_hip_wavelet) as the internal enum Wavelet: ids 0..5 are the same
-// numbers, DWT_HIP_INTERP53_S (6) is kInterp53S -- internal 6 is the contracted float 9/7.  false: no such public id.
+// numbers, DWT_HIP_INTERP53_S (6) is kInterp53S -- internal 6 is the contracted float 9/7 --, DWT_HIP_CDF53_I16 (8) is
+// kCdf53I16.  false: no such public id.
 static inline bool wavelet_of(int id, Wavelet *w)
 {
 	if (id >= 0 && id <= 5) {
@@ -145,6 +152,10 @@ static inline bool wavelet_of(int id, Wavelet *w)
 	}
 	if (id == DWT_HIP_INTERP53_S) {
 		*w = kInterp53S;
+		return true;
+	}
+	if (id == DWT_HIP_CDF53_I16) {
+		*w = kCdf53I16;
 		return true;
 	}
 	return false;
@@ -167,7 +178,7 @@ inline int ceil_log2(int x)                                               // src
 }
 inline long align_up(long v, long a) { return (v + a - 1) / a * a; }
 
-// A device image: element (y,x) at p + y*sx + x*es (dense elements of es = 4 or 8 bytes).
+// A device image: element (y,x) at p + y*sx + x*es (dense elements of es = 2, 4 or 8 bytes).
 struct Img {
 	char *p;
 	long sx;    // row pitch in bytes

@@ -164,7 +164,7 @@ int generic_pass(Wavelet w, bool inverse, bool rows, Img in, Img out, int frame_
 {
 	if (n_lines <= 0 || N <= 0)
 		return 0;
-	if (N == 1 && (w == kCdf53I || w == kCdf97I)) {
+	if (N == 1 && (w == kCdf53I || w == kCdf97I || w == kCdf53I16)) {
 		// the int kernels leave a lone sample as it is (src/libdwt.c:10961); out of place that
 		// still means the samples have to arrive in the destination
 		if (in.p != out.p)
@@ -258,12 +258,28 @@ int ensure_ll(const Geom &ge, int batch, int es)
 }
 
 thread_local bool g_elems_are_32bit = true;
+thread_local int g_i16_call = 0;
+
+void call_elems(int es, std::initializer_list<const void *> ptrs, std::initializer_list<long> strides)
+{
+	g_elems_are_32bit = es == 4;
+	g_i16_call = 0;
+	if (es != 2)
+		return;
+	bool ok = true;
+	for (const void *p : ptrs)
+		ok = ok && (uintptr_t)p % 4 == 0;
+	for (long s : strides)
+		ok = ok && s % 4 == 0;
+	g_i16_call = ok ? 2 : 1;
+}
 
 // the fused sweeps exist for the 32-bit types and, since round 2, for the double-precision wavelets
-// (dwt_sweep2d_d.hip; option "fused_d" = 0 sends those back to the exact line passes)
+// (dwt_sweep2d_d.hip; option "fused_d" = 0 sends those back to the exact line passes); the int16 5/3 has its own
+// (dwt_sweep2d_i16.hip) for the calls that call_elems found aligned
 bool level_fused_ok(const Geom &ge, int j)
 {
-	return !g.force_generic && (g_elems_are_32bit || g.fused_d) && ge.Wi(j) == ge.Wo(j) && ge.Hi(j) == ge.Ho(j) && ge.Wo(j) >= 2 &&
+	return !g.force_generic && (g_elems_are_32bit || (g_i16_call ? g_i16_call == 2 : g.fused_d != 0)) && ge.Wi(j) == ge.Wo(j) && ge.Hi(j) == ge.Ho(j) && ge.Wo(j) >= 2 &&
 		ge.Ho(j) >= 2;
 }
 // Levels 0 and 1 of a forward transform in ONE launch (launch_fwd01: overlapped tiles, level 0's LL band never written):
@@ -305,7 +321,8 @@ int forward2d(Wavelet w, Img src, Img dst, const Geom &ge, int *jp, int decompos
 	if (J == 0)
 		return 0;
 	const int es = elem_size(w);
-	const bool dbl = es == 8;
+	const bool dbl = es == 8, i16 = es == 2;
+	const bool cols_first = i16; // the int16 5/3 lifts the columns of a level before its rows (2D_SD)
 	if (ensure_ll(ge, batch, es))
 		return 1;
 
@@ -317,7 +334,7 @@ int forward2d(Wavelet w, Img src, Img dst, const Geom &ge, int *jp, int decompos
 	auto carriers_from = [&](int j0) {
 		int n = 0;
 		for (int j = j0; j < J && level_fused_ok(ge, j); j++)
-			n += !dbl && sweep_ride_ok(g.tune, ge.Wo(j), ge.Ho(j), batch, false);
+			n += es == 4 && sweep_ride_ok(g.tune, ge.Wo(j), ge.Ho(j), batch, false);
 		return n;
 	};
 	for (int j = 0; j < J; j++) {
@@ -373,9 +390,9 @@ int forward2d(Wavelet w, Img src, Img dst, const Geom &ge, int *jp, int decompos
 				a.ll_bstride = a.ll_pitch * ge.Ho(jl + 1);
 			}
 			SweepTuning tune = g.tune;
-			if (!dbl && tune.tile_pairs <= 0)
+			if (es == 4 && tune.tile_pairs <= 0)
 				apply_tile_choice(pair ? tuned_tile_pairs01(w, a) : tuned_tile_pairs(w, a), &tune, false); // (nothing measured: the launcher's own rule)
-			if (ride.on && ride.next < ride.total && !dbl && sweep_ride_ok(tune, Wo, Ho, batch, false)) {
+			if (ride.on && ride.next < ride.total && es == 4 && sweep_ride_ok(tune, Wo, Ho, batch, false)) {
 				a.ride = &ride.r;
 				a.ride_lo = ride.next;
 				a.ride_hi = ride.next + ride.share((size_t)Wo * Ho * es, carriers_from(j + 1));
@@ -384,6 +401,7 @@ int forward2d(Wavelet w, Img src, Img dst, const Geom &ge, int *jp, int decompos
 			prof_before(j);
 			hipError_t e = pair ? launch_fwd01(a, tune, g.stream)
 			             : dbl  ? launch_fwd_level_d(w, a, tune, g.stream)
+			             : i16  ? launch_fwd_level_i16(w, a, tune, g.stream)
 			                    : launch_fwd_level((g.fma && w == kCdf97S) ? kCdf97SFma : w, a, tune, g.stream);
 			prof_after(j);
 			if (e != hipSuccess)
@@ -393,12 +411,19 @@ int forward2d(Wavelet w, Img src, Img dst, const Geom &ge, int *jp, int decompos
 				// quadrant too when it was written here (in line: on a side stream beside the deeper
 				// levels it measured 8-10 us slower, profiles/archive/r03_entries_summary.md)
 				const Rect rc[3] = {{Wd, 0, Wd, 0, Wo - Wd, Ho}, {0, Hd, 0, Hd, Wd, Ho - Hd}, {0, 0, 0, 0, last ? Wd : 0, Hd}};
-				ride.r = make_copy_rects(dst, hdst, rc, 3, 3);
-				ride.total = copy_rects_plan(&ride.r);
-				ride.next = 0;
-				ride.on = g.ride_copy && ride.total > 0 && carriers_from(j + 1) > 0;
-				if (!ride.on && copy_rects_on(g.stream, dst, hdst, rc, 3))
-					return 1;
+				if (i16) {
+					// (the rectangle kernel moves whole dwords: 2-byte elements go by plain 2-D copies)
+					for (const Rect &r : rc)
+						if (copy_rect(dst, r.dx, r.dy, hdst, r.sx, r.sy, r.w, r.h))
+							return 1;
+				} else {
+					ride.r = make_copy_rects(dst, hdst, rc, 3, 3);
+					ride.total = copy_rects_plan(&ride.r);
+					ride.next = 0;
+					ride.on = g.ride_copy && ride.total > 0 && carriers_from(j + 1) > 0;
+					if (!ride.on && copy_rects_on(g.stream, dst, hdst, rc, 3))
+						return 1;
+				}
 			}
 			ll_in = ll_out;
 			cur = dst;
@@ -427,19 +452,25 @@ int forward2d(Wavelet w, Img src, Img dst, const Geom &ge, int *jp, int decompos
 			if (grow(g.stage_img, (size_t)dst.sx * Ho))
 				return 1;
 			const Img S{(char *)g.stage_img.p, dst.sx, dst.es};
-			if (generic_pass(w, false, true, cur, S, Wo, Ho, Ho, Wi, Wd) || generic_pass(w, false, false, S, dst, Wo, Ho, Wo, Hi, Hd))
+			if (cols_first ? (generic_pass(w, false, false, cur, S, Wo, Ho, Wo, Hi, Hd) || generic_pass(w, false, true, S, dst, Wo, Ho, Ho, Wi, Wd))
+			               : (generic_pass(w, false, true, cur, S, Wo, Ho, Ho, Wi, Wd) || generic_pass(w, false, false, S, dst, Wo, Ho, Wo, Hi, Hd)))
 				return 1;
 			cur = dst;
-		} else {
-			if (!skip_single(w) || Wo > 1) {
-				if (generic_pass(w, false, true, cur, dst, Wo, Ho, Ho, Wi, Wd))
-					return 1;
-				cur = dst; // src/libdwt.c:12709
-			}
-			if (!skip_single(w) || Ho > 1) {
-				if (generic_pass(w, false, false, cur, dst, Wo, Ho, Wo, Hi, Hd))
-					return 1;
-				cur = dst; // src/libdwt.c:12742
+		} else
+		for (int pass = 0; pass < 2; pass++) {
+			const bool rows = cols_first ? (pass == 1) : (pass == 0);
+			if (rows) {
+				if (!skip_single(w) || Wo > 1) {
+					if (generic_pass(w, false, true, cur, dst, Wo, Ho, Ho, Wi, Wd))
+						return 1;
+					cur = dst; // src/libdwt.c:12709
+				}
+			} else {
+				if (!skip_single(w) || Ho > 1) {
+					if (generic_pass(w, false, false, cur, dst, Wo, Ho, Wo, Hi, Hd))
+						return 1;
+					cur = dst; // src/libdwt.c:12742
+				}
 			}
 		}
 		if (zero_padding) {
@@ -468,10 +499,10 @@ int inverse2d(Wavelet w, Img src, Img dst, const Geom &ge, int j_max, int decomp
 		return 0;
 	}
 	const int es = elem_size(w);
-	const bool dbl = es == 8;
+	const bool dbl = es == 8, i16 = es == 2;
 	if (ensure_ll(ge, batch, es))
 		return 1;
-	const bool cols_first = (w == kCdf53I || w == kCdf97I); // the int inverses undo columns first
+	const bool cols_first = (w == kCdf53I || w == kCdf97I); // the int32 inverses undo columns first (the int16 5/3 rows: the mirror of its forward)
 
 	// reconstruction level j consumes the subbands of size ceil(.,j) and produces the
 	// band of size ceil(.,j-1); it is fused when that PRODUCED frame is dense and >= 2
@@ -484,7 +515,7 @@ int inverse2d(Wavelet w, Img src, Img dst, const Geom &ge, int j_max, int decomp
 	// In place (one image), every level fused: the final level would overwrite subbands it still reads, so they are
 	// moved aside first -- a copy that depends on none of the deeper levels and rides along with them (RideCopy)
 	RideCopy ride;
-	if (src.p == dst.p && batch == 1 && J >= 2 && g.ride_copy && !dbl) {
+	if (src.p == dst.p && batch == 1 && J >= 2 && g.ride_copy && es == 4) {
 		bool all = true;
 		int carriers = 0;
 		for (int j = J; j >= 1; j--)
@@ -542,6 +573,11 @@ int inverse2d(Wavelet w, Img src, Img dst, const Geom &ge, int j_max, int decomp
 						// (most of it went with the deeper levels' launches; what is left goes now)
 						if (ride.flush())
 							return 1;
+					} else if (i16) {
+						// (the rectangle kernel moves whole dwords: 2-byte elements go by plain 2-D copies)
+						for (const Rect &r : rc)
+							if (copy_rect(st, r.dx, r.dy, cur, r.sx, r.sy, r.w, r.h))
+								return 1;
 					} else if (copy_rects_on(g.stream, st, cur, rc, 3, /* temporal both ways: the final level reads the staged subbands (233 against 237 us) */ 0))
 						return 1;
 					a.in_h = st.p;
@@ -560,7 +596,7 @@ int inverse2d(Wavelet w, Img src, Img dst, const Geom &ge, int j_max, int decomp
 			SweepTuning tune = g.tune;
 			if (tune.inv_pairs <= 0)
 				tune.inv_pairs = src.p == dst.p ? 32 : 16; // (in place: 32 pairs, 230.7 against 234.0 us; scripts/r06/inv_call_ab.py)
-			if (!dbl && tune.tile_pairs <= 0)
+			if (es == 4 && tune.tile_pairs <= 0)
 				apply_tile_choice(tuned_tile_pairs(w, a), &tune, true);
 			if (ride.on && !last && ride.next < ride.total && sweep_ride_ok(tune, Wo, Ho, batch, true)) {
 				int after = 0;
@@ -573,6 +609,7 @@ int inverse2d(Wavelet w, Img src, Img dst, const Geom &ge, int j_max, int decomp
 			}
 			prof_before(j - 1);
 			hipError_t e = dbl ? launch_inv_level_d(w, a, tune, g.stream)
+			             : i16 ? launch_inv_level_i16(w, a, tune, g.stream)
 			                   : launch_inv_level((g.fma && w == kCdf97S) ? kCdf97SFma : w, a, tune, g.stream);
 			prof_after(j - 1);
 			if (e != hipSuccess)

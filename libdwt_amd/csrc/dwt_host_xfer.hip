@@ -89,6 +89,8 @@ static int host_upload(const void *hp, int stride_x, int stride_y, int es, int w
 				char *out = pin + (long)y * pitch;
 				if (stride_y == es)
 					memcpy(out, row, (size_t)w * es);
+				else if (es == 2)
+					gather_row<2>(out, row, w, stride_y);
 				else if (es == 4)
 					gather_row<4>(out, row, w, stride_y);
 				else
@@ -135,6 +137,8 @@ static int host_download(void *hp, int stride_x, int stride_y, int es, int w, in
 				const char *in = pin + (long)y * pitch;
 				if (stride_y == es)
 					memcpy(row, in, (size_t)w * es);
+				else if (es == 2)
+					scatter_row<2>(row, in, w, stride_y);
 				else if (es == 4)
 					scatter_row<4>(row, in, w, stride_y);
 				else

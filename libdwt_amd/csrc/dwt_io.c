@@ -39,11 +39,11 @@ static int pgm_skip(FILE *f)
 	}
 }
 
-/* P2 header + samples; is_float selects the element type.  Return codes as in the
+/* P2 header + samples; is_float selects the element type, es its size (2: int16_t samples, src/libdwt.c:19626).  Return codes as in the
  * reference (src/libdwt.c:19426-19523 float, :19525-19622 int): 1 open, 2 header,
  * 3 depth, 4 data, 5 sample out of range. */
 static int load_pgm(const char *filename, int is_float, float max_s, int max_i, void **pptr, int *pstride_x, int *pstride_y,
-	int *psize_x, int *psize_y)
+	int *psize_x, int *psize_y, int es)
 {
 	FILE *f = fopen(filename, "r");
 	if (!f) {
@@ -78,7 +78,7 @@ static int load_pgm(const char *filename, int is_float, float max_s, int max_i, 
 		fclose(f);
 		return 2;
 	}
-	*pstride_y = 4;
+	*pstride_y = es;
 	*pstride_x = dwt_util_get_opt_stride(*pstride_y * *psize_x);
 	dwt_util_alloc_image(pptr, *pstride_x, *pstride_y, *psize_x, *psize_y);
 	for (int y = 0; y < *psize_y; y++)
@@ -98,6 +98,9 @@ static int load_pgm(const char *filename, int is_float, float max_s, int max_i, 
 			if (is_float) {
 				const float v = max_s * val / depth; /* :19514 */
 				memcpy(px(*pptr, y, x, *pstride_x, *pstride_y), &v, 4);
+			} else if (es == 2) {
+				const int16_t v = (int16_t)(max_i * val / depth); /* :19718 */
+				memcpy(px(*pptr, y, x, *pstride_x, *pstride_y), &v, 2);
 			} else {
 				const int v = max_i * val / depth; /* :19613 */
 				memcpy(px(*pptr, y, x, *pstride_x, *pstride_y), &v, 4);
@@ -110,13 +113,19 @@ static int load_pgm(const char *filename, int is_float, float max_s, int max_i, 
 int dwt_util_load_from_pgm_s(const char *filename, float max_value, void **pptr, int *pstride_x, int *pstride_y,
 	int *psize_x, int *psize_y)
 {
-	return load_pgm(filename, 1, max_value, 0, pptr, pstride_x, pstride_y, psize_x, psize_y);
+	return load_pgm(filename, 1, max_value, 0, pptr, pstride_x, pstride_y, psize_x, psize_y, 4);
 }
 
 int dwt_util_load_from_pgm_i(const char *filename, int max_value, void **pptr, int *pstride_x, int *pstride_y,
 	int *psize_x, int *psize_y)
 {
-	return load_pgm(filename, 0, 0.f, max_value, pptr, pstride_x, pstride_y, psize_x, psize_y);
+	return load_pgm(filename, 0, 0.f, max_value, pptr, pstride_x, pstride_y, psize_x, psize_y, 4);
+}
+
+int dwt_util_load_from_pgm_i16(const char *filename, int16_t max_value, void **pptr, int *pstride_x, int *pstride_y,
+	int *psize_x, int *psize_y)
+{
+	return load_pgm(filename, 0, 0.f, max_value, pptr, pstride_x, pstride_y, psize_x, psize_y, 2);
 }
 
 /* ---- text matrices: one row per line, cells "%f" separated by ','

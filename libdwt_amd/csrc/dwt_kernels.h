@@ -10,9 +10,10 @@ enum Wavelet { kCdf97S = 0, kCdf53I = 1, kCdf53S = 2, kCdf97D = 3, kCdf53D = 4, 
 	kCdf97SFma = 6 /* internal: float 9/7 with contracted steps, option "fma" */,
 	kCdf53SNew = 7 /* internal: float 5/3 of dwt-simple.c (odd scale 1/zeta in float), interleaved layout only */,
 	kCdf97IIp = 8 /* internal: fixed-point int 9/7 of the interleaved in-place drivers (rounded terms added) */,
-	kInterp53S = 9 /* interpolating 5/3 float (public id DWT_HIP_INTERP53_S = 6): predict step only */ };
+	kInterp53S = 9 /* interpolating 5/3 float (public id DWT_HIP_INTERP53_S = 6): predict step only */,
+	kCdf53I16 = 10 /* reversible int16 5/3 in JPEG 2000 order (public id DWT_HIP_CDF53_I16 = 8): columns before rows */ };
 
-inline int elem_size(Wavelet w) { return (w == kCdf97D || w == kCdf53D) ? 8 : 4; }
+inline int elem_size(Wavelet w) { return (w == kCdf97D || w == kCdf53D) ? 8 : w == kCdf53I16 ? 2 : 4; }
 
 // Tuning knobs of the fused sweep kernels (set through dwt_hip_set_option).
 struct SweepTuning {
@@ -130,6 +131,10 @@ hipError_t launch_inv_level(Wavelet w, const InvLevelArgs &a, const SweepTuning 
 // the same two sweeps for the double-precision wavelets (dwt_sweep2d_d.hip); pitches in 8-byte ELEMENTS
 hipError_t launch_fwd_level_d(Wavelet w, const FwdLevelArgs &a, const SweepTuning &t, hipStream_t s);
 hipError_t launch_inv_level_d(Wavelet w, const InvLevelArgs &a, const SweepTuning &t, hipStream_t s);
+// the two sweeps of the int16 5/3 (dwt_sweep2d_i16.hip): pitches in 2-byte ELEMENTS; the images' bases and pitches are
+// multiples of 4 bytes (the driver sends everything else through the line passes)
+hipError_t launch_fwd_level_i16(Wavelet w, const FwdLevelArgs &a, const SweepTuning &t, hipStream_t s);
+hipError_t launch_inv_level_i16(Wavelet w, const InvLevelArgs &a, const SweepTuning &t, hipStream_t s);
 // true when launch_inv_level has a fused kernel for this wavelet
 bool have_fused_inverse(Wavelet w);
 
@@ -532,7 +537,7 @@ struct TfPlaneArgs {
 hipError_t launch_tf_plane_op(const TfPlaneArgs &a, hipStream_t s);
 
 // the strided gather / scatter (dwt_util_memcpy_stride_s / _i, src/system.c:102-164) on the device: w x h elements of
-// `es` bytes between a dense image (row pitch `pitch`) and one whose element (y, x) lies at y*sx + x*sy; all in BYTES
+// `es` (2, 4 or 8) bytes between a dense image (row pitch `pitch`) and one whose element (y, x) lies at y*sx + x*sy; all in BYTES
 hipError_t launch_strided_pack(void *dense, long pitch, const void *strided, long sx, long sy, int es, int w, int h, hipStream_t st);
 hipError_t launch_strided_unpack(void *strided, long sx, long sy, const void *dense, long pitch, int es, int w, int h, hipStream_t st);
 

@@ -124,6 +124,44 @@ struct Cdf53I {
 	static __device__ __forceinline__ T inv_single(T v) { return v; }
 };
 
+// Reversible int16 CDF 5/3 in JPEG 2000 order (ITU-T T.800 F.3.8.1 / F.3.2; the reference has it as a core only,
+// examples/cores/cores.c: cores2f_cdf53_v2x2_i16 / cores2i_cdf53_v2x2_i16, element step cdf53_vert_2x1_i16).  Samples are
+// STORED as int16 (S) and LIFTED in 32-bit lanes (T): every sum and shift is evaluated in int on sign-extended operands
+// and the result is truncated to 16 bits where the reference stores it -- sx() after every step, because the next step
+// reads the stored value.  Operands are within +-2^15, so no int sum here can overflow.
+// No end forms.  The int32 policy's special forms at a line end, where both taps are one sample m, are `-= m` for
+// `-= (m + m) >> 1` and `+= (m + 1) >> 1` for `+= (m + m + 2) >> 2`.  For |m| <= 2^15 the doubled terms are exact in int,
+// (2m) >> 1 == m, and (2m + 2) >> 2 == floor((m + 1) / 2) == (m + 1) >> 1: the reflected taps give the very same value
+// for EVERY 16-bit sample (the int32 forms differ only once 2m wraps, |m| >= 2^30).  Whole-sample reflection is the rule.
+// Order: a forward level lifts every column, then every row (2D_SD); the inverse every row, then every column.
+struct Cdf53I16 {
+	using T = int;   // register type
+	using S = short; // storage type
+	static constexpr bool kEndForms = false;
+	static constexpr int K = 2;
+	static constexpr bool kScaleSingle = false; // a line of one sample is left as it is
+	static constexpr bool kSkipSingleLine = false;
+	static constexpr bool kInvColsFirst = false; // inverse: rows, then columns -- the mirror of the forward
+	static constexpr bool kFwdColsFirst = true;
+	static __device__ __forceinline__ T sx(T v) { return (T)(S)v; }
+	static __device__ __forceinline__ T fwd_step(int s, T c, T l, T r)
+	{
+		return s == 0 ? sx(c - ((l + r) >> 1)) : sx(c + ((l + r + 2) >> 2));
+	}
+	static __device__ __forceinline__ T inv_step(int s, T c, T l, T r)
+	{
+		return s == 0 ? sx(c - ((l + r + 2) >> 2)) : sx(c + ((l + r) >> 1));
+	}
+	static __device__ __forceinline__ T fwd_scale(int, T v) { return v; }
+	static __device__ __forceinline__ T inv_scale(int, T v) { return v; }
+	static __device__ __forceinline__ T fwd_single(T v) { return v; }
+	static __device__ __forceinline__ T inv_single(T v) { return v; }
+};
+
+// the type a policy's samples have in memory: W::S where the policy names one, else its register type
+template <class W, class = void> struct storage_of { using type = typename W::T; };
+template <class W> struct storage_of<W, std::void_t<typename W::S>> { using type = typename W::S; };
+
 // Fixed-point int32 CDF 9/7 (src/libdwt.c:10901-10948, 11699-11746): no scaling; the
 // reference's own end formulas are the reflected ones (`a[N-2]+a[N-2]`), so reflection
 // is exact here for any input.

@@ -585,7 +585,7 @@ int dwt_hip_alloc_batch(int wavelet, int n_images, int size_x, int size_y, int l
 	if (!wavelet_of(wavelet, &w) || n_images < 1 || n_images > 65535 || size_x < 1 || size_y < 1 || !src_out || !dst_out)
 		return fail("dwt_hip_alloc_batch: bad argument");
 	const int es = elem_size(w);
-	g_elems_are_32bit = es == 4;
+	call_elems(es, {}, {(long)size_x * es, (long)size_x * es * size_y});
 	const size_t total = (size_t)size_x * es * size_y * n_images;
 	const Geom ge{size_x, size_y, size_x, size_y};
 	g_arena = ArenaStats();

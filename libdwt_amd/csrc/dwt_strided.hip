@@ -19,7 +19,9 @@ template <int ES, bool ALIGNED>
 static __device__ __forceinline__ void move_elem(char *d, const char *s)
 {
 	if constexpr (ALIGNED) {
-		if constexpr (ES == 4)
+		if constexpr (ES == 2)
+			*(unsigned short *)d = *(const unsigned short *)s;
+		else if constexpr (ES == 4)
 			*(unsigned *)d = *(const unsigned *)s;
 		else
 			*(unsigned long long *)d = *(const unsigned long long *)s;
@@ -65,12 +67,14 @@ static hipError_t strided_move_t(void *dense, long pitch, void *strided, long sx
 hipError_t launch_strided_pack(void *dense, long pitch, const void *strided, long sx, long sy, int es, int w, int h, hipStream_t st)
 {
 	return es == 8 ? strided_move_t<8, true>(dense, pitch, (void *)strided, sx, sy, w, h, st)
+	     : es == 2 ? strided_move_t<2, true>(dense, pitch, (void *)strided, sx, sy, w, h, st)
 	               : strided_move_t<4, true>(dense, pitch, (void *)strided, sx, sy, w, h, st);
 }
 
 hipError_t launch_strided_unpack(void *strided, long sx, long sy, const void *dense, long pitch, int es, int w, int h, hipStream_t st)
 {
 	return es == 8 ? strided_move_t<8, false>((void *)dense, pitch, strided, sx, sy, w, h, st)
+	     : es == 2 ? strided_move_t<2, false>((void *)dense, pitch, strided, sx, sy, w, h, st)
 	               : strided_move_t<4, false>((void *)dense, pitch, strided, sx, sy, w, h, st);
 }
 

@@ -44,6 +44,7 @@ __global__ __launch_bounds__(256) void k_line_pass(const char *__restrict__ src,
 	long line_stride, long elem_stride, int n_lines, int N, int hoff, int lanes_along_lines)
 {
 	using T = typename W::T;
+	using S = typename storage_of<W>::type; // (the int16 5/3 lifts in int what it keeps as short)
 	constexpr int K = W::K;
 	const int fast = blockIdx.x * blockDim.x + threadIdx.x;
 	const int slow = blockIdx.y;
@@ -54,8 +55,8 @@ __global__ __launch_bounds__(256) void k_line_pass(const char *__restrict__ src,
 		return;
 	const char *s = src + (long)line * line_stride;
 	char *d = dst + (long)line * line_stride;
-	auto ld = [&](int idx) { return *(const T *)(s + (long)idx * elem_stride); };
-	auto st = [&](int idx, T v) { *(T *)(d + (long)idx * elem_stride) = v; };
+	auto ld = [&](int idx) { return (T) * (const S *)(s + (long)idx * elem_stride); };
+	auto st = [&](int idx, T v) { *(S *)(d + (long)idx * elem_stride) = (S)v; };
 	const bool il = hoff < 0; // interleaved layout on both sides: L_k at 2k, H_k at 2k+1
 
 	if (N == 1) {
@@ -122,6 +123,7 @@ hipError_t launch_line_pass(Wavelet w, bool inverse, const void *src, void *dst,
 	case kCdf53SNew: return line_pass_t<Cdf53SNew>(inverse, src, dst, line_stride, elem_stride, n_lines, N, hoff, lanes_along_lines, s);
 	case kCdf97IIp: return line_pass_t<Cdf97IIp>(inverse, src, dst, line_stride, elem_stride, n_lines, N, hoff, lanes_along_lines, s);
 	case kInterp53S: return line_pass_t<Interp53S>(inverse, src, dst, line_stride, elem_stride, n_lines, N, hoff, lanes_along_lines, s);
+	case kCdf53I16: return line_pass_t<Cdf53I16>(inverse, src, dst, line_stride, elem_stride, n_lines, N, hoff, lanes_along_lines, s);
 	// the contracted variant exists for the fused sweeps only: line passes of such a call are exact
 	case kCdf97SFma: return line_pass_t<Cdf97S>(inverse, src, dst, line_stride, elem_stride, n_lines, N, hoff, lanes_along_lines, s);
 	}

@@ -305,7 +305,6 @@ int dwt_hip_tune(int wavelet, int inverse, const void *src, void *dst, size_t ba
 	if (!wavelet_of(wavelet, &w))
 		return fail("unknown wavelet %d", wavelet);
 	const int es = elem_size(w);
-	g_elems_are_32bit = es == 4;
 	if (!src || !dst || batch < 1 || batch > 65535)
 		return fail("dwt_hip_tune: bad argument (batch must be 1..65535)");
 	if (!dwt_hip_is_device_pointer(src) || !dwt_hip_is_device_pointer(dst))
@@ -314,8 +313,9 @@ int dwt_hip_tune(int wavelet, int inverse, const void *src, void *dst, size_t ba
 		batch_stride = (size_t)stride_x * size_y;
 	if ((stride_x % es) || stride_x < size_x * es || (batch_stride % es) || batch_stride < (size_t)stride_x * size_y)
 		return fail("bad strides");
-	if (src == dst)
-		return 0; // (the in-place entries stage level 0: nothing of theirs is measured)
+	call_elems(es, {src, dst}, {(long)stride_x, (long)batch_stride});
+	if (src == dst || g_i16_call == 1)
+		return 0; // (the in-place entries stage level 0, the line passes have no choices: nothing of theirs is measured)
 	const Geom ge{size_x, size_y, size_x, size_y};
 	return tune2d(w, inverse != 0, Img{(char *)src, stride_x, es}, Img{(char *)dst, stride_x, es}, ge, levels, batch, (long)batch_stride,
 		(long)batch_stride);

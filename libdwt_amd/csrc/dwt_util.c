@@ -270,6 +270,26 @@ void dwt_util_test_image_fill2_i(void *ptr, int stride_x, int stride_y, int size
 		}
 }
 
+/* src/libdwt.c:1170-1195, 1315: the same two patterns, every value narrowed to int16_t */
+void dwt_util_test_image_fill2_i16(void *ptr, int stride_x, int stride_y, int size_i_big_x, int size_i_big_y, int rand, int type)
+{
+	for (int y = 0; y < size_i_big_y; y++)
+		for (int x = 0; x < size_i_big_x; x++) {
+			int16_t v;
+			if (type == 0) {
+				const int xx = x >> rand;
+				v = (int16_t)(255 * (2 * xx * y) / (xx * xx + y * y + 1));
+			} else if (type == 2) {
+				v = (int16_t)((x ^ y) & 0xff);
+			} else {
+				dwt_util_log(LOG_ERR, "Unknown test image type.\n");
+				dwt_util_abort();
+				return;
+			}
+			memcpy(px(ptr, y, x, stride_x, stride_y), &v, sizeof v);
+		}
+}
+
 void dwt_util_copy_s(const void *src, void *dst, int stride_x, int stride_y, int size_i_big_x, int size_i_big_y)
 {
 	for (int y = 0; y < size_i_big_y; y++)
@@ -411,6 +431,18 @@ void dwt_util_conv_show_i(const void *src, void *dst, int stride_x, int stride_y
 		}
 }
 
+/* src/libdwt.c:21047: |x|, narrowed to int16_t like the reference (|-32768| stays -32768) */
+void dwt_util_conv_show_i16(const void *src, void *dst, int stride_x, int stride_y, int size_i_big_x, int size_i_big_y)
+{
+	for (int y = 0; y < size_i_big_y; y++)
+		for (int x = 0; x < size_i_big_x; x++) {
+			int16_t c;
+			memcpy(&c, px(src, y, x, stride_x, stride_y), sizeof c);
+			const int16_t v = (int16_t)abs(c);
+			memcpy(px(dst, y, x, stride_x, stride_y), &v, sizeof v);
+		}
+}
+
 /* src/libdwt.c:19727-19792: temp = conv_show(input); scale = the largest sample of temp (dwt_util_find_min_max_s,
  * :25426); ASCII PGM of temp against that scale */
 int dwt_util_save_log_to_pgm_s(const char *path, const void *ptr, int stride_x, int stride_y, int size_x, int size_y)
@@ -480,6 +512,42 @@ int dwt_util_save_to_pgm_i(const char *filename, int max_value, const void *ptr,
 		for (int x = 0; x < size_i_big_x; x++) {
 			const int p = ld_i(px(ptr, y, x, stride_x, stride_y));
 			int val = max_value ? (int)(255LL * p / max_value) : 0;
+			if (p > max_value) {
+				if (!incidents++)
+					dwt_util_log(LOG_WARN, "%s: Maximum pixel intensity exceeded (%i > %i) at (y=%i, x=%i). Such an incident will be reported only once.\n", __func__, p, max_value, y, x);
+				val = 255;
+			}
+			if (p < 0) {
+				if (!incidents++)
+					dwt_util_log(LOG_WARN, "%s: Minimum pixel intensity exceeded (%i < %i) at (y=%i, x=%i). Such an incident will be reported only once.\n", __func__, p, 0, y, x);
+				val = 0;
+			}
+			if (fprintf(f, "%i\n", val) < 0) {
+				dwt_util_log(LOG_WARN, "%s: error writing into file.\n", __func__);
+				fclose(f);
+				return 1;
+			}
+		}
+	fclose(f);
+	if (incidents)
+		dwt_util_log(LOG_WARN, "%s: %i errors ocurred while saving a file.\n", __func__, incidents);
+	return 0;
+}
+
+/* src/libdwt.c:19314 */
+int dwt_util_save_to_pgm_i16(const char *filename, int16_t max_value, const void *ptr, int stride_x, int stride_y,
+	int size_i_big_x, int size_i_big_y)
+{
+	FILE *f = fopen(filename, "w");
+	if (!f)
+		return 1;
+	fprintf(f, "P2\n%i %i\n%i\n", size_i_big_x, size_i_big_y, 255);
+	int incidents = 0;
+	for (int y = 0; y < size_i_big_y; y++)
+		for (int x = 0; x < size_i_big_x; x++) {
+			int16_t p;
+			memcpy(&p, px(ptr, y, x, stride_x, stride_y), sizeof p);
+			int val = max_value ? 255 * p / max_value : 0;
 			if (p > max_value) {
 				if (!incidents++)
 					dwt_util_log(LOG_WARN, "%s: Maximum pixel intensity exceeded (%i > %i) at (y=%i, x=%i). Such an incident will be reported only once.\n", __func__, p, max_value, y, x);
