@@ -459,7 +459,7 @@ int dwt_hip_transform2d_batch(int wavelet, int inverse, const void *src, void *d
 		return fail("unknown wavelet %d", wavelet);
 	const int es = elem_size(w);
 	call_elems(es, {src, dst}, {(long)stride_x, (long)batch_stride});
-	if (!src || !dst || !j || batch < 1 || batch > 65535)
+	if (!src || !dst || !j || batch < 1 || batch > 65535) // (past the cap: tests/test_hip_grid_limits.py)
 		return fail("bad argument (batch must be 1..65535)");
 	if (!dwt_hip_is_device_pointer(src) || !dwt_hip_is_device_pointer(dst))
 		return fail("batched transforms take device pointers");

@@ -58,7 +58,7 @@ void fill_walk(NtermArgs *a, int batch, int channels, int w, int h)
 	a->h = h;
 	a->slab_rows = std::max(1, NTERM_SLAB / std::max(w, 1));
 	a->slabs = (h + a->slab_rows - 1) / a->slab_rows;
-	// 8 workgroups on each of the 256 CUs, shared out over the groups; the rest by the workgroups' slab loop
+	// 8 workgroups on each of the 256 CUs, shared out over the groups; the rest by the workgroups' slab loop (past the cap: tests/test_hip_grid_limits.py)
 	a->bpg = std::max(1, std::min(a->slabs, (2048 + batch - 1) / std::max(batch, 1)));
 }
 

@@ -142,7 +142,7 @@ hipError_t launch_band_ops(const BandOpsArgs &a, hipStream_t s)
 	const long total = (long)a.batch * a.first[a.nslots];
 	if (total <= 0)
 		return hipSuccess;
-	const long cap = 256 * 64; // 64 workgroups on each of the 256 CUs, the rest by the grid-stride loop
+	const long cap = 256 * 64; // 64 workgroups on each of the 256 CUs, the rest by the grid-stride loop (past the cap: tests/test_hip_grid_limits.py)
 	k_band_ops<<<(unsigned)(total < cap ? total : cap), 256, 0, s>>>(a);
 	return hipGetLastError();
 }

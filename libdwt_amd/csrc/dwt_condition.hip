@@ -335,7 +335,7 @@ __global__ __launch_bounds__(256) void k_info_init(int *info, int n_lines)
 	}
 }
 
-dim3 grid2(int w, int h) { return dim3((w + 255) / 256, h < 16384 ? h : 16384); }
+dim3 grid2(int w, int h) { return dim3((w + 255) / 256, h < 16384 ? h : 16384); } // (past the cap: tests/test_hip_grid_limits.py)
 
 } // namespace
 

@@ -56,7 +56,7 @@ static inline int eaw_mode(float alpha) { return alpha == 0.f ? 0 : alpha == 1.f
 static inline dim3 eaw_grid(long threads)
 {
 	long b = (threads + 255) / 256;
-	return dim3((unsigned)(b < 65536 ? (b > 0 ? b : 1) : 65536));
+	return dim3((unsigned)(b < 65536 ? (b > 0 ? b : 1) : 65536)); // (past the cap: tests/test_hip_grid_limits.py)
 }
 
 // ---- the two wavelets ------------------------------------------------------------------------------------------------

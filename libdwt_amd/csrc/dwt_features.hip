@@ -300,7 +300,7 @@ hipError_t launch_feat_abs(void *p, long sx, long sy, int w, int h, hipStream_t 
 {
 	if (w <= 0 || h <= 0)
 		return hipSuccess;
-	dim3 grid((w + 255) / 256, h < 16384 ? h : 16384);
+	dim3 grid((w + 255) / 256, h < 16384 ? h : 16384); // (past the cap: tests/test_hip_grid_limits.py)
 	k_feat_abs<<<grid, 256, 0, s>>>((char *)p, sx, sy, w, h);
 	return hipGetLastError();
 }

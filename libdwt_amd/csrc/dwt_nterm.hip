@@ -139,7 +139,7 @@ __global__ __launch_bounds__(256) void k_nterm(NtermArgs a)
 		lg++;
 	const int TX = 1 << lg, TY = 256 >> lg, tx = threadIdx.x & (TX - 1), ty = threadIdx.x >> lg;
 	char *base = a.img + (long)g * a.bstride;
-	for (int slab = b0; slab < a.slabs; slab += a.bpg) {
+	for (int slab = b0; slab < a.slabs; slab += a.bpg) { // (past the cap: tests/test_hip_grid_limits.py)
 		const int r0 = slab * a.slab_rows, rows = min(a.slab_rows, a.h - r0);
 		for (int r = ty; r < rows; r += TY) {
 			const int y = r0 + r;

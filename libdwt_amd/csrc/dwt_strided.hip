@@ -56,7 +56,7 @@ static hipError_t strided_move_t(void *dense, long pitch, void *strided, long sx
 	if (w <= 0 || h <= 0)
 		return hipSuccess;
 	const bool aligned = ((uintptr_t)strided | (uintptr_t)sx | (uintptr_t)sy) % ES == 0;
-	dim3 grid((w + 255) / 256, h < 16384 ? h : 16384);
+	dim3 grid((w + 255) / 256, h < 16384 ? h : 16384); // (past the cap: tests/test_hip_grid_limits.py)
 	if (aligned)
 		k_strided_move<ES, true, PACK><<<grid, 256, 0, st>>>((char *)dense, pitch, (char *)strided, sx, sy, w, h);
 	else

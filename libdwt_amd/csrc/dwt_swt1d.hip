@@ -153,7 +153,7 @@ hipError_t launch_swt_level(Wavelet w, const SwtLevelArgs &a, hipStream_t s)
 		return hipSuccess;
 	if (a.level < 0 || a.level >= SWT_MAX_LEVELS)
 		return hipErrorInvalidValue;
-	const dim3 grid((unsigned)((a.N + 255l) / 256), (unsigned)(a.n_lines < 65535 ? a.n_lines : 65535));
+	const dim3 grid((unsigned)((a.N + 255l) / 256), (unsigned)(a.n_lines < 65535 ? a.n_lines : 65535)); // (past the cap: tests/test_hip_grid_limits.py)
 	if (w == kCdf97S)
 		k_swt_level<Swt97><<<grid, 256, 0, s>>>(a);
 	else if (w == kCdf53S)

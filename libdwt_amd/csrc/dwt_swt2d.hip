@@ -153,7 +153,7 @@ static bool pass_args_ok(const Swt2dLevelArgs &a) { return a.level >= 0 && a.lev
 static dim3 pass_grid(const Swt2dLevelArgs &a)
 {
 	const long lines = (long)a.H * a.batch;
-	return dim3((unsigned)((a.W + 255l) / 256), (unsigned)(lines < 65535 ? lines : 65535));
+	return dim3((unsigned)((a.W + 255l) / 256), (unsigned)(lines < 65535 ? lines : 65535)); // (past the cap: tests/test_hip_grid_limits.py)
 }
 
 template <class F>
@@ -173,7 +173,7 @@ hipError_t swt2d_fused_t(const Swt2dLevelArgs &a, hipStream_t s)
 
 bool swt2d_fused_fits(const Swt2dLevelArgs &a)
 {
-	if (a.level < 0 || a.level >= SWT2D_FUSED_LEVELS || a.src_sy != 4 || a.d_sy != 4 || a.batch > 65535)
+	if (a.level < 0 || a.level >= SWT2D_FUSED_LEVELS || a.src_sy != 4 || a.d_sy != 4 || a.batch > 65535) // (past the cap: tests/test_hip_grid_limits.py)
 		return false;
 	return std::min<long>(1l << a.level, a.H) * class_tiles(a.H, a.level) <= 65535;
 }

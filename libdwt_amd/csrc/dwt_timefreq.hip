@@ -224,7 +224,7 @@ __global__ __launch_bounds__(256) void k_tf_plane_op(TfPlaneArgs a)
 	}
 }
 
-unsigned capped(long n) { return (unsigned)(n < 65535 ? n : 65535); }
+unsigned capped(long n) { return (unsigned)(n < 65535 ? n : 65535); } // (past the cap: tests/test_hip_grid_limits.py)
 
 } // namespace
 

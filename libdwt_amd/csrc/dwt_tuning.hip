@@ -305,7 +305,7 @@ int dwt_hip_tune(int wavelet, int inverse, const void *src, void *dst, size_t ba
 	if (!wavelet_of(wavelet, &w))
 		return fail("unknown wavelet %d", wavelet);
 	const int es = elem_size(w);
-	if (!src || !dst || batch < 1 || batch > 65535)
+	if (!src || !dst || batch < 1 || batch > 65535) // (past the cap: tests/test_hip_grid_limits.py)
 		return fail("dwt_hip_tune: bad argument (batch must be 1..65535)");
 	if (!dwt_hip_is_device_pointer(src) || !dwt_hip_is_device_pointer(dst))
 		return fail("dwt_hip_tune takes the device buffers the transforms will run on");

@@ -30,7 +30,8 @@ def dwt():
 
     d.dwt_util_init()
     yield d
-    d.set_option("generic", 0)
+    for k, v in (("generic", 0), ("tile_pairs", 0), ("waves", 4), ("xcd_swizzle", 1)):
+        d.set_option(k, v)
     d.dwt_util_finish()
 
 
@@ -213,6 +214,40 @@ def test_generic_option_gives_the_fused_bits(dwt, shape):
     assert res[0][1] == jw and res[1][1] == 2 * jw  # one fused launch per level; a column pass and a row pass per level
     src.free()
     dst.free()
+
+
+@pytest.mark.parametrize("shape", [(515, 300), (130, 2049), (67, 131)])
+def test_tile_variants_agree(dwt, shape):
+    """Every tile height, wave count and block order gives the model's bits: the int16 twin of test_tile_variants_agree
+    and test_double_tile_variants_agree in tests/test_hip_parity.py.  Left alone the launcher picks 2 row pairs per tile
+    for calls of up to 2 Mi samples, 4 up to 8 Mi and up to 64 (forward) or 32 (inverse) beyond (i16_tile_pairs,
+    dwt_sweep2d_i16.hip:181-195), so no image of this file's size ever meets the taller tiles; option "tile_pairs" forces
+    them.  515 x 300: several tile rows, the last one short; 130 x 2049: three forward tiles across, an odd width;
+    67 x 131: fewer than 64 rows, odd both ways.  64 and 128 pairs exceed the Hd of the smaller shapes on purpose: one
+    tile taller than the image.  Forward out of place, inverse in place, dense and padded pitch, sentinels kept."""
+    h, w = shape
+    ins = dict(inputs(shape))
+    try:
+        for tp in (2, 4, 8, 64, 128):
+            for waves in (1, 4):
+                for swz in (0, 1):
+                    for k, v in (("tile_pairs", tp), ("waves", waves), ("xcd_swizzle", swz)):
+                        dwt.set_option(k, v)
+                    for name in ("full", "checker"):
+                        img = ins[name]
+                        wf, jw = want(shape, name, img, -1)
+                        for pitch in pitches(w)[:2]:
+                            src, dst = Padded(dwt, img, pitch), Padded(dwt, np.zeros_like(img), pitch)
+                            assert t2d(dwt, 0, src.ptr, dst.ptr, pitch, shape, -1) == jw
+                            assert np.array_equal(dst.read(), wf), ("forward", tp, waves, swz, name, pitch)
+                            assert np.array_equal(src.read(), img), ("source", tp, waves, swz, name, pitch)
+                            t2d(dwt, 1, dst.ptr, dst.ptr, pitch, shape, jw)
+                            assert np.array_equal(dst.read(), img), ("inverse", tp, waves, swz, name, pitch)
+                            src.free()
+                            dst.free()
+    finally:
+        for k, v in (("tile_pairs", 0), ("waves", 4), ("xcd_swizzle", 1)):
+            dwt.set_option(k, v)
 
 
 def test_one_launch_per_level(dwt):

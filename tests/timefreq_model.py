@@ -11,6 +11,7 @@ infinite part; bin y of a bank writes plane row bins-1-y.
 
 * `cdots`, `magnitude`, `planes` -- the numpy float32 restatement;
 * `phase_derivative`, `ridges1`, `ridges2` -- the plane operators, float32 operation by operation;
+* `ridges3` -- detect_ridges3_s with the angle, its cosine and sine in float64 rounded once, as the device takes them;
 * `ridges3_margin` -- how close the float64 cosine / sine of a point's gradient angle comes to +-1/2 (detect_ridges3_s);
 * `CASES` -- what tests/golden/timefreq.npz holds, written by scripts/gen_timefreq_golden.py from the reference itself."""
 import os
@@ -118,6 +119,29 @@ def ridges3_margin(mag):
         d = np.minimum(np.abs(np.abs(np.cos(ang)) - 0.5), np.abs(np.abs(np.sin(ang)) - 0.5))
     d = d[~np.isnan(d)]
     return float(d.min()) if d.size else np.inf
+
+
+def ridges3(mag, threshold):
+    """detect_ridges3_s the way the device evaluates it (libdwt_amd/csrc/dwt_timefreq.hip: grad_max): the gradient angle,
+    its cosine and its sine each taken in float64 and rounded to float32 once.  The reference's float libm gives the same
+    plane wherever no cosine or sine comes within `ridges3_margin` of -+1/2 (tests/test_grid_limits_model.py holds this
+    function to the fixtures)."""
+    m = np.asarray(mag, F32)
+    out = np.zeros(m.shape, F32)
+    if m.shape[0] < 3 or m.shape[1] < 3:
+        return out
+    with np.errstate(all="ignore"):
+        m1 = m[1:-1, 1:-1]
+        dx = ((m[1:-1, 2:] - m[1:-1, :-2]).astype(F32) / F32(2)).astype(F32)
+        dy = ((m[2:, 1:-1] - m[:-2, 1:-1]).astype(F32) / F32(2)).astype(F32)
+        ang = np.arctan2(dy.astype(np.float64), dx.astype(np.float64)).astype(F32).astype(np.float64)
+        dir_x, dir_y = np.cos(ang).astype(F32), np.sin(ang).astype(F32)
+        nx = np.where(dir_x < F32(-0.5), -1, np.where(dir_x > F32(0.5), 1, 0))
+        ny = np.where(dir_y < F32(-0.5), -1, np.where(dir_y > F32(0.5), 1, 0))
+        yy, xx = np.mgrid[1:m.shape[0] - 1, 1:m.shape[1] - 1]
+        keep = (m1 >= m[yy + ny, xx + nx]) & (m1 > F32(threshold))
+        out[1:-1, 1:-1] = np.where(keep, ((m1 / F32(2)).astype(F32) / PI).astype(F32), F32(0))
+    return out
 
 
 def ulps(got, exact64):
