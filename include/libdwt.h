@@ -72,6 +72,19 @@ void dwt_cdf53_2i_i16(void *ptr, int stride_x, int stride_y,
 	int size_o_big_x, int size_o_big_y, int size_i_big_x, int size_i_big_y,
 	int j_max, int decompose_one, int zero_padding);
 
+/* EXTENSION: float CDF 9/7 on IEEE binary16 storage.  The parameter list, Mallat layout and j_max rules of dwt_cdf97_2f_s /
+ * dwt_cdf97_2i_s; samples are binary16 bit patterns (stride_y >= 2).  Every level widens its frame to binary32 (exact),
+ * computes what one level of dwt_cdf97_2f_s / _2i_s computes, and rounds the result to binary16 once, to nearest even.  Not
+ * reversible (a 5-level round trip of 8-bit data returns within one grey level: 0.625 measured on 8192 x 8192) and not protected against overflow: a
+ * level doubles the gain of the LL band, so max|x| * 2^levels must stay below 65504 (8-bit data: 8 levels; 12-bit data: 3),
+ * beyond which coefficients become +-Inf and NaN as IEEE arithmetic has it.  DESIGN.md s22. */
+void dwt_cdf97_2f_h(void *ptr, int stride_x, int stride_y,
+	int size_o_big_x, int size_o_big_y, int size_i_big_x, int size_i_big_y,
+	int *j_max_ptr, int decompose_one, int zero_padding);
+void dwt_cdf97_2i_h(void *ptr, int stride_x, int stride_y,
+	int size_o_big_x, int size_o_big_y, int size_i_big_x, int size_i_big_y,
+	int j_max, int decompose_one, int zero_padding);
+
 /* Float CDF 5/3.  src/libdwt.h:722, 1053. */
 void dwt_cdf53_2f_s(void *ptr, int stride_x, int stride_y,
 	int size_o_big_x, int size_o_big_y, int size_i_big_x, int size_i_big_y,
@@ -262,6 +275,13 @@ void dwt_util_conv_show_s(const void *src, void *dst, int stride_x, int stride_y
 void dwt_util_conv_show_i(const void *src, void *dst, int stride_x, int stride_y, int size_i_big_x, int size_i_big_y);
 /* |x| of int16_t samples, stored as int16_t, src/libdwt.h:2460 */
 void dwt_util_conv_show_i16(const void *src, void *dst, int stride_x, int stride_y, int size_i_big_x, int size_i_big_y);
+/* EXTENSION: host images of float samples <-> IEEE binary16 samples, element (y, x) of either at y * stride_x + x * stride_y
+ * bytes.  float -> half rounds to nearest even (|x| >= 65520 to Inf, results below 2^-14 subnormal, NaN to a quiet NaN);
+ * half -> float is exact. */
+void dwt_util_float_to_half(void *dst, int dst_stride_x, int dst_stride_y, const void *src, int src_stride_x, int src_stride_y,
+	int size_x, int size_y);
+void dwt_util_half_to_float(void *dst, int dst_stride_x, int dst_stride_y, const void *src, int src_stride_x, int src_stride_y,
+	int size_x, int size_y);
 /* double-precision twins (examples/simple-double): pattern with 0-based x, y
  * (src/libdwt.c:1112-1125), copy, compare within 1e-6 absolute, view, PGM writer */
 void dwt_util_test_image_fill_d(void *ptr, int stride_x, int stride_y, int size_i_big_x, int size_i_big_y, int rand);

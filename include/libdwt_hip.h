@@ -53,6 +53,9 @@ enum dwt_hip_wavelet {
 	DWT_HIP_CDF53_I16 = 8, /* reversible int16 CDF 5/3 in JPEG 2000 order (columns before rows, ITU-T T.800 F.3.2 / F.3.8.1):
 	                          dwt_cdf53_2f_i16 / dwt_cdf53_2i_i16; 2-byte elements; dwt_hip_transform2d, _transform2d_batch,
 	                          dwt_hip_alloc_batch and dwt_hip_tune only */
+	DWT_HIP_CDF97_H = 9, /* float CDF 9/7 on IEEE binary16 storage: dwt_cdf97_2f_h / dwt_cdf97_2i_h; 2-byte elements, binary32
+	                        arithmetic, one rounding to nearest even per level; not reversible, no overflow protection
+	                        (max|x| * 2^levels must stay below 65504); the same four entries only */
 	DWT_HIP_INTERP53_S = 6 /* float interpolating 5/3 (CDF 5/3 predict step, no update): dwt_interp53_2f_s / dwt_interp53_2i_s
 	                          (src/libdwt.c:16801, 18457), 1-D dwt_interp53_1f_s / _1i_s (:16166, :15900); not in the
 	                          interleaved layout */

@@ -470,7 +470,7 @@ int dwt_hip_transform2d_batch(int wavelet, int inverse, const void *src, void *d
 	const Geom ge{size_x, size_y, size_x, size_y};
 	Img s{(char *)src, stride_x, es}, d{(char *)dst, stride_x, es};
 	if (g_i16_call == 1 && batch > 1) {
-		// int16 images that the fused sweeps do not take: the line passes, which run image by image
+		// images of 2-byte elements that the fused sweeps do not take: the line passes, which run image by image
 		const int j_in = *j;
 		for (int b = 0; b < batch; b++) {
 			const Img sb{s.p + (size_t)b * batch_stride, stride_x, es}, db{d.p + (size_t)b * batch_stride, stride_x, es};

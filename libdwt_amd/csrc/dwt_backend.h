@@ -54,10 +54,11 @@ struct Ctx {
 	Buf cond_ws; // row conditioning: per-row medians, extrema, centres, moves, records (dwt_backend_condition.hip)
 	Buf band_ws; // band operators: the per-image operator tables of a batch (dwt_backend_bandops.hip)
 	Buf nterm_ws; // N-term approximation: ranks, select histograms, records (dwt_backend_nterm.hip)
+	Buf half_f32; // float 9/7 on binary16 storage, line-pass route: the binary32 copies of a level's frame (dwt_backend.hip)
 	// every device scratch buffer above: a new one is declared there, listed here, and named nowhere else for freeing
 	auto bufs()
 	{
-		return std::array{&stage_img, &ll[0], &ll[1], &frame_a, &frame_b, &vol_out, &vol_host[0], &vol_host[1], &eaw_w, &eaw_ll[0], &eaw_ll[1], &feat_ws, &swt_ws, &cond_ws, &band_ws, &nterm_ws};
+		return std::array{&stage_img, &ll[0], &ll[1], &frame_a, &frame_b, &vol_out, &vol_host[0], &vol_host[1], &eaw_w, &eaw_ll[0], &eaw_ll[1], &feat_ws, &swt_ws, &cond_ws, &band_ws, &nterm_ws, &half_f32};
 	}
 	hipEvent_t dl_ev[8] = {}; // strip events of the host downloads (dwt_host_xfer.hip), created once
 	hipEvent_t switch_ev = nullptr; // dwt_hip_set_stream: orders a newly set stream behind the old one's work
@@ -122,10 +123,11 @@ struct Ctx {
 extern thread_local Ctx g;
 extern thread_local char g_err[512];
 extern thread_local bool g_elems_are_32bit; // set per call: the fused sweeps exist for 4-byte elements only
-// set with it by every call that takes a wavelet of any element size (call_elems): 0 -- no int16 call --, 1 -- an int16 call
-// whose levels all take the exact line passes --, 2 -- an int16 call on the fused sweeps of dwt_sweep2d_i16.hip
+// set with it by every call that takes a wavelet of any element size (call_elems): 0 -- no call on 2-byte elements (the int16
+// 5/3, the float 9/7 on binary16 storage) --, 1 -- such a call whose levels all take the exact line passes --, 2 -- such a
+// call on the fused sweeps of dwt_sweep2d_i16.hip / dwt_sweep2d_h.hip
 extern thread_local int g_i16_call;
-// The route rule of the int16 5/3: the fused sweeps take images whose bases, pitches and batch strides are all multiples
+// The route rule of the wavelets of 2-byte elements: the fused sweeps take images whose bases, pitches and batch strides are all multiples
 // of 4 bytes (a lane's own bytes of a row are then dword-aligned); anything else takes the line passes.
 void call_elems(int es, std::initializer_list<const void *> ptrs, std::initializer_list<long> strides);
 
@@ -143,7 +145,7 @@ inline bool overlap(const void *a, size_t na, const void *b, size_t nb)
 
 // The public wavelet id of a C-ABI call (enum dwt_hip_wavelet) as the internal enum Wavelet: ids 0..5 are the same
 // numbers, DWT_HIP_INTERP53_S (6) is kInterp53S -- internal 6 is the contracted float 9/7 --, DWT_HIP_CDF53_I16 (8) is
-// kCdf53I16.  false: no such public id.
+// kCdf53I16, DWT_HIP_CDF97_H (9) kCdf97H.  false: no such public id.
 static inline bool wavelet_of(int id, Wavelet *w)
 {
 	if (id >= 0 && id <= 5) {
@@ -156,6 +158,10 @@ static inline bool wavelet_of(int id, Wavelet *w)
 	}
 	if (id == DWT_HIP_CDF53_I16) {
 		*w = kCdf53I16;
+		return true;
+	}
+	if (id == DWT_HIP_CDF97_H) {
+		*w = kCdf97H;
 		return true;
 	}
 	return false;

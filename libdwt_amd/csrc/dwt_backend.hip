@@ -275,8 +275,8 @@ void call_elems(int es, std::initializer_list<const void *> ptrs, std::initializ
 }
 
 // the fused sweeps exist for the 32-bit types and, since round 2, for the double-precision wavelets
-// (dwt_sweep2d_d.hip; option "fused_d" = 0 sends those back to the exact line passes); the int16 5/3 has its own
-// (dwt_sweep2d_i16.hip) for the calls that call_elems found aligned
+// (dwt_sweep2d_d.hip; option "fused_d" = 0 sends those back to the exact line passes); the int16 5/3 and the float 9/7 on
+// binary16 storage have their own (dwt_sweep2d_i16.hip, dwt_sweep2d_h.hip) for the calls that call_elems found aligned
 bool level_fused_ok(const Geom &ge, int j)
 {
 	return !g.force_generic && (g_elems_are_32bit || (g_i16_call ? g_i16_call == 2 : g.fused_d != 0)) && ge.Wi(j) == ge.Wo(j) && ge.Hi(j) == ge.Ho(j) && ge.Wo(j) >= 2 &&
@@ -309,6 +309,34 @@ static bool pair01_ok(Wavelet w, const Geom &ge, int J, int batch)
 	return fwd01_tiles(W) * 10 <= ntx * 11 && ntx * nty * batch >= 32768;
 }
 
+// ---- the line-pass route of the float 9/7 on binary16 storage (kCdf97H) ----------------
+// A level rounds ONCE: its exact line passes are those of the float 9/7 (kCdf97S) on binary32 copies of the level's frame,
+// widened before the passes (exact) and narrowed after them (round to nearest even).  half_level_begin: the Wo x Ho frame of
+// `cur` -- and that of `dst` where it is another image: the passes leave the elements they do not write as the destination
+// has them -- in binary32 (Ctx::half_f32); half_level_end: the destination's copy narrowed into dst.  Elements no pass writes
+// go through both conversions and keep their value, except the payload of a signalling NaN, which the widening quiets.
+static int half_level_begin(Img cur, Img dst, int Wo, int Ho, Img *fcur, Img *fdst)
+{
+	const long fp = align_up((long)Wo * 4, 256);
+	if (grow(g.half_f32, (size_t)fp * Ho * 2))
+		return 1;
+	*fcur = Img{(char *)g.half_f32.p, fp, 4};
+	if (launched(launch_half_frame_cvt(true, cur.p, cur.sx, fcur->p, fp, Wo, Ho, g.stream), "binary16 frame", "widening"))
+		return 1;
+	*fdst = *fcur;
+	if (cur.p != dst.p) {
+		*fdst = Img{(char *)g.half_f32.p + (size_t)fp * Ho, fp, 4};
+		if (launched(launch_half_frame_cvt(true, dst.p, dst.sx, fdst->p, fp, Wo, Ho, g.stream), "binary16 frame", "widening"))
+			return 1;
+	}
+	return 0;
+}
+
+static int half_level_end(Img fdst, Img dst, int Wo, int Ho)
+{
+	return launched(launch_half_frame_cvt(false, dst.p, dst.sx, fdst.p, fdst.sx, Wo, Ho, g.stream), "binary16 frame", "narrowing");
+}
+
 // ---- forward ---------------------------------------------------------------------
 int forward2d(Wavelet w, Img src, Img dst, const Geom &ge, int *jp, int decompose_one, int zero_padding,
 	int batch, long src_bstride, long dst_bstride)
@@ -321,8 +349,8 @@ int forward2d(Wavelet w, Img src, Img dst, const Geom &ge, int *jp, int decompos
 	if (J == 0)
 		return 0;
 	const int es = elem_size(w);
-	const bool dbl = es == 8, i16 = es == 2;
-	const bool cols_first = i16; // the int16 5/3 lifts the columns of a level before its rows (2D_SD)
+	const bool dbl = es == 8, i16 = es == 2, half = w == kCdf97H; // (i16: 2-byte elements, the int16 5/3 and the binary16 9/7)
+	const bool cols_first = w == kCdf53I16; // the int16 5/3 lifts the columns of a level before its rows (2D_SD)
 	if (ensure_ll(ge, batch, es))
 		return 1;
 
@@ -401,6 +429,7 @@ int forward2d(Wavelet w, Img src, Img dst, const Geom &ge, int *jp, int decompos
 			prof_before(j);
 			hipError_t e = pair ? launch_fwd01(a, tune, g.stream)
 			             : dbl  ? launch_fwd_level_d(w, a, tune, g.stream)
+			             : half ? launch_fwd_level_h(w, a, tune, g.stream)
 			             : i16  ? launch_fwd_level_i16(w, a, tune, g.stream)
 			                    : launch_fwd_level((g.fma && w == kCdf97S) ? kCdf97SFma : w, a, tune, g.stream);
 			prof_after(j);
@@ -444,35 +473,50 @@ int forward2d(Wavelet w, Img src, Img dst, const Geom &ge, int *jp, int decompos
 			ll_in = -1;
 			cur = dst;
 		}
+		// the wavelet and the images the line passes of this level run on: the call's own, or (binary16 storage) the float
+		// 9/7 on binary32 copies of the level's frame
+		Wavelet wl = w;
+		Img lc = cur, ld = dst;
+		if (half) {
+			wl = kCdf97S;
+			if (half_level_begin(cur, dst, Wo, Ho, &lc, &ld))
+				return 1;
+		}
 		if (Wi == Wo && Hi == Ho && Wo >= 2 && Ho >= 2) {
 			// dense frame: each pass writes every element of the level's frame, so the two passes
 			// ping-pong through the staging image (rows: image -> stage, columns: stage -> image)
 			// instead of each staging and copying back a frame of its own: 4 instead of 12 frame
 			// transfers per level (the double-precision drivers and accel 1 live on these passes)
-			if (grow(g.stage_img, (size_t)dst.sx * Ho))
+			if (grow(g.stage_img, (size_t)ld.sx * Ho))
 				return 1;
-			const Img S{(char *)g.stage_img.p, dst.sx, dst.es};
-			if (cols_first ? (generic_pass(w, false, false, cur, S, Wo, Ho, Wo, Hi, Hd) || generic_pass(w, false, true, S, dst, Wo, Ho, Ho, Wi, Wd))
-			               : (generic_pass(w, false, true, cur, S, Wo, Ho, Ho, Wi, Wd) || generic_pass(w, false, false, S, dst, Wo, Ho, Wo, Hi, Hd)))
+			const Img S{(char *)g.stage_img.p, ld.sx, ld.es};
+			if (cols_first ? (generic_pass(wl, false, false, lc, S, Wo, Ho, Wo, Hi, Hd) || generic_pass(wl, false, true, S, ld, Wo, Ho, Ho, Wi, Wd))
+			               : (generic_pass(wl, false, true, lc, S, Wo, Ho, Ho, Wi, Wd) || generic_pass(wl, false, false, S, ld, Wo, Ho, Wo, Hi, Hd)))
 				return 1;
-			cur = dst;
+			lc = ld;
 		} else
 		for (int pass = 0; pass < 2; pass++) {
 			const bool rows = cols_first ? (pass == 1) : (pass == 0);
 			if (rows) {
-				if (!skip_single(w) || Wo > 1) {
-					if (generic_pass(w, false, true, cur, dst, Wo, Ho, Ho, Wi, Wd))
+				if (!skip_single(wl) || Wo > 1) {
+					if (generic_pass(wl, false, true, lc, ld, Wo, Ho, Ho, Wi, Wd))
 						return 1;
-					cur = dst; // src/libdwt.c:12709
+					lc = ld; // src/libdwt.c:12709
 				}
 			} else {
-				if (!skip_single(w) || Ho > 1) {
-					if (generic_pass(w, false, false, cur, dst, Wo, Ho, Wo, Hi, Hd))
+				if (!skip_single(wl) || Ho > 1) {
+					if (generic_pass(wl, false, false, lc, ld, Wo, Ho, Wo, Hi, Hd))
 						return 1;
-					cur = dst; // src/libdwt.c:12742
+					lc = ld; // src/libdwt.c:12742
 				}
 			}
 		}
+		if (half) {
+			if (half_level_end(ld, dst, Wo, Ho))
+				return 1;
+			cur = dst;
+		} else
+			cur = lc;
 		if (zero_padding) {
 			// dwt_zero_padding_f_stride_* (src/libdwt.c:12079-12131) over rows then columns
 			const int nl_x = (Wi + 1) >> 1, nh_x = Wi >> 1, nl_y = (Hi + 1) >> 1, nh_y = Hi >> 1;
@@ -499,7 +543,7 @@ int inverse2d(Wavelet w, Img src, Img dst, const Geom &ge, int j_max, int decomp
 		return 0;
 	}
 	const int es = elem_size(w);
-	const bool dbl = es == 8, i16 = es == 2;
+	const bool dbl = es == 8, i16 = es == 2, half = w == kCdf97H; // (i16: 2-byte elements, the int16 5/3 and the binary16 9/7)
 	if (ensure_ll(ge, batch, es))
 		return 1;
 	const bool cols_first = (w == kCdf53I || w == kCdf97I); // the int32 inverses undo columns first (the int16 5/3 rows: the mirror of its forward)
@@ -609,6 +653,7 @@ int inverse2d(Wavelet w, Img src, Img dst, const Geom &ge, int j_max, int decomp
 			}
 			prof_before(j - 1);
 			hipError_t e = dbl ? launch_inv_level_d(w, a, tune, g.stream)
+			             : half ? launch_inv_level_h(w, a, tune, g.stream)
 			             : i16 ? launch_inv_level_i16(w, a, tune, g.stream)
 			                   : launch_inv_level((g.fma && w == kCdf97S) ? kCdf97SFma : w, a, tune, g.stream);
 			prof_after(j - 1);
@@ -636,28 +681,39 @@ int inverse2d(Wavelet w, Img src, Img dst, const Geom &ge, int j_max, int decomp
 				return 1;
 			ll_in = -1;
 		}
+		// (binary16 storage: the float 9/7 on a binary32 copy of the level's frame, as in the forward driver)
+		Wavelet wl = w;
+		Img ld = dst;
+		if (half) {
+			Img same;
+			wl = kCdf97S;
+			if (half_level_begin(dst, dst, Wo, Ho, &ld, &same))
+				return 1;
+		}
 		if (Wi == Wo && Hi == Ho && Wo >= 2 && Ho >= 2) {
 			// dense frame: ping-pong through the staging image, as in the forward driver
-			if (grow(g.stage_img, (size_t)dst.sx * Ho))
+			if (grow(g.stage_img, (size_t)ld.sx * Ho))
 				return 1;
-			const Img S{(char *)g.stage_img.p, dst.sx, dst.es};
+			const Img S{(char *)g.stage_img.p, ld.sx, ld.es};
 			const bool rows_first = !cols_first;
-			if (generic_pass(w, true, rows_first, dst, S, Wo, Ho, rows_first ? Ho : Wo, rows_first ? Wi : Hi, rows_first ? Ws : Hs) ||
-				generic_pass(w, true, !rows_first, S, dst, Wo, Ho, rows_first ? Wo : Ho, rows_first ? Hi : Wi, rows_first ? Hs : Ws))
+			if (generic_pass(wl, true, rows_first, ld, S, Wo, Ho, rows_first ? Ho : Wo, rows_first ? Wi : Hi, rows_first ? Ws : Hs) ||
+				generic_pass(wl, true, !rows_first, S, ld, Wo, Ho, rows_first ? Wo : Ho, rows_first ? Hi : Wi, rows_first ? Hs : Ws))
 				return 1;
 		} else
 		for (int pass = 0; pass < 2; pass++) {
 			const bool rows = cols_first ? (pass == 1) : (pass == 0);
 			if (rows) {
-				if (!skip_single(w) || Wo > 1)
-					if (generic_pass(w, true, true, dst, dst, Wo, Ho, Ho, Wi, Ws))
+				if (!skip_single(wl) || Wo > 1)
+					if (generic_pass(wl, true, true, ld, ld, Wo, Ho, Ho, Wi, Ws))
 						return 1;
 			} else {
-				if (!skip_single(w) || Ho > 1)
-					if (generic_pass(w, true, false, dst, dst, Wo, Ho, Wo, Hi, Hs))
+				if (!skip_single(wl) || Ho > 1)
+					if (generic_pass(wl, true, false, ld, ld, Wo, Ho, Wo, Hi, Hs))
 						return 1;
 			}
 		}
+		if (half && half_level_end(ld, dst, Wo, Ho))
+			return 1;
 		if (zero_padding) {
 			// dwt_zero_padding_i_stride_* (src/libdwt.c:12161-12215)
 			if (zero_rect(dst, Wi, 0, Wo - Wi, Ho) || zero_rect(dst, 0, Hi, Wo, Ho - Hi))

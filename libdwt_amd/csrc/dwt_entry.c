@@ -77,6 +77,19 @@ void dwt_cdf53_2i_i16(void *ptr, int stride_x, int stride_y, int sox, int soy, i
 	run(DWT_HIP_CDF53_I16, 1, ptr, ptr, stride_x, stride_y, sox, soy, six, siy, &j_max, decompose_one, zero_padding, __func__);
 }
 
+/* extension: float CDF 9/7 on binary16 storage */
+void dwt_cdf97_2f_h(void *ptr, int stride_x, int stride_y, int sox, int soy, int six, int siy,
+	int *j_max_ptr, int decompose_one, int zero_padding)
+{
+	run(DWT_HIP_CDF97_H, 0, ptr, ptr, stride_x, stride_y, sox, soy, six, siy, j_max_ptr, decompose_one, zero_padding, __func__);
+}
+
+void dwt_cdf97_2i_h(void *ptr, int stride_x, int stride_y, int sox, int soy, int six, int siy,
+	int j_max, int decompose_one, int zero_padding)
+{
+	run(DWT_HIP_CDF97_H, 1, ptr, ptr, stride_x, stride_y, sox, soy, six, siy, &j_max, decompose_one, zero_padding, __func__);
+}
+
 /* src/libdwt.c:16470 */
 void dwt_cdf53_2f_s(void *ptr, int stride_x, int stride_y, int sox, int soy, int six, int siy,
 	int *j_max_ptr, int decompose_one, int zero_padding)

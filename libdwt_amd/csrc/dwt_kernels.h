@@ -11,9 +11,10 @@ enum Wavelet { kCdf97S = 0, kCdf53I = 1, kCdf53S = 2, kCdf97D = 3, kCdf53D = 4, 
 	kCdf53SNew = 7 /* internal: float 5/3 of dwt-simple.c (odd scale 1/zeta in float), interleaved layout only */,
 	kCdf97IIp = 8 /* internal: fixed-point int 9/7 of the interleaved in-place drivers (rounded terms added) */,
 	kInterp53S = 9 /* interpolating 5/3 float (public id DWT_HIP_INTERP53_S = 6): predict step only */,
-	kCdf53I16 = 10 /* reversible int16 5/3 in JPEG 2000 order (public id DWT_HIP_CDF53_I16 = 8): columns before rows */ };
+	kCdf53I16 = 10 /* reversible int16 5/3 in JPEG 2000 order (public id DWT_HIP_CDF53_I16 = 8): columns before rows */,
+	kCdf97H = 11 /* float 9/7 on binary16 storage (public id DWT_HIP_CDF97_H = 9): binary32 arithmetic, one rounding per level */ };
 
-inline int elem_size(Wavelet w) { return (w == kCdf97D || w == kCdf53D) ? 8 : w == kCdf53I16 ? 2 : 4; }
+inline int elem_size(Wavelet w) { return (w == kCdf97D || w == kCdf53D) ? 8 : (w == kCdf53I16 || w == kCdf97H) ? 2 : 4; }
 
 // Tuning knobs of the fused sweep kernels (set through dwt_hip_set_option).
 struct SweepTuning {
@@ -135,6 +136,13 @@ hipError_t launch_inv_level_d(Wavelet w, const InvLevelArgs &a, const SweepTunin
 // multiples of 4 bytes (the driver sends everything else through the line passes)
 hipError_t launch_fwd_level_i16(Wavelet w, const FwdLevelArgs &a, const SweepTuning &t, hipStream_t s);
 hipError_t launch_inv_level_i16(Wavelet w, const InvLevelArgs &a, const SweepTuning &t, hipStream_t s);
+// the two sweeps of the float 9/7 on binary16 storage (dwt_sweep2d_h.hip): pitches in 2-byte ELEMENTS, the alignment rule of
+// the int16 sweeps
+hipError_t launch_fwd_level_h(Wavelet w, const FwdLevelArgs &a, const SweepTuning &t, hipStream_t s);
+hipError_t launch_inv_level_h(Wavelet w, const InvLevelArgs &a, const SweepTuning &t, hipStream_t s);
+// its line-pass route: a w x h frame of binary16 samples widened into a frame of binary32 ones (exact), or narrowed back
+// (round to nearest even); pitches in BYTES
+hipError_t launch_half_frame_cvt(bool widen, void *halves, long half_pitch, void *floats, long float_pitch, int w, int h, hipStream_t s);
 // true when launch_inv_level has a fused kernel for this wavelet
 bool have_fused_inverse(Wavelet w);
 

@@ -162,6 +162,23 @@ struct Cdf53I16 {
 template <class W, class = void> struct storage_of { using type = typename W::T; };
 template <class W> struct storage_of<W, std::void_t<typename W::S>> { using type = typename W::S; };
 
+// Float CDF 9/7 on IEEE binary16 STORAGE (public id DWT_HIP_CDF97_H): the steps, scaling and order of Cdf97S
+// in binary32 registers (T); samples are binary16 in memory (S), widened on load -- exact, subnormals kept -- and rounded
+// to nearest even ONCE per level, when its four subbands (or, inverse, its result) are stored.  The casts are plain
+// (T)(S) / (S)(T) conversions: the compiler emits v_cvt_f32_f16 / v_cvt_f16_f32 under the default float mode (round to
+// nearest even, 16-bit denormals on); never the packed round-toward-zero conversion.
+// kEndForms = false: the reflected taps give the bits of the reference's end form.  That form adds (2c) x where reflection
+// adds c (x + x).  2c and x + x are exact, so both products round the same real number 2cx -- the same float for every x,
+// +-0, +-Inf and NaN included -- unless x + x overflows, |x| > FLT_MAX / 2.  A level starts from binary16 values,
+// |x| <= 65504 or not finite; a step grows the largest magnitude by at most 1 + 2 * 1.586 = 4.2, so the eight steps and two
+// scalings of a level by less than 2^18: no finite value of a level comes near 2^127.  So the fused sweeps have one form of
+// the line ends in either build of DWT_FLOAT_END_FORMS, and it gives the bits of both.  (tests/test_hip_f16.py compares the
+// sweeps with the line passes, which run Cdf97S -- end forms as the build has them -- on a binary32 copy of the level.)
+struct Cdf97H : Cdf97S {
+	using S = _Float16; // storage type
+	static constexpr bool kEndForms = false;
+};
+
 // Fixed-point int32 CDF 9/7 (src/libdwt.c:10901-10948, 11699-11746): no scaling; the
 // reference's own end formulas are the reflected ones (`a[N-2]+a[N-2]`), so reflection
 // is exact here for any input.

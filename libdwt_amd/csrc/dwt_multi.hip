@@ -222,8 +222,8 @@ static int batch_multi(bool tune, int wavelet, int inverse, const void *const *s
 	Wavelet w_;
 	if (!wavelet_of(wavelet, &w_))
 		return fail("unknown wavelet %d", wavelet);
-	if (w_ == kCdf53I16)
-		return fail("the sharded and multi-device entries take wavelets of 4- and 8-byte elements, not DWT_HIP_CDF53_I16");
+	if (elem_size(w_) == 2)
+		return fail("the sharded and multi-device entries take wavelets of 4- and 8-byte elements, not DWT_HIP_CDF53_I16 or DWT_HIP_CDF97_H");
 	const int ndev = dwt_hip_device_count();
 	for (int k = 0; k < n_shards; k++) {
 		if (devices[k] < 0 || devices[k] >= ndev)
@@ -333,8 +333,8 @@ int dwt_hip_transform2d_batch_sharded(int wavelet, int inverse, const void *src,
 	Wavelet w_;
 	if (!wavelet_of(wavelet, &w_))
 		return fail("unknown wavelet %d", wavelet);
-	if (w_ == kCdf53I16)
-		return fail("the sharded and multi-device entries take wavelets of 4- and 8-byte elements, not DWT_HIP_CDF53_I16");
+	if (elem_size(w_) == 2)
+		return fail("the sharded and multi-device entries take wavelets of 4- and 8-byte elements, not DWT_HIP_CDF53_I16 or DWT_HIP_CDF97_H");
 	const int es = elem_size(w_);
 	const int G = n_devices < batch ? n_devices : batch; // never more slots than images
 	const bool dense = (size_t)stride_x == (size_t)size_x * es && batch_stride == (size_t)stride_x * size_y;

@@ -124,6 +124,8 @@ hipError_t launch_line_pass(Wavelet w, bool inverse, const void *src, void *dst,
 	case kCdf97IIp: return line_pass_t<Cdf97IIp>(inverse, src, dst, line_stride, elem_stride, n_lines, N, hoff, lanes_along_lines, s);
 	case kInterp53S: return line_pass_t<Interp53S>(inverse, src, dst, line_stride, elem_stride, n_lines, N, hoff, lanes_along_lines, s);
 	case kCdf53I16: return line_pass_t<Cdf53I16>(inverse, src, dst, line_stride, elem_stride, n_lines, N, hoff, lanes_along_lines, s);
+	// (binary16 storage: the driver runs Cdf97S on a binary32 copy of the level's frame, so that a level rounds once)
+	case kCdf97H: break;
 	// the contracted variant exists for the fused sweeps only: line passes of such a call are exact
 	case kCdf97SFma: return line_pass_t<Cdf97S>(inverse, src, dst, line_stride, elem_stride, n_lines, N, hoff, lanes_along_lines, s);
 	}

@@ -443,6 +443,79 @@ void dwt_util_conv_show_i16(const void *src, void *dst, int stride_x, int stride
 		}
 }
 
+/* ---- IEEE binary16 <-> binary32 on the host, for the images of dwt_cdf97_2f_h / dwt_cdf97_2i_h (an extension; plain
+ * bit arithmetic: no _Float16 is asked of the host compiler) ---- */
+
+/* round to nearest even; overflow (|x| >= 65520) to Inf, results below 2^-14 subnormal, NaN -> quiet NaN */
+static uint16_t half_of_float_bits(uint32_t f)
+{
+	const uint16_t sign = (uint16_t)((f >> 16) & 0x8000u);
+	const uint32_t a = f & 0x7fffffffu;
+	if (a > 0x7f800000u)
+		return (uint16_t)(sign | 0x7e00u | ((a >> 13) & 0x3ffu));
+	if (a >= 0x477ff000u) /* 65520 = 65504 + half an ulp: ties to the even 2^16, which binary16 does not have */
+		return (uint16_t)(sign | 0x7c00u);
+	if (a >= 0x38800000u) { /* normal in binary16: rebias the exponent, round the 13 bits that go */
+		uint32_t r = a - 0x38000000u;
+		r += 0xfffu + ((r >> 13) & 1u);
+		return (uint16_t)(sign | (r >> 13));
+	}
+	/* subnormal: multiples of 2^-24 */
+	const int shift = 126 - (int)(a >> 23);
+	if (shift > 25)
+		return sign;
+	const uint32_t m = (a & 0x7fffffu) | 0x800000u;
+	uint32_t q = m >> shift;
+	const uint32_t rem = m & ((1u << shift) - 1u), half = 1u << (shift - 1);
+	if (rem > half || (rem == half && (q & 1u)))
+		q++;
+	return (uint16_t)(sign | q);
+}
+
+/* exact */
+static uint32_t float_of_half_bits(uint16_t h)
+{
+	const uint32_t sign = (uint32_t)(h & 0x8000u) << 16;
+	uint32_t e = (h >> 10) & 31u, m = h & 0x3ffu;
+	if (e == 31u)
+		return sign | 0x7f800000u | (m << 13);
+	if (e == 0u) {
+		if (!m)
+			return sign;
+		e = 1u;
+		while (!(m & 0x400u)) {
+			m <<= 1;
+			e--; /* (wraps below zero for m < 2^9; e + 112 is taken modulo 2^32 and comes out right) */
+		}
+		m &= 0x3ffu;
+	}
+	return sign | ((e + 112u) << 23) | (m << 13);
+}
+
+void dwt_util_float_to_half(void *dst, int dst_stride_x, int dst_stride_y, const void *src, int src_stride_x, int src_stride_y,
+	int size_x, int size_y)
+{
+	for (int y = 0; y < size_y; y++)
+		for (int x = 0; x < size_x; x++) {
+			uint32_t f;
+			memcpy(&f, px(src, y, x, src_stride_x, src_stride_y), sizeof f);
+			const uint16_t h = half_of_float_bits(f);
+			memcpy(px(dst, y, x, dst_stride_x, dst_stride_y), &h, sizeof h);
+		}
+}
+
+void dwt_util_half_to_float(void *dst, int dst_stride_x, int dst_stride_y, const void *src, int src_stride_x, int src_stride_y,
+	int size_x, int size_y)
+{
+	for (int y = 0; y < size_y; y++)
+		for (int x = 0; x < size_x; x++) {
+			uint16_t h;
+			memcpy(&h, px(src, y, x, src_stride_x, src_stride_y), sizeof h);
+			const uint32_t f = float_of_half_bits(h);
+			memcpy(px(dst, y, x, dst_stride_x, dst_stride_y), &f, sizeof f);
+		}
+}
+
 /* src/libdwt.c:19727-19792: temp = conv_show(input); scale = the largest sample of temp (dwt_util_find_min_max_s,
  * :25426); ASCII PGM of temp against that scale */
 int dwt_util_save_log_to_pgm_s(const char *path, const void *ptr, int stride_x, int stride_y, int size_x, int size_y)
