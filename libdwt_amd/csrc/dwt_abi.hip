@@ -354,8 +354,8 @@ int dwt_hip_transform2d(int wavelet, int inverse, const void *src, void *dst, in
 		return fail("unknown wavelet %d", wavelet);
 	if (!src || !dst || !j)
 		return fail("null pointer argument");
-	const int es = elem_size(w);
-	call_elems(es, {src, dst}, {(long)stride_x});
+	Call2d c = call2d(w, {src, dst}, {(long)stride_x});
+	const int es = c.es;
 	if (sox <= 0 || soy <= 0 || six < 0 || siy < 0 || six > sox || siy > soy)
 		return fail("bad sizes: outer %dx%d inner %dx%d", sox, soy, six, siy);
 	const Geom ge{sox, soy, six, siy};
@@ -365,10 +365,10 @@ int dwt_hip_transform2d(int wavelet, int inverse, const void *src, void *dst, in
 
 	if (dev_dst && stride_y == es && stride_x % es == 0 && stride_x >= sox * es && (uintptr_t)src % es == 0 && (uintptr_t)dst % es == 0) {
 		Img s{(char *)src, stride_x, es}, d{(char *)dst, stride_x, es};
-		if (!inverse && !decompose_one && (*j < 0 || *j >= 2) && place_ll_scratch(w, s, d, ge, *j, 1, 0, 0))
+		if (!inverse && !decompose_one && (*j < 0 || *j >= 2) && place_ll_scratch(c, s, d, ge, *j, 1, 0, 0))
 			return 1;
-		return inverse ? inverse2d(w, s, d, ge, *j, decompose_one, zero_padding, 1, 0, 0)
-		               : forward2d(w, s, d, ge, j, decompose_one, zero_padding, 1, 0, 0);
+		return inverse ? inverse2d(c, s, d, ge, *j, decompose_one, zero_padding, 1, 0, 0)
+		               : forward2d(c, s, d, ge, j, decompose_one, zero_padding, 1, 0, 0);
 	}
 	// ---- a device image whose elements are not adjacent (one channel of an interleaved multi-channel image,
 	// src/cvdwt.cpp:98-135) or not aligned: the reference gathers every line through dwt_util_memcpy_stride_*
@@ -379,8 +379,8 @@ int dwt_hip_transform2d(int wavelet, int inverse, const void *src, void *dst, in
 
 	// ---- host pointers: stage the whole outer frame through HBM ----
 	if (!dev_dst && ge.dense() && stride_y == es && es == 4) {
-		const int rc = inverse ? host_inverse_pipelined(w, src, dst, stride_x, sox, soy, *j, decompose_one)
-		                       : host_forward_pipelined(w, src, dst, stride_x, sox, soy, j, decompose_one);
+		const int rc = inverse ? host_inverse_pipelined(c, src, dst, stride_x, sox, soy, *j, decompose_one)
+		                       : host_forward_pipelined(c, src, dst, stride_x, sox, soy, j, decompose_one);
 		if (rc >= 0)
 			return rc;
 	}
@@ -391,7 +391,7 @@ int dwt_hip_transform2d(int wavelet, int inverse, const void *src, void *dst, in
 		return 1;
 	const long pitch = A.sx;
 	const Img B{(char *)g.frame_b.p, pitch, es};
-	call_elems(es, {A.p, B.p}, {pitch}); // (the transform runs on the staged images)
+	c = call2d(w, {A.p, B.p}, {pitch}); // (the transform runs on the staged images)
 	// B receives the result.  It starts as a copy of what the destination holds so
 	// that every element the reference leaves untouched keeps its value -- unless the call
 	// writes every element of the frame anyway (a dense frame, at least one level: no second
@@ -412,11 +412,11 @@ int dwt_hip_transform2d(int wavelet, int inverse, const void *src, void *dst, in
 	int rc;
 	if (s2 || ge.dense()) {
 		// out of place on the device: no in-place detour even for the in-place entry
-		rc = inverse ? inverse2d(w, A, B, ge, *j, decompose_one, zero_padding, 1, 0, 0)
-		             : forward2d(w, A, B, ge, j, decompose_one, zero_padding, 1, 0, 0);
+		rc = inverse ? inverse2d(c, A, B, ge, *j, decompose_one, zero_padding, 1, 0, 0)
+		             : forward2d(c, A, B, ge, j, decompose_one, zero_padding, 1, 0, 0);
 	} else {
-		rc = inverse ? inverse2d(w, B, B, ge, *j, decompose_one, zero_padding, 1, 0, 0)
-		             : forward2d(w, B, B, ge, j, decompose_one, zero_padding, 1, 0, 0);
+		rc = inverse ? inverse2d(c, B, B, ge, *j, decompose_one, zero_padding, 1, 0, 0)
+		             : forward2d(c, B, B, ge, j, decompose_one, zero_padding, 1, 0, 0);
 	}
 	if (rc)
 		return rc;
@@ -439,7 +439,6 @@ int dwt_hip_transform1d_batch(int wavelet, int inverse, const void *src, void *d
 		return fail("bad sizes: %d lines, outer %d inner %d", n_lines, size_o, size_i);
 	if (elem_stride < 4 || line_stride > (size_t)LONG_MAX / 2)
 		return fail("bad strides: line %zu bytes, element %d bytes", line_stride, elem_stride);
-	g_elems_are_32bit = true;
 	return transform1d(w, inverse != 0, src, dst, (long)line_stride, elem_stride, n_lines, size_o, size_i, j, zero_padding);
 }
 
@@ -457,8 +456,8 @@ int dwt_hip_transform2d_batch(int wavelet, int inverse, const void *src, void *d
 	Wavelet w;
 	if (!wavelet_of(wavelet, &w))
 		return fail("unknown wavelet %d", wavelet);
-	const int es = elem_size(w);
-	call_elems(es, {src, dst}, {(long)stride_x, (long)batch_stride});
+	const Call2d c = call2d(w, {src, dst}, {(long)stride_x, (long)batch_stride});
+	const int es = c.es;
 	if (!src || !dst || !j || batch < 1 || batch > 65535) // (past the cap: tests/test_hip_grid_limits.py)
 		return fail("bad argument (batch must be 1..65535)");
 	if (!dwt_hip_is_device_pointer(src) || !dwt_hip_is_device_pointer(dst))
@@ -469,21 +468,21 @@ int dwt_hip_transform2d_batch(int wavelet, int inverse, const void *src, void *d
 		return fail("in-place batches are not supported; use distinct src and dst");
 	const Geom ge{size_x, size_y, size_x, size_y};
 	Img s{(char *)src, stride_x, es}, d{(char *)dst, stride_x, es};
-	if (g_i16_call == 1 && batch > 1) {
+	if (c.line_passes_only() && batch > 1) {
 		// images of 2-byte elements that the fused sweeps do not take: the line passes, which run image by image
 		const int j_in = *j;
 		for (int b = 0; b < batch; b++) {
 			const Img sb{s.p + (size_t)b * batch_stride, stride_x, es}, db{d.p + (size_t)b * batch_stride, stride_x, es};
 			*j = j_in;
-			if (inverse ? inverse2d(w, sb, db, ge, *j, 0, 0, 1, 0, 0) : forward2d(w, sb, db, ge, j, 0, 0, 1, 0, 0))
+			if (inverse ? inverse2d(c, sb, db, ge, *j, 0, 0, 1, 0, 0) : forward2d(c, sb, db, ge, j, 0, 0, 1, 0, 0))
 				return 1;
 		}
 		return 0;
 	}
-	if (!inverse && (*j < 0 || *j >= 2) && place_ll_scratch(w, s, d, ge, *j, batch, (long)batch_stride, (long)batch_stride))
+	if (!inverse && (*j < 0 || *j >= 2) && place_ll_scratch(c, s, d, ge, *j, batch, (long)batch_stride, (long)batch_stride))
 		return 1;
-	return inverse ? inverse2d(w, s, d, ge, *j, 0, 0, batch, (long)batch_stride, (long)batch_stride)
-	               : forward2d(w, s, d, ge, j, 0, 0, batch, (long)batch_stride, (long)batch_stride);
+	return inverse ? inverse2d(c, s, d, ge, *j, 0, 0, batch, (long)batch_stride, (long)batch_stride)
+	               : forward2d(c, s, d, ge, j, 0, 0, batch, (long)batch_stride, (long)batch_stride);
 }
 
 int dwt_hip_conv_show(int is_int, const void *src, void *dst, int stride_x, int stride_y, int size_x, int size_y)

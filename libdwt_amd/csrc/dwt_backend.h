@@ -1,5 +1,6 @@
 // dwt_backend.h -- what the backend's translation units share: the device context, workspace and
-// staging helpers, the level-pass helpers.  Internal to the shared library (hidden visibility).
+// staging helpers, the level-pass helpers, the route of a 2-D call as a value (Call2d).  The only per-thread state is
+// the context `g` and the error text `g_err`.  Internal to the shared library (hidden visibility).
 #pragma once
 #include "../../include/libdwt_hip.h"
 #include "dwt_kernels.h"
@@ -122,14 +123,21 @@ struct Ctx {
 // device").  Options set through dwt_hip_set_option / dwt_util_set_accel are per thread too.
 extern thread_local Ctx g;
 extern thread_local char g_err[512];
-extern thread_local bool g_elems_are_32bit; // set per call: the fused sweeps exist for 4-byte elements only
-// set with it by every call that takes a wavelet of any element size (call_elems): 0 -- no call on 2-byte elements (the int16
-// 5/3, the float 9/7 on binary16 storage) --, 1 -- such a call whose levels all take the exact line passes --, 2 -- such a
-// call on the fused sweeps of dwt_sweep2d_i16.hip / dwt_sweep2d_h.hip
-extern thread_local int g_i16_call;
-// The route rule of the wavelets of 2-byte elements: the fused sweeps take images whose bases, pitches and batch strides are all multiples
-// of 4 bytes (a lane's own bytes of a row are then dword-aligned); anything else takes the line passes.
-void call_elems(int es, std::initializer_list<const void *> ptrs, std::initializer_list<long> strides);
+// The route of ONE 2-D call as a value: its entry decides it once (call2d) from the wavelet and from the images the
+// transform will RUN ON -- the staged ones where the call is staged -- and every driver below takes it as an argument.
+// Nothing about a call's route outlives the call.
+struct Call2d {
+	Wavelet w;
+	int es;       // elem_size(w)
+	bool aligned; // every base, pitch and batch stride of those images is a multiple of 4 bytes
+	// The route rule of the wavelets of 2-byte elements (the int16 5/3, the float 9/7 on binary16 storage): the fused sweeps of
+	// dwt_sweep2d_i16.hip / dwt_sweep2d_h.hip take aligned images (a lane's own bytes of a row are then dword-aligned);
+	// anything else takes the exact line passes at every level
+	bool line_passes_only() const { return es == 2 && !aligned; }
+};
+Call2d call2d(Wavelet w, std::initializer_list<const void *> ptrs, std::initializer_list<long> strides);
+// the wavelet the 32-bit sweeps are launched with (option "fma": the contracted float 9/7)
+inline Wavelet sweep32_wavelet(Wavelet w) { return (g.fma && w == kCdf97S) ? kCdf97SFma : w; }
 
 int fail(const char *fmt, ...);
 // the tail of a kernel launch that this context counts (stat_launches): 0, or fail("<family> <what> launch failed: ...")
@@ -143,27 +151,16 @@ inline bool overlap(const void *a, size_t na, const void *b, size_t nb)
 	return na && nb && pa < pb + nb && pb < pa + na;
 }
 
-// The public wavelet id of a C-ABI call (enum dwt_hip_wavelet) as the internal enum Wavelet: ids 0..5 are the same
-// numbers, DWT_HIP_INTERP53_S (6) is kInterp53S -- internal 6 is the contracted float 9/7 --, DWT_HIP_CDF53_I16 (8) is
-// kCdf53I16, DWT_HIP_CDF97_H (9) kCdf97H.  false: no such public id.
+// The public wavelet id of a C-ABI call (enum dwt_hip_wavelet) as the internal enum Wavelet: the row of kWaveletFacts that
+// names it.  false: no such public id (7 is none; the internal wavelets have none).
+static_assert(facts(kInterp53S).id == DWT_HIP_INTERP53_S && facts(kCdf53I16).id == DWT_HIP_CDF53_I16 && facts(kCdf97H).id == DWT_HIP_CDF97_H, "kWaveletFacts");
 static inline bool wavelet_of(int id, Wavelet *w)
 {
-	if (id >= 0 && id <= 5) {
-		*w = (Wavelet)id;
-		return true;
-	}
-	if (id == DWT_HIP_INTERP53_S) {
-		*w = kInterp53S;
-		return true;
-	}
-	if (id == DWT_HIP_CDF53_I16) {
-		*w = kCdf53I16;
-		return true;
-	}
-	if (id == DWT_HIP_CDF97_H) {
-		*w = kCdf97H;
-		return true;
-	}
+	for (int k = 0; id >= 0 && k < kWavelets; k++)
+		if (kWaveletFacts[k].id == id) {
+			*w = (Wavelet)k;
+			return true;
+		}
 	return false;
 }
 
@@ -236,26 +233,26 @@ int host_volume_xfer(bool to_device, void *dev, size_t d_sy, size_t d_sz, void *
 int generic_pass(Wavelet w, bool inverse, bool rows, Img in, Img out, int frame_w, int frame_h, int n_lines, int N, int hoff);
 // placement (dwt_backend.hip / dwt_placement.hip)
 size_t ll_band_bytes(const Geom &ge, int k, int batch, int es); // bytes of LL scratch band k (0: level-1 band, 1: level-2 band)
-int timed_forward(Wavelet w, Img s, Img d, const Geom &ge, int levels, int batch, long sb, long db, double *ms); // ms of the 2nd of two calls
-int place_ll_scratch(Wavelet w, Img s, Img d, const Geom &ge, int levels, int batch, long sb, long db);
-int tune2d(Wavelet w, bool inverse, Img s, Img d, const Geom &ge, int levels, int batch, long sb, long db);
+int timed_forward(const Call2d &c, Img s, Img d, const Geom &ge, int levels, int batch, long sb, long db, double *ms); // ms of the 2nd of two calls
+int place_ll_scratch(const Call2d &c, Img s, Img d, const Geom &ge, int levels, int batch, long sb, long db);
+int tune2d(const Call2d &c, bool inverse, Img s, Img d, const Geom &ge, int levels, int batch, long sb, long db);
 bool stream_is_capturing();
 bool may_measure(); // inside dwt_hip_tune, or DWT_HIP_TUNE=1 / option "tune_in_call"
 int tuned_tile_pairs(Wavelet w, const FwdLevelArgs &a); // the measured choice for this level (packed; 0: none) ...
 int tuned_tile_pairs(Wavelet w, const InvLevelArgs &a);
 int tuned_tile_pairs01(Wavelet w, const FwdLevelArgs &a); // the same for the fused pair of levels 0 and 1 (launch_fwd01)
 void apply_tile_choice(int choice, SweepTuning *t, bool inverse); // ... applied to the launch's tuning
-int forward2d(Wavelet w, Img src, Img dst, const Geom &ge, int *jp, int decompose_one, int zero_padding, int batch, long src_bstride, long dst_bstride);
-int inverse2d(Wavelet w, Img src, Img dst, const Geom &ge, int j_max, int decompose_one, int zero_padding, int batch, long src_bstride, long dst_bstride);
-bool level_fused_ok(const Geom &ge, int j);
+int forward2d(const Call2d &c, Img src, Img dst, const Geom &ge, int *jp, int decompose_one, int zero_padding, int batch, long src_bstride, long dst_bstride);
+int inverse2d(const Call2d &c, Img src, Img dst, const Geom &ge, int j_max, int decompose_one, int zero_padding, int batch, long src_bstride, long dst_bstride);
+bool level_fused_ok(const Call2d &c, const Geom &ge, int j); // reads options "generic" and "fused_d" when asked
 // the 1-D drivers (dwt_backend_1d.hip): n_lines lines `line_stride` bytes apart, elements `elem_stride` bytes apart, host
 // or device; *jp as the reference's forward (clamped, stored) / inverse (read) takes it
 int transform1d(Wavelet w, bool inverse, const void *src, void *dst, long line_stride, long elem_stride, int n_lines,
 	int so, int si, int *jp, int zero_padding); // level j runs on the fused sweeps (dense frame, both sides >= 2)
 // host-pointer calls on large images, band by band under their own PCIe transfers (dwt_host_xfer.hip):
 // 0 done, 1 error, -1 not applicable (the caller takes the plain path)
-int host_forward_pipelined(Wavelet w, const void *src, void *dst, int stride_x, int W, int H, int *jp, int decompose_one);
-int host_inverse_pipelined(Wavelet w, const void *src, void *dst, int stride_x, int W, int H, int j_max, int decompose_one);
+int host_forward_pipelined(const Call2d &c, const void *src, void *dst, int stride_x, int W, int H, int *jp, int decompose_one);
+int host_inverse_pipelined(const Call2d &c, const void *src, void *dst, int stride_x, int W, int H, int j_max, int decompose_one);
 // the stationary wavelet transform of rows (dwt_backend_swt.hip): device memory on every side, H of level l of line y at
 // dst_h + l*plane_stride + y*dls with elements h_es bytes apart, L by l_mode; level l at dilation 1 << (level0 + l)
 bool swt_fused_ok(const void *src, long ls, long es, int N);

@@ -21,7 +21,10 @@
 //
 // Frames with size_o != size_i, zero padding, and levels where a direction has a
 // single line follow the reference's exact line-by-line semantics through the
-// generic line-pass kernel, out of place per pass.
+// generic line-pass kernel, out of place per pass (generic_level).
+//
+// Which of the two a level takes is a function of the call alone: its entry builds a Call2d (call2d) from the wavelet and
+// the images the transform runs on, and the drivers, level_fused_ok and the tuners take that value as an argument.
 #include "dwt_backend.h"
 
 namespace dwtb {
@@ -44,14 +47,24 @@ int launched(hipError_t e, const char *family, const char *what)
 	return e == hipSuccess ? 0 : fail("%s %s launch failed: %s", family, what, hipGetErrorString(e));
 }
 
-int check_dev_align(std::initializer_list<const void *> ptrs, std::initializer_list<long> strides)
+static bool dword_aligned(std::initializer_list<const void *> ptrs, std::initializer_list<long> strides)
 {
 	bool ok = true;
 	for (const void *p : ptrs)
 		ok = ok && (uintptr_t)p % 4 == 0;
 	for (long s : strides)
 		ok = ok && s % 4 == 0;
-	return ok ? 0 : fail("device memory takes strides and addresses that are multiples of 4 bytes");
+	return ok;
+}
+
+int check_dev_align(std::initializer_list<const void *> ptrs, std::initializer_list<long> strides)
+{
+	return dword_aligned(ptrs, strides) ? 0 : fail("device memory takes strides and addresses that are multiples of 4 bytes");
+}
+
+Call2d call2d(Wavelet w, std::initializer_list<const void *> ptrs, std::initializer_list<long> strides)
+{
+	return Call2d{w, elem_size(w), dword_aligned(ptrs, strides)};
 }
 
 int grow(Buf &b, size_t need)
@@ -74,9 +87,6 @@ void drop(Buf &b)
 		dev_free(b.p);
 	b = Buf{};
 }
-
-
-bool skip_single(Wavelet w) { return w == kCdf97S; } // only the 9/7 drivers guard on lines > 1
 
 // several rectangles (element coordinates) between two device images in one kernel launch
 struct Rect {
@@ -101,9 +111,16 @@ static CopyRects make_copy_rects(Img dst, Img src, const Rect *rc, int n, int po
 	return r;
 }
 
-int copy_rects_on(hipStream_t st, Img dst, Img src, const Rect *rc, int n, int policy = 3)
+// the staged subbands of an in-place call between the image and the staging image: one launch of the rectangle kernel --
+// which moves whole dwords, so 2-byte elements go by plain 2-D copies
+static int copy_staged(Img dst, Img src, const Rect *rc, int n, int policy)
 {
-	return launched(launch_copy_rects(make_copy_rects(dst, src, rc, n, policy), st), "rectangle", "copy");
+	if (dst.es != 2)
+		return launched(launch_copy_rects(make_copy_rects(dst, src, rc, n, policy), g.stream), "rectangle", "copy");
+	for (int k = 0; k < n; k++)
+		if (copy_rect(dst, rc[k].dx, rc[k].dy, src, rc[k].sx, rc[k].sy, rc[k].w, rc[k].h))
+			return 1;
+	return 0;
 }
 
 // A rectangle copy that RIDES ALONG with the levels it does not depend on (one image, in place: the staged subbands of
@@ -164,7 +181,7 @@ int generic_pass(Wavelet w, bool inverse, bool rows, Img in, Img out, int frame_
 {
 	if (n_lines <= 0 || N <= 0)
 		return 0;
-	if (N == 1 && (w == kCdf53I || w == kCdf97I || w == kCdf53I16)) {
+	if (N == 1 && facts(w).lone) {
 		// the int kernels leave a lone sample as it is (src/libdwt.c:10961); out of place that
 		// still means the samples have to arrive in the destination
 		if (in.p != out.p)
@@ -257,29 +274,12 @@ int ensure_ll(const Geom &ge, int batch, int es)
 	return 0;
 }
 
-thread_local bool g_elems_are_32bit = true;
-thread_local int g_i16_call = 0;
-
-void call_elems(int es, std::initializer_list<const void *> ptrs, std::initializer_list<long> strides)
-{
-	g_elems_are_32bit = es == 4;
-	g_i16_call = 0;
-	if (es != 2)
-		return;
-	bool ok = true;
-	for (const void *p : ptrs)
-		ok = ok && (uintptr_t)p % 4 == 0;
-	for (long s : strides)
-		ok = ok && s % 4 == 0;
-	g_i16_call = ok ? 2 : 1;
-}
-
 // the fused sweeps exist for the 32-bit types and, since round 2, for the double-precision wavelets
 // (dwt_sweep2d_d.hip; option "fused_d" = 0 sends those back to the exact line passes); the int16 5/3 and the float 9/7 on
-// binary16 storage have their own (dwt_sweep2d_i16.hip, dwt_sweep2d_h.hip) for the calls that call_elems found aligned
-bool level_fused_ok(const Geom &ge, int j)
+// binary16 storage have their own (dwt_sweep2d_i16.hip, dwt_sweep2d_h.hip) for the calls whose images call2d found aligned
+bool level_fused_ok(const Call2d &c, const Geom &ge, int j)
 {
-	return !g.force_generic && (g_elems_are_32bit || (g_i16_call ? g_i16_call == 2 : g.fused_d != 0)) && ge.Wi(j) == ge.Wo(j) && ge.Hi(j) == ge.Ho(j) && ge.Wo(j) >= 2 &&
+	return !g.force_generic && (c.es == 4 || (c.es == 2 ? c.aligned : g.fused_d != 0)) && ge.Wi(j) == ge.Wo(j) && ge.Hi(j) == ge.Ho(j) && ge.Wo(j) >= 2 &&
 		ge.Ho(j) >= 2;
 }
 // Levels 0 and 1 of a forward transform in ONE launch (launch_fwd01: overlapped tiles, level 0's LL band never written):
@@ -295,10 +295,10 @@ bool level_fused_ok(const Geom &ge, int j)
 //     to win at (profiles/fuse01_summary.md).  Below 3072 tiles level 0 does not take the deep ring itself -- a round or
 //     two of waves wants the shallow ring's 8 waves per CU --; in between nothing was measured, and a call on 16 images
 //     of 8192^2 is held to one launch per level (tests/test_hip_multi.py).
-static bool pair01_ok(Wavelet w, const Geom &ge, int J, int batch)
+static bool pair01_ok(const Call2d &c, const Geom &ge, int J, int batch)
 {
 	const int W = ge.Wo(0), H = ge.Ho(0);
-	if (!g.fuse01 || g.fma || J < 2 || !level_fused_ok(ge, 0) || !level_fused_ok(ge, 1) || !fwd01_can(w, W, H))
+	if (!g.fuse01 || g.fma || J < 2 || !level_fused_ok(c, ge, 0) || !level_fused_ok(c, ge, 1) || !fwd01_can(c.w, W, H))
 		return false;
 	const SweepTuning &t = g.tune;
 	if (t.cpt == 4 || t.ring == 8 || (t.nt & 8) || (t.tile_pairs & 1))
@@ -337,8 +337,55 @@ static int half_level_end(Img fdst, Img dst, int Wo, int Ho)
 	return launched(launch_half_frame_cvt(false, dst.p, dst.sx, fdst.p, fdst.sx, Wo, Ho, g.stream), "binary16 frame", "narrowing");
 }
 
+// ---- one level on the exact line passes, both directions ---------------------------------
+// The Wo x Ho frame of `in` -> that of `out` (forward: the running image and dst; inverse: dst and dst); Wi x Hi: the
+// frame's inner sizes, (Wh, Hh): where the H halves start.  The passes run as the call's wavelet on its own images, or
+// (binary16 storage) as the float 9/7 on binary32 copies of the frame.  Zero padding stays with the drivers.
+static int generic_level(const Call2d &c, bool inverse, Img in, Img out, int Wo, int Ho, int Wi, int Hi, int Wh, int Hh)
+{
+	const WaveletFacts &f = facts(c.w);
+	const bool cols_first = inverse ? f.cols_inv : f.cols_fwd;
+	Img lc = in, ld = out;
+	if (widened(c.w) && half_level_begin(in, out, Wo, Ho, &lc, &ld))
+		return 1;
+	// dense frame: each pass writes every element of the level's frame, so the two passes
+	// ping-pong through the staging image (first pass: image -> stage, second: stage -> image)
+	// instead of each staging and copying back a frame of its own: 4 instead of 12 frame
+	// transfers per level (the double-precision drivers and accel 1 live on these passes)
+	const bool dense = Wi == Wo && Hi == Ho && Wo >= 2 && Ho >= 2;
+	if (dense && grow(g.stage_img, (size_t)ld.sx * Ho))
+		return 1;
+	for (int pass = 0; pass < 2; pass++) {
+		const bool rows = cols_first != (pass == 0);
+		if (f.skip1 && (rows ? Wo : Ho) <= 1)
+			continue;
+		const Img to = dense && pass == 0 ? Img{(char *)g.stage_img.p, ld.sx, ld.es} : ld;
+		if (generic_pass(f.line_as, inverse, rows, lc, to, Wo, Ho, rows ? Ho : Wo, rows ? Wi : Hi, rows ? Wh : Hh))
+			return 1;
+		lc = to; // the second pass reads what the first wrote -- the input itself where that one was skipped (src/libdwt.c:12709, :12742)
+	}
+	return widened(c.w) ? half_level_end(ld, out, Wo, Ho) : 0;
+}
+
+// ---- one fused level: the sweep of the call's element type -------------------------------
+static hipError_t sweep_fwd(const Call2d &c, const FwdLevelArgs &a, const SweepTuning &t, hipStream_t s)
+{
+	return c.es == 8 ? launch_fwd_level_d(c.w, a, t, s)
+	     : c.es == 4 ? launch_fwd_level(sweep32_wavelet(c.w), a, t, s)
+	     : widened(c.w) ? launch_fwd_level_h(c.w, a, t, s) // (2-byte elements: binary16 storage, or the int16 5/3)
+	                    : launch_fwd_level_i16(c.w, a, t, s);
+}
+
+static hipError_t sweep_inv(const Call2d &c, const InvLevelArgs &a, const SweepTuning &t, hipStream_t s)
+{
+	return c.es == 8 ? launch_inv_level_d(c.w, a, t, s)
+	     : c.es == 4 ? launch_inv_level(sweep32_wavelet(c.w), a, t, s)
+	     : widened(c.w) ? launch_inv_level_h(c.w, a, t, s)
+	                    : launch_inv_level_i16(c.w, a, t, s);
+}
+
 // ---- forward ---------------------------------------------------------------------
-int forward2d(Wavelet w, Img src, Img dst, const Geom &ge, int *jp, int decompose_one, int zero_padding,
+int forward2d(const Call2d &c, Img src, Img dst, const Geom &ge, int *jp, int decompose_one, int zero_padding,
 	int batch, long src_bstride, long dst_bstride)
 {
 	const int so_min = ge.sox < ge.soy ? ge.sox : ge.soy, so_max = ge.sox > ge.soy ? ge.sox : ge.soy;
@@ -348,9 +395,8 @@ int forward2d(Wavelet w, Img src, Img dst, const Geom &ge, int *jp, int decompos
 	const int J = *jp;
 	if (J == 0)
 		return 0;
-	const int es = elem_size(w);
-	const bool dbl = es == 8, i16 = es == 2, half = w == kCdf97H; // (i16: 2-byte elements, the int16 5/3 and the binary16 9/7)
-	const bool cols_first = w == kCdf53I16; // the int16 5/3 lifts the columns of a level before its rows (2D_SD)
+	const Wavelet w = c.w;
+	const int es = c.es;
 	if (ensure_ll(ge, batch, es))
 		return 1;
 
@@ -361,18 +407,18 @@ int forward2d(Wavelet w, Img src, Img dst, const Geom &ge, int *jp, int decompos
 	// the fused levels from j on that can carry copy blocks (one image, a sweep variant with the ride-along kernel)
 	auto carriers_from = [&](int j0) {
 		int n = 0;
-		for (int j = j0; j < J && level_fused_ok(ge, j); j++)
+		for (int j = j0; j < J && level_fused_ok(c, ge, j); j++)
 			n += es == 4 && sweep_ride_ok(g.tune, ge.Wo(j), ge.Ho(j), batch, false);
 		return n;
 	};
 	for (int j = 0; j < J; j++) {
 		const int Wo = ge.Wo(j), Ho = ge.Ho(j), Wi = ge.Wi(j), Hi = ge.Hi(j);
 		const int Wd = ge.Wo(j + 1), Hd = ge.Ho(j + 1);
-		if (level_fused_ok(ge, j)) {
+		if (level_fused_ok(c, ge, j)) {
 			// (a fused pair: levels 0 and 1 of an out-of-place call; jl: the level whose LL band leaves the launch)
-			const bool pair = j == 0 && ll_in < 0 && cur.p != dst.p && pair01_ok(w, ge, J, batch);
+			const bool pair = j == 0 && ll_in < 0 && cur.p != dst.p && pair01_ok(c, ge, J, batch);
 			const int jl = pair ? j + 1 : j;
-			const bool last = (jl == J - 1) || !level_fused_ok(ge, jl + 1);
+			const bool last = (jl == J - 1) || !level_fused_ok(c, ge, jl + 1);
 			FwdLevelArgs a;
 			a.W = Wo;
 			a.H = Ho;
@@ -427,11 +473,7 @@ int forward2d(Wavelet w, Img src, Img dst, const Geom &ge, int *jp, int decompos
 				ride.next = a.ride_hi;
 			}
 			prof_before(j);
-			hipError_t e = pair ? launch_fwd01(a, tune, g.stream)
-			             : dbl  ? launch_fwd_level_d(w, a, tune, g.stream)
-			             : half ? launch_fwd_level_h(w, a, tune, g.stream)
-			             : i16  ? launch_fwd_level_i16(w, a, tune, g.stream)
-			                    : launch_fwd_level((g.fma && w == kCdf97S) ? kCdf97SFma : w, a, tune, g.stream);
+			hipError_t e = pair ? launch_fwd01(a, tune, g.stream) : sweep_fwd(c, a, tune, g.stream);
 			prof_after(j);
 			if (e != hipSuccess)
 				return fail("forward level %d launch failed: %s", j, hipGetErrorString(e));
@@ -440,19 +482,14 @@ int forward2d(Wavelet w, Img src, Img dst, const Geom &ge, int *jp, int decompos
 				// quadrant too when it was written here (in line: on a side stream beside the deeper
 				// levels it measured 8-10 us slower, profiles/archive/r03_entries_summary.md)
 				const Rect rc[3] = {{Wd, 0, Wd, 0, Wo - Wd, Ho}, {0, Hd, 0, Hd, Wd, Ho - Hd}, {0, 0, 0, 0, last ? Wd : 0, Hd}};
-				if (i16) {
-					// (the rectangle kernel moves whole dwords: 2-byte elements go by plain 2-D copies)
-					for (const Rect &r : rc)
-						if (copy_rect(dst, r.dx, r.dy, hdst, r.sx, r.sy, r.w, r.h))
-							return 1;
-				} else {
+				if (es == 4) {
 					ride.r = make_copy_rects(dst, hdst, rc, 3, 3);
 					ride.total = copy_rects_plan(&ride.r);
 					ride.next = 0;
 					ride.on = g.ride_copy && ride.total > 0 && carriers_from(j + 1) > 0;
-					if (!ride.on && copy_rects_on(g.stream, dst, hdst, rc, 3))
-						return 1;
 				}
+				if (!ride.on && copy_staged(dst, hdst, rc, 3, 3))
+					return 1;
 			}
 			ll_in = ll_out;
 			cur = dst;
@@ -473,50 +510,9 @@ int forward2d(Wavelet w, Img src, Img dst, const Geom &ge, int *jp, int decompos
 			ll_in = -1;
 			cur = dst;
 		}
-		// the wavelet and the images the line passes of this level run on: the call's own, or (binary16 storage) the float
-		// 9/7 on binary32 copies of the level's frame
-		Wavelet wl = w;
-		Img lc = cur, ld = dst;
-		if (half) {
-			wl = kCdf97S;
-			if (half_level_begin(cur, dst, Wo, Ho, &lc, &ld))
-				return 1;
-		}
-		if (Wi == Wo && Hi == Ho && Wo >= 2 && Ho >= 2) {
-			// dense frame: each pass writes every element of the level's frame, so the two passes
-			// ping-pong through the staging image (rows: image -> stage, columns: stage -> image)
-			// instead of each staging and copying back a frame of its own: 4 instead of 12 frame
-			// transfers per level (the double-precision drivers and accel 1 live on these passes)
-			if (grow(g.stage_img, (size_t)ld.sx * Ho))
-				return 1;
-			const Img S{(char *)g.stage_img.p, ld.sx, ld.es};
-			if (cols_first ? (generic_pass(wl, false, false, lc, S, Wo, Ho, Wo, Hi, Hd) || generic_pass(wl, false, true, S, ld, Wo, Ho, Ho, Wi, Wd))
-			               : (generic_pass(wl, false, true, lc, S, Wo, Ho, Ho, Wi, Wd) || generic_pass(wl, false, false, S, ld, Wo, Ho, Wo, Hi, Hd)))
-				return 1;
-			lc = ld;
-		} else
-		for (int pass = 0; pass < 2; pass++) {
-			const bool rows = cols_first ? (pass == 1) : (pass == 0);
-			if (rows) {
-				if (!skip_single(wl) || Wo > 1) {
-					if (generic_pass(wl, false, true, lc, ld, Wo, Ho, Ho, Wi, Wd))
-						return 1;
-					lc = ld; // src/libdwt.c:12709
-				}
-			} else {
-				if (!skip_single(wl) || Ho > 1) {
-					if (generic_pass(wl, false, false, lc, ld, Wo, Ho, Wo, Hi, Hd))
-						return 1;
-					lc = ld; // src/libdwt.c:12742
-				}
-			}
-		}
-		if (half) {
-			if (half_level_end(ld, dst, Wo, Ho))
-				return 1;
-			cur = dst;
-		} else
-			cur = lc;
+		if (generic_level(c, false, cur, dst, Wo, Ho, Wi, Hi, Wd, Hd))
+			return 1;
+		cur = dst; // (a pass ran: a level has a side of 2 or more, and only a direction of ONE line is ever skipped)
 		if (zero_padding) {
 			// dwt_zero_padding_f_stride_* (src/libdwt.c:12079-12131) over rows then columns
 			const int nl_x = (Wi + 1) >> 1, nh_x = Wi >> 1, nl_y = (Hi + 1) >> 1, nh_y = Hi >> 1;
@@ -529,7 +525,7 @@ int forward2d(Wavelet w, Img src, Img dst, const Geom &ge, int *jp, int decompos
 }
 
 // ---- inverse ---------------------------------------------------------------------
-int inverse2d(Wavelet w, Img src, Img dst, const Geom &ge, int j_max, int decompose_one, int zero_padding,
+int inverse2d(const Call2d &c, Img src, Img dst, const Geom &ge, int j_max, int decompose_one, int zero_padding,
 	int batch, long src_bstride, long dst_bstride)
 {
 	const int so_min = ge.sox < ge.soy ? ge.sox : ge.soy, so_max = ge.sox > ge.soy ? ge.sox : ge.soy;
@@ -542,15 +538,14 @@ int inverse2d(Wavelet w, Img src, Img dst, const Geom &ge, int j_max, int decomp
 			return 1;
 		return 0;
 	}
-	const int es = elem_size(w);
-	const bool dbl = es == 8, i16 = es == 2, half = w == kCdf97H; // (i16: 2-byte elements, the int16 5/3 and the binary16 9/7)
+	const Wavelet w = c.w;
+	const int es = c.es;
 	if (ensure_ll(ge, batch, es))
 		return 1;
-	const bool cols_first = (w == kCdf53I || w == kCdf97I); // the int32 inverses undo columns first (the int16 5/3 rows: the mirror of its forward)
 
 	// reconstruction level j consumes the subbands of size ceil(.,j) and produces the
 	// band of size ceil(.,j-1); it is fused when that PRODUCED frame is dense and >= 2
-	auto fused_ok = [&](int j) { return level_fused_ok(ge, j - 1); };
+	auto fused_ok = [&](int j) { return level_fused_ok(c, ge, j - 1); };
 
 	Img cur = src;          // image holding the not-yet-consumed subbands
 	long cur_bstride = src_bstride;
@@ -617,12 +612,7 @@ int inverse2d(Wavelet w, Img src, Img dst, const Geom &ge, int j_max, int decomp
 						// (most of it went with the deeper levels' launches; what is left goes now)
 						if (ride.flush())
 							return 1;
-					} else if (i16) {
-						// (the rectangle kernel moves whole dwords: 2-byte elements go by plain 2-D copies)
-						for (const Rect &r : rc)
-							if (copy_rect(st, r.dx, r.dy, cur, r.sx, r.sy, r.w, r.h))
-								return 1;
-					} else if (copy_rects_on(g.stream, st, cur, rc, 3, /* temporal both ways: the final level reads the staged subbands (233 against 237 us) */ 0))
+					} else if (copy_staged(st, cur, rc, 3, /* temporal both ways: the final level reads the staged subbands (233 against 237 us) */ 0))
 						return 1;
 					a.in_h = st.p;
 					a.h_bstride = 0;
@@ -652,10 +642,7 @@ int inverse2d(Wavelet w, Img src, Img dst, const Geom &ge, int j_max, int decomp
 				ride.next = a.ride_hi;
 			}
 			prof_before(j - 1);
-			hipError_t e = dbl ? launch_inv_level_d(w, a, tune, g.stream)
-			             : half ? launch_inv_level_h(w, a, tune, g.stream)
-			             : i16 ? launch_inv_level_i16(w, a, tune, g.stream)
-			                   : launch_inv_level((g.fma && w == kCdf97S) ? kCdf97SFma : w, a, tune, g.stream);
+			hipError_t e = sweep_inv(c, a, tune, g.stream);
 			prof_after(j - 1);
 			if (e != hipSuccess)
 				return fail("inverse level %d launch failed: %s", j, hipGetErrorString(e));
@@ -681,38 +668,7 @@ int inverse2d(Wavelet w, Img src, Img dst, const Geom &ge, int j_max, int decomp
 				return 1;
 			ll_in = -1;
 		}
-		// (binary16 storage: the float 9/7 on a binary32 copy of the level's frame, as in the forward driver)
-		Wavelet wl = w;
-		Img ld = dst;
-		if (half) {
-			Img same;
-			wl = kCdf97S;
-			if (half_level_begin(dst, dst, Wo, Ho, &ld, &same))
-				return 1;
-		}
-		if (Wi == Wo && Hi == Ho && Wo >= 2 && Ho >= 2) {
-			// dense frame: ping-pong through the staging image, as in the forward driver
-			if (grow(g.stage_img, (size_t)ld.sx * Ho))
-				return 1;
-			const Img S{(char *)g.stage_img.p, ld.sx, ld.es};
-			const bool rows_first = !cols_first;
-			if (generic_pass(wl, true, rows_first, ld, S, Wo, Ho, rows_first ? Ho : Wo, rows_first ? Wi : Hi, rows_first ? Ws : Hs) ||
-				generic_pass(wl, true, !rows_first, S, ld, Wo, Ho, rows_first ? Wo : Ho, rows_first ? Hi : Wi, rows_first ? Hs : Ws))
-				return 1;
-		} else
-		for (int pass = 0; pass < 2; pass++) {
-			const bool rows = cols_first ? (pass == 1) : (pass == 0);
-			if (rows) {
-				if (!skip_single(wl) || Wo > 1)
-					if (generic_pass(wl, true, true, ld, ld, Wo, Ho, Ho, Wi, Ws))
-						return 1;
-			} else {
-				if (!skip_single(wl) || Ho > 1)
-					if (generic_pass(wl, true, false, ld, ld, Wo, Ho, Wo, Hi, Hs))
-						return 1;
-			}
-		}
-		if (half && half_level_end(ld, dst, Wo, Ho))
+		if (generic_level(c, true, dst, dst, Wo, Ho, Wi, Hi, Ws, Hs))
 			return 1;
 		if (zero_padding) {
 			// dwt_zero_padding_i_stride_* (src/libdwt.c:12161-12215)

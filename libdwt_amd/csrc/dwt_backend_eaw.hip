@@ -288,7 +288,6 @@ int eaw2d_checked(EawWavelet wv, int inverse, int layout, void *ptr, int stride_
 	const Geom ge{size_o_x, size_o_y, size_i_x, size_i_y};
 	if (eaw_levels(inverse != 0, ge, decompose_one, &jj) > 0 && !weights && size_o_x > 0 && size_o_y > 0)
 		return fail("null weights");
-	g_elems_are_32bit = true;
 	return eaw2d(wv, inverse != 0, layout, ptr, stride_x, stride_y, ge, j, decompose_one, zero_padding, weights, alpha);
 }
 
@@ -315,7 +314,6 @@ int eaw2d_batch_checked(EawWavelet wv, int inverse, void *ptr, size_t batch_stri
 		return fail("EAW batch: weights stride %zu floats, one image takes %ld", weights_stride, f.total);
 	if (batch == 0 || f.J == 0 || size_x == 0 || size_y == 0)
 		return 0;
-	g_elems_are_32bit = true;
 	return run_device(inverse != 0, f, Img{(char *)ptr, stride_x, 4}, batch, (long)batch_stride, weights, (long)weights_stride, 0, alpha);
 }
 

@@ -441,7 +441,6 @@ int dwt_hip_transform2d_interleaved(int wavelet, int inverse, int flavour, const
 		return fail("null pointer argument");
 	if (sox <= 0 || soy <= 0 || six < 0 || siy < 0 || six > sox || siy > soy)
 		return fail("bad sizes: outer %dx%d inner %dx%d", sox, soy, six, siy);
-	g_elems_are_32bit = true;
 	// single-sample lines: the 9/7 drivers and fdwt2_* leave them (guards `size > 1`,
 	// libdwt.c:12978, dwt-simple.c:2266), the 5/3 _inplace_ drivers scale them (:11041, :11840)
 	const bool scale_single = wavelet == kCdf53S && flavour == 0;

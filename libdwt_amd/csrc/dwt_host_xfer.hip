@@ -297,7 +297,7 @@ struct HostPin {
 // rows Hd + [A, B) that band [A, B)'s LH / HH rows will overwrite are uploaded together with the band itself, so
 // that no output lands on input that has not been read.  The deeper levels run on the complete low-pass band at the
 // end and its quadrant follows.  Returns 0 done, 1 error, -1 not applicable (the caller takes the plain path).
-int host_forward_pipelined(Wavelet w, const void *src, void *dst, int stride_x, int W, int H, int *jp, int decompose_one)
+int host_forward_pipelined(const Call2d &c, const void *src, void *dst, int stride_x, int W, int H, int *jp, int decompose_one)
 {
 	const Geom ge{W, H, W, H};
 	const int Hd = (H + 1) / 2, Wd = (W + 1) / 2, Hh = H / 2;
@@ -309,7 +309,7 @@ int host_forward_pipelined(Wavelet w, const void *src, void *dst, int stride_x, 
 	const int n_bands = (Hd + kBand - 1) / kBand;
 	// (decompose_one: the levels past the shorter side's last run on the generic passes, which borrow the buffers used here;
 	// a tile height set by hand must divide the band: tiles do not straddle bands)
-	if (!g.host_pipeline || decompose_one || kBand % 64 || (g.tune.tile_pairs > 0 && kBand % g.tune.tile_pairs) || elem_size(w) != 4 || !level_fused_ok(ge, 0) || (size_t)W * H * 4 < ((size_t)64 << 20) || n_bands < 2 || n_bands > 16 ||
+	if (!g.host_pipeline || decompose_one || kBand % 64 || (g.tune.tile_pairs > 0 && kBand % g.tune.tile_pairs) || c.es != 4 || !level_fused_ok(c, ge, 0) || (size_t)W * H * 4 < ((size_t)64 << 20) || n_bands < 2 || n_bands > 16 ||
 		stride_x % 4 || stride_x < W * 4)
 		return -1;
 	const int j_lim = ceil_log2(decompose_one ? (W > H ? W : H) : (W < H ? W : H));
@@ -437,7 +437,7 @@ int host_forward_pipelined(Wavelet w, const void *src, void *dst, int stride_x, 
 			}
 			a.W = W; a.H = H; a.batch = 1;
 			a.pair_lo = P0; a.pair_hi = P1 == Hd ? Hd + kBand : P1;
-			hipError_t e = launch_fwd_level((g.fma && w == kCdf97S) ? kCdf97SFma : w, a, g.tune, g.stream);
+			hipError_t e = launch_fwd_level(sweep32_wavelet(c.w), a, g.tune, g.stream);
 			if (e != hipSuccess)
 				return fail("forward level 0 (band %d) launch failed: %s", b, hipGetErrorString(e));
 			// level 1 on the rows of the low-pass band that are complete now (its tiles read up to row 2 hi + 2)
@@ -455,7 +455,7 @@ int host_forward_pipelined(Wavelet w, const void *src, void *dst, int stride_x, 
 					}
 					a1.W = Wd; a1.H = Hd; a1.batch = 1;
 					a1.pair_lo = lo1; a1.pair_hi = hi1 == Hd1 ? Hd1 + kBand : hi1;
-					e = launch_fwd_level((g.fma && w == kCdf97S) ? kCdf97SFma : w, a1, g.tune, g.stream);
+					e = launch_fwd_level(sweep32_wavelet(c.w), a1, g.tune, g.stream);
 					if (e != hipSuccess)
 						return fail("forward level 1 (band %d) launch failed: %s", b, hipGetErrorString(e));
 					done1 = hi1;
@@ -487,7 +487,7 @@ int host_forward_pipelined(Wavelet w, const void *src, void *dst, int stride_x, 
 			if (J > 2) {
 				int j2 = J - 2;
 				const Geom gl{Wd1, Hd1, Wd1, Hd1};
-				if (forward2d(w, Img{(char *)ll1, llp1 * 4, 4}, Img{B, pitch, 4}, gl, &j2, decompose_one, 0, 1, 0, 0))
+				if (forward2d(c, Img{(char *)ll1, llp1 * 4, 4}, Img{B, pitch, 4}, gl, &j2, decompose_one, 0, 1, 0, 0))
 					return 1;
 			}
 		}
@@ -524,7 +524,7 @@ int host_forward_pipelined(Wavelet w, const void *src, void *dst, int stride_x, 
 // follow; band [P0, P1) of level 0 needs the HL rows up to P1 + 2 and the LH | HH rows up to Hd + P1 + 2, and its
 // result -- rows [2 P0, 2 P1) of the image -- comes down at once.  In place that result overwrites coefficient rows:
 // every row below 2 P1 goes up before it (a band's uploads run ahead of its own needs by that much).
-int host_inverse_pipelined(Wavelet w, const void *src, void *dst, int stride_x, int W, int H, int j_max, int decompose_one)
+int host_inverse_pipelined(const Call2d &c, const void *src, void *dst, int stride_x, int W, int H, int j_max, int decompose_one)
 {
 	const Geom ge{W, H, W, H};
 	const int Hd = (H + 1) / 2, Wd = (W + 1) / 2, Hh = H / 2;
@@ -533,7 +533,7 @@ int host_inverse_pipelined(Wavelet w, const void *src, void *dst, int stride_x, 
 	const int n_bands = (Hd + kBand - 1) / kBand;
 	// (decompose_one: the levels past the shorter side's last run on the generic passes, which borrow the buffers used here;
 	// a tile height set by hand must divide the band: tiles do not straddle bands)
-	if (!g.host_pipeline || decompose_one || kBand % 64 || (g.tune.tile_pairs > 0 && kBand % g.tune.tile_pairs) || elem_size(w) != 4 || !level_fused_ok(ge, 0) || (size_t)W * H * 4 < ((size_t)64 << 20) || n_bands < 2 || n_bands > 16 ||
+	if (!g.host_pipeline || decompose_one || kBand % 64 || (g.tune.tile_pairs > 0 && kBand % g.tune.tile_pairs) || c.es != 4 || !level_fused_ok(c, ge, 0) || (size_t)W * H * 4 < ((size_t)64 << 20) || n_bands < 2 || n_bands > 16 ||
 		stride_x % 4 || stride_x < W * 4)
 		return -1;
 	int J = ceil_log2(decompose_one ? (W > H ? W : H) : (W < H ? W : H));
@@ -583,7 +583,7 @@ int host_inverse_pipelined(Wavelet w, const void *src, void *dst, int stride_x, 
 		long ll_pitch = pitch / 4;
 		if (J > 1) {
 			const Geom gl{Wd, Hd, Wd, Hd};
-			if (inverse2d(w, Img{A, pitch, 4}, Img{(char *)g.stage_img.p, llp * 4, 4}, gl, J - 1, decompose_one, 0, 1, 0, 0))
+			if (inverse2d(c, Img{A, pitch, 4}, Img{(char *)g.stage_img.p, llp * 4, 4}, gl, J - 1, decompose_one, 0, 1, 0, 0))
 				return 1;
 			ll = g.stage_img.p;
 			ll_pitch = llp;
@@ -611,7 +611,7 @@ int host_inverse_pipelined(Wavelet w, const void *src, void *dst, int stride_x, 
 			a.in_ll = ll; a.ll_pitch = ll_pitch; a.ll_bstride = 0;
 			a.out = B; a.out_pitch = pitch / 4; a.out_bstride = 0;
 			a.pair_lo = P0; a.pair_hi = last ? Hd + kBand : P1;
-			hipError_t e = launch_inv_level((g.fma && w == kCdf97S) ? kCdf97SFma : w, a, g.tune, g.stream);
+			hipError_t e = launch_inv_level(sweep32_wavelet(c.w), a, g.tune, g.stream);
 			if (e != hipSuccess)
 				return fail("inverse level 1 (band %d) launch failed: %s", b, hipGetErrorString(e));
 			HIP_TRY(hipEventRecord(g.pipe_ev[1][b], g.stream));

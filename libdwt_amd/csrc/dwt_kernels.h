@@ -13,8 +13,36 @@ enum Wavelet { kCdf97S = 0, kCdf53I = 1, kCdf53S = 2, kCdf97D = 3, kCdf53D = 4, 
 	kInterp53S = 9 /* interpolating 5/3 float (public id DWT_HIP_INTERP53_S = 6): predict step only */,
 	kCdf53I16 = 10 /* reversible int16 5/3 in JPEG 2000 order (public id DWT_HIP_CDF53_I16 = 8): columns before rows */,
 	kCdf97H = 11 /* float 9/7 on binary16 storage (public id DWT_HIP_CDF97_H = 9): binary32 arithmetic, one rounding per level */ };
+constexpr int kWavelets = kCdf97H + 1; // one past the LAST enumerator: a new one moves this, and the table below then wants its row
 
-inline int elem_size(Wavelet w) { return (w == kCdf97D || w == kCdf53D) ? 8 : (w == kCdf53I16 || w == kCdf97H) ? 2 : 4; }
+// What the drivers branch on per wavelet, one row per enumerator in its order.  id: the public one (enum dwt_hip_wavelet),
+// -1 internal only.  cols_fwd / cols_inv: a level's exact column pass comes before its row pass.  lone: a line of one sample
+// is passed through untouched (the int kernels, src/libdwt.c:10961).  skip1: a direction that has one line is skipped (only
+// the 9/7 drivers guard on lines > 1).  line_as: the wavelet the exact line passes run as -- another one: on a binary32 copy
+// of the level's frame, widened before the passes and narrowed after them.
+struct WaveletFacts {
+	int es, id;
+	bool cols_fwd, cols_inv, lone, skip1;
+	Wavelet line_as;
+};
+constexpr WaveletFacts kWaveletFacts[] = {
+	{4, 0, false, false, false, true, kCdf97S},
+	{4, 1, false, true, true, false, kCdf53I}, // (the int32 inverses undo columns first)
+	{4, 2, false, false, false, false, kCdf53S},
+	{8, 3, false, false, false, false, kCdf97D},
+	{8, 4, false, false, false, false, kCdf53D},
+	{4, 5, false, true, true, false, kCdf97I},
+	{4, -1, false, false, false, false, kCdf97SFma},
+	{4, -1, false, false, false, false, kCdf53SNew},
+	{4, -1, false, false, false, false, kCdf97IIp},
+	{4, 6, false, false, false, false, kInterp53S},
+	{2, 8, true, false, true, false, kCdf53I16}, // (2D_SD: columns before rows forward, the mirror inverse)
+	{2, 9, false, false, false, true, kCdf97S},
+};
+static_assert(sizeof(kWaveletFacts) / sizeof(kWaveletFacts[0]) == kWavelets, "a row of kWaveletFacts for every enumerator of Wavelet");
+constexpr const WaveletFacts &facts(Wavelet w) { return kWaveletFacts[w]; }
+inline int elem_size(Wavelet w) { return facts(w).es; }
+constexpr bool widened(Wavelet w) { return facts(w).line_as != w; }
 
 // Tuning knobs of the fused sweep kernels (set through dwt_hip_set_option).
 struct SweepTuning {

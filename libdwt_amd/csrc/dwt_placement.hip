@@ -426,9 +426,9 @@ struct TrialLL {
 	}
 };
 
-static int alloc_batch_arena(Wavelet w, int n_images, int size_x, int size_y, int levels, void **src_out, void **dst_out)
+static int alloc_batch_arena(const Call2d &c, int n_images, int size_x, int size_y, int levels, void **src_out, void **dst_out)
 {
-	const int es = elem_size(w);
+	const int es = c.es;
 	const size_t pitch = (size_t)size_x * es, img = pitch * size_y, total = img * n_images;
 	const Geom ge{size_x, size_y, size_x, size_y};
 	ArenaJob job;
@@ -444,11 +444,11 @@ static int alloc_batch_arena(Wavelet w, int n_images, int size_x, int size_y, in
 		// (a one-level call never touches the scratch; the context is pointed at the source region so that
 		// it does not allocate one of its own meanwhile)
 		TrialLL t(s, total, s, total);
-		return timed_forward(w, Img{s, (long)pitch, es}, Img{d, (long)pitch, es}, ge, 1, n_images, (long)img, (long)img, ms);
+		return timed_forward(c, Img{s, (long)pitch, es}, Img{d, (long)pitch, es}, ge, 1, n_images, (long)img, (long)img, ms);
 	};
 	job.full = [&](char *s, char *d, char *const *ws, double *ms) {
 		TrialLL t(ws[0], cap0, ws[1], cap1);
-		return timed_forward(w, Img{s, (long)pitch, es}, Img{d, (long)pitch, es}, ge, levels, n_images, (long)img, (long)img, ms);
+		return timed_forward(c, Img{s, (long)pitch, es}, Img{d, (long)pitch, es}, ge, levels, n_images, (long)img, (long)img, ms);
 	};
 	void *out[4] = {nullptr, nullptr, nullptr, nullptr};
 	const int rc = arena_place(job, out);
@@ -585,7 +585,6 @@ int dwt_hip_alloc_batch(int wavelet, int n_images, int size_x, int size_y, int l
 	if (!wavelet_of(wavelet, &w) || n_images < 1 || n_images > 65535 || size_x < 1 || size_y < 1 || !src_out || !dst_out)
 		return fail("dwt_hip_alloc_batch: bad argument");
 	const int es = elem_size(w);
-	call_elems(es, {}, {(long)size_x * es, (long)size_x * es * size_y});
 	const size_t total = (size_t)size_x * es * size_y * n_images;
 	const Geom ge{size_x, size_y, size_x, size_y};
 	g_arena = ArenaStats();
@@ -593,7 +592,8 @@ int dwt_hip_alloc_batch(int wavelet, int n_images, int size_x, int size_y, int l
 	const bool search = g.place_tries >= 2 && total >= ((size_t)g.place_min_mib << 20) && ge.Wo(2) >= 2 && ge.Ho(2) >= 2 && !g.ll_external &&
 		!g.force_generic && es == 4 && !stream_is_capturing();
 	if (search) {
-		const int rc = alloc_batch_arena(w, n_images, size_x, size_y, levels, src_out, dst_out);
+		// (the trials are forward calls on the arena's dense images)
+		const int rc = alloc_batch_arena(call2d(w, {}, {(long)size_x * es, (long)size_x * es * size_y}), n_images, size_x, size_y, levels, src_out, dst_out);
 		if (rc >= 0)
 			return rc;
 	} else {

@@ -16,7 +16,7 @@
 //     dwords (forward: two 8-byte loads; inverse: three dwords and a sample); lanes at a row's ends, and rows whose
 //     subband starts at an odd sample, fetch it sample by sample through reflected indices.
 //   - LINE ENDS by reflection: Cdf97H has no end forms (dwt_lift.h says why the bits are the reference's).
-//   - ALIGNMENT as in the int16 sweeps: bases, pitches and batch strides are multiples of 4 bytes (call_elems), a lane's
+//   - ALIGNMENT as in the int16 sweeps: bases, pitches and batch strides are multiples of 4 bytes (call2d), a lane's
 //     own bytes of an image row are dword-aligned; the subbands right of the LL / LH quarter start at sample ceil(W/2)
 //     and are accessed sample by sample where that is odd (a test on the address, uniform over the wave).
 #include "dwt_sweep2d.h"

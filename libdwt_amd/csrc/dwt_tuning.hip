@@ -117,7 +117,7 @@ int tuned_tile_pairs(Wavelet w, const FwdLevelArgs &a)
 {
 	if (!tunable(a.W, a.H, a.batch, a.interleaved))
 		return 0;
-	const Wavelet wk = (g.fma && w == kCdf97S) ? kCdf97SFma : w;
+	const Wavelet wk = sweep32_wavelet(w);
 	// (round 5 also tried 128 pairs and the 256-column tile with the deep ring: never the fastest on a batch, and on one
 	// image -- 100.5 against 105.1 us in a variant scan -- inside the noise of where the image lies; scripts/r05/tuned_single.py)
 	return tune_tile_pairs(tile_key(w, false, a.W, a.H, a.batch), false, {{64, 0, 0}, {32, 0, 0}, {16, 0, 0}},
@@ -139,7 +139,7 @@ int tuned_tile_pairs(Wavelet w, const InvLevelArgs &a)
 {
 	if (!tunable(a.W, a.H, a.batch, a.interleaved))
 		return 0;
-	const Wavelet wk = (g.fma && w == kCdf97S) ? kCdf97SFma : w;
+	const Wavelet wk = sweep32_wavelet(w);
 	// (round 6: the 512-column tile joins the candidates; the launcher's rule is 16 pairs)
 	return tune_tile_pairs(tile_key(w, true, a.W, a.H, a.batch), true, {{16, 0, 0}, {32, 0, 0}, {8, 0, 0}, {16, 8, 0}, {32, 8, 0}},
 		[&](const SweepTuning &t) { return launch_inv_level(wk, a, t, g.stream); });
@@ -153,7 +153,7 @@ int tuned_tile_pairs(Wavelet w, const InvLevelArgs &a)
 // it into other physical memory, times the call itself on each (it writes exactly what the call will
 // write: idempotent for distinct source and destination), and keeps the fastest.  Once per
 // size: later calls find the scratch in place, allocate nothing and never synchronise.
-int timed_forward(Wavelet w, Img s, Img d, const Geom &ge, int levels, int batch, long sb, long db, double *ms)
+int timed_forward(const Call2d &c, Img s, Img d, const Geom &ge, int levels, int batch, long sb, long db, double *ms)
 {
 	hipEvent_t e0, e1;
 	HIP_TRY(hipEventCreate(&e0));
@@ -163,7 +163,7 @@ int timed_forward(Wavelet w, Img s, Img d, const Geom &ge, int levels, int batch
 	for (int r = 0; r < 2 && !rc; r++) {
 		int j = levels;
 		hipEventRecord(e0, g.stream);
-		rc = forward2d(w, s, d, ge, &j, 0, 0, batch, sb, db);
+		rc = forward2d(c, s, d, ge, &j, 0, 0, batch, sb, db);
 		hipEventRecord(e1, g.stream);
 	}
 	g.placing = false;
@@ -192,9 +192,9 @@ bool stream_is_capturing()
 	return st != hipStreamCaptureStatusNone;
 }
 
-int place_ll_scratch(Wavelet w, Img s, Img d, const Geom &ge, int levels, int batch, long sb, long db)
+int place_ll_scratch(const Call2d &call, Img s, Img d, const Geom &ge, int levels, int batch, long sb, long db)
 {
-	const int es = elem_size(w);
+	const int es = call.es;
 	const size_t need[2] = {ll_band_bytes(ge, 0, batch, es), ll_band_bytes(ge, 1, batch, es)};
 	g.place_n = 0;
 	g.place_best = -1;
@@ -242,7 +242,7 @@ int place_ll_scratch(Wavelet w, Img s, Img d, const Geom &ge, int levels, int ba
 		}
 		for (int b = 0; b < 2; b++)
 			g.ll[b] = Buf{c.ll[b], need[b]};
-		rc = timed_forward(w, s, d, ge, levels, batch, sb, db, &c.ms);
+		rc = timed_forward(call, s, d, ge, levels, batch, sb, db, &c.ms);
 		c.ok = rc == 0; // (a trial that failed has no time: never the best)
 		cands.push_back(c);
 	}
@@ -272,7 +272,7 @@ int place_ll_scratch(Wavelet w, Img s, Img d, const Geom &ge, int levels, int ba
 
 // the body of dwt_hip_tune: placement search of the scratch (forward, large batches), then ONE transform with the
 // tile tuner switched on -- every large level measures its tile heights on the way and the context keeps them
-int tune2d(Wavelet w, bool inverse, Img s, Img d, const Geom &ge, int levels, int batch, long sb, long db)
+int tune2d(const Call2d &c, bool inverse, Img s, Img d, const Geom &ge, int levels, int batch, long sb, long db)
 {
 	std::lock_guard<std::recursive_mutex> turn(measure_mutex());
 	struct Guard {
@@ -281,10 +281,10 @@ int tune2d(Wavelet w, bool inverse, Img s, Img d, const Geom &ge, int levels, in
 	} guard;
 	if (stream_is_capturing())
 		return fail("dwt_hip_tune measures and synchronises: not under a stream capture");
-	if (!inverse && (levels < 0 || levels >= 2) && place_ll_scratch(w, s, d, ge, levels, batch, sb, db))
+	if (!inverse && (levels < 0 || levels >= 2) && place_ll_scratch(c, s, d, ge, levels, batch, sb, db))
 		return 1;
 	int j = levels;
-	const int rc = inverse ? inverse2d(w, s, d, ge, levels, 0, 0, batch, sb, db) : forward2d(w, s, d, ge, &j, 0, 0, batch, sb, db);
+	const int rc = inverse ? inverse2d(c, s, d, ge, levels, 0, 0, batch, sb, db) : forward2d(c, s, d, ge, &j, 0, 0, batch, sb, db);
 	if (!rc)
 		HIP_TRY(hipStreamSynchronize(g.stream));
 	return rc;
@@ -313,11 +313,11 @@ int dwt_hip_tune(int wavelet, int inverse, const void *src, void *dst, size_t ba
 		batch_stride = (size_t)stride_x * size_y;
 	if ((stride_x % es) || stride_x < size_x * es || (batch_stride % es) || batch_stride < (size_t)stride_x * size_y)
 		return fail("bad strides");
-	call_elems(es, {src, dst}, {(long)stride_x, (long)batch_stride});
-	if (src == dst || g_i16_call == 1)
+	const Call2d c = call2d(w, {src, dst}, {(long)stride_x, (long)batch_stride});
+	if (src == dst || c.line_passes_only())
 		return 0; // (the in-place entries stage level 0, the line passes have no choices: nothing of theirs is measured)
 	const Geom ge{size_x, size_y, size_x, size_y};
-	return tune2d(w, inverse != 0, Img{(char *)src, stride_x, es}, Img{(char *)dst, stride_x, es}, ge, levels, batch, (long)batch_stride,
+	return tune2d(c, inverse != 0, Img{(char *)src, stride_x, es}, Img{(char *)dst, stride_x, es}, ge, levels, batch, (long)batch_stride,
 		(long)batch_stride);
 }
 
