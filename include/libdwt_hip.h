@@ -26,7 +26,15 @@
  * GPUs with one thread per device: each thread calls dwt_hip_set_device(d) first.  Options
  * (dwt_hip_set_option, dwt_util_set_accel) and dwt_hip_set_stream are per thread as well.
  * Calls are asynchronous for device pointers (stream-ordered on the stream given to
- * dwt_hip_set_stream) and synchronous for host pointers.
+ * dwt_hip_set_stream) and synchronous for host pointers.  A call whose pointers are all device memory
+ * still WAITS for its stream where a value has to reach the host first, each said at its entry: the
+ * feature entries (dwt_hip_features2d / _2d_batch / _1d_batch, dwt_hip_swt_features1d_batch: the sums are
+ * finished on the host) and dwt_hip_rows_condition on its per-operation route (one flag per centring
+ * iteration).  An entry that takes a small per-row array in either memory space (info, center, min, max, displ)
+ * waits exactly when that array is host memory.  The results that are host memory by definition make their calls
+ * wait as well: dwt_hip_universal_threshold_batch always (lambda), dwt_hip_keep_largest_batch / _keep_largest
+ * whenever thr or kept is not NULL.  tests/test_hip_streams.py holds every entry to this on a busy stream
+ * (DESIGN.md s23).
  *
  * Error rule: every int function returns 0 on success and non-zero on failure with
  * a message retrievable by dwt_hip_last_error().  There is NO CPU fallback: without
@@ -328,7 +336,8 @@ int dwt_hip_is_device_pointer(const void *p);
  * The bands are those of dwt_util_subband for levels 1 .. j_max-1 (level j_max itself is not visited, as in the
  * reference), HL, LH, HH within a level, empty bands skipped: dwt_hip_count_subbands of them.
  * `fv` receives one block of that many floats per feature of the mask, in enum order.  It lies in the memory space of
- * `ptr` (both host or both device); device calls are ordered on the context's stream.
+ * `ptr` (both host or both device); device calls are ordered on the context's stream and wait for it: the raw sums
+ * come back to the host, are finished there and go out to `fv` before the call returns.
  * Numerics: maxnorm, maxidx and med are the reference's values for every NaN-free input (med as a value: which of +0 /
  * -0 stands in the middle of equal zeros is unspecified; behaviour on NaN inputs is not pinned, the reference's
  * qsort comparator being no order there).  Sums accumulate in double in a fixed order -- the same bits on every run
@@ -382,7 +391,8 @@ int dwt_hip_abs(void *ptr, int stride_x, int stride_y, int size_x, int size_y);
  * ptr + y*line_stride + i*elem_stride (bytes), in host or device memory; rows are conditioned in place.  Dense device
  * rows of up to 8192 samples take ONE launch whatever the iteration count, up to the batch size from which one kernel per
  * operation is faster (option "cond_fused" = 1 / 0 forces either route, -1 restores the choice; same bits).  The per-row arrays (info, center, min, max, displ) may each be host
- * or device memory.
+ * or device memory.  The one-launch route with `info` NULL or in device memory does not wait for the device; the
+ * per-operation route with CENTER reads one flag back after every centring iteration and so waits for its stream.
  *   MED_SHIFT  x += -median, the median being the element of rank size/2 of the row's signed values;
  *   CENTER     up to max_iters times: c = the row's centre; stop if c == size/2, else row[x] = row[x + c - size/2] with
  *              zeros moving in (samples moved out are lost: the iterations are not one shift of the original row);
@@ -557,7 +567,8 @@ int dwt_hip_swt2d_level(int wavelet, const void *src, int stride_x, int stride_y
 /* The feature statistics of the transform's planes without the planes: feature k of the mask (enum order) of level l of
  * line y at fv[y*fv_line_stride + k*levels + l] (floats).  band 0: the H planes, 1: the L planes.  Each value is what
  * dwt_util_band_<name>_s(plane, 0, sizeof(float), N, 1[, p]) gives for that plane, wps with j = l.  fv lies where src
- * lies (host or device).  Lines the one-launch kernel takes are reduced in that launch and no coefficient is stored. */
+ * lies (host or device).  Lines the one-launch kernel takes are reduced in that launch and no coefficient is stored.  Like
+ * the other feature entries the call waits for its stream: the sums are finished on the host. */
 int dwt_hip_swt_features1d_batch(int wavelet, unsigned feature_mask, const void *src, size_t line_stride, size_t elem_stride,
 	int n_lines, int N, int levels, int band, float p, float *fv, int fv_line_stride);
 
