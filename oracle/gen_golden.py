@@ -294,9 +294,48 @@ def gen_float_range(ref, manifest):
     print(path, os.path.getsize(path), "bytes", len(meta), "cases")
 
 
+# ---- inputs that do not turn to NaN: tests/floatends.py (finite_floats, ends_floats) ----
+# every float entry, forward and the inverse OF THE INPUT ITSELF (a coefficient image of the class), by the reference;
+# "finite" at full depth, "ends" at the depth floatends.ends_level picks with the oracle (2 where the NaN share allows)
+def gen_float_ends(ref, manifest):
+    import warnings
+
+    import floatends as F
+    from oraclelib import Oracle
+
+    warnings.simplefilter("ignore")
+    orc = Oracle()
+    arrays, meta = {}, []
+    seed = 12000
+    for e, klass, shp, d1, full in F.case_list():
+        seed += 1
+        m = {"entry": e, "klass": klass, "shape": shp, "seed": seed, "decompose_one": d1, "full": full}
+        src = F.case_input(m)
+        j = -1 if klass == "finite" else F.ends_level(orc, e, src, d1)
+        fwd, jret = F.transform(ref, e, 0, src, j, d1)
+        inv, _ = F.transform(ref, e, 1, src, jret, d1)
+        name = f"{e}.{klass}.{'x'.join(map(str, shp))}"
+        m.update({"name": name, "j_in": j, "j_out": jret,
+                  "sha": {"in": canonical_sha(src), "fwd": canonical_sha(fwd), "inv": canonical_sha(inv)}})
+        if full:
+            arrays[name + ".in"], arrays[name + ".fwd"], arrays[name + ".inv"] = src, fwd, inv
+        meta.append(m)
+    path = os.path.join(OUT, "float_ends.npz")
+    np.savez_compressed(path, **arrays)
+    manifest["files"]["float_ends.npz"] = {"sha256": hashlib.sha256(open(path, "rb").read()).hexdigest(), "cases": meta}
+    print(path, os.path.getsize(path), "bytes", len(meta), "cases")
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     ref = Reference()
+    if sys.argv[1:] == ["float_ends"]:
+        with open(os.path.join(OUT, "manifest.json")) as f:
+            manifest = json.load(f)
+        gen_float_ends(ref, manifest)
+        with open(os.path.join(OUT, "manifest.json"), "w") as f:
+            json.dump(manifest, f, indent=1)
+        return
     if sys.argv[1:] == ["volumes"]:
         with open(os.path.join(OUT, "manifest.json")) as f:
             manifest = json.load(f)
@@ -431,6 +470,7 @@ def main():
     gen_multichannel(ref, manifest)
     gen_volumes(ref, manifest)
     gen_float_range(ref, manifest)
+    gen_float_ends(ref, manifest)
 
     with open(os.path.join(OUT, "manifest.json"), "w") as f:
         json.dump(manifest, f, indent=1)

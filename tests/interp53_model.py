@@ -18,6 +18,12 @@ P1 = np.float32(0.5)
 S1 = np.float32(1.41421356237309504880)
 S2 = np.float32(0.70710678118654752440)
 TWO_P1 = np.float32(2) * P1  # `2 * dwt_cdf53_p1_s`, a float
+REFLECTED_ENDS = False  # True: the doubled tap as reflection gives it, p*(x+x) (tests/floatends.py counts against it)
+
+
+def end2(x):
+    """The two equal taps of the last odd sample of an even line: the reference's (2p)*x."""
+    return P1 * (x + x) if REFLECTED_ENDS else TWO_P1 * x
 
 
 def ceil_log2(x):
@@ -44,7 +50,7 @@ def fwd_lines(t):
     # the odd samples depend on the even ones only: the reference's loop order does not matter
     t[:, odd] = t[:, odd] - P1 * (t[:, odd - 1] + t[:, odd + 1])
     if N % 2 == 0:
-        t[:, N - 1] = t[:, N - 1] - TWO_P1 * t[:, N - 2]
+        t[:, N - 1] = t[:, N - 1] - end2(t[:, N - 2])
     t[:, 0::2] = t[:, 0::2] * S1
     t[:, 1::2] = t[:, 1::2] * S2
     return t
@@ -61,7 +67,7 @@ def inv_lines(t):
     t[:, 0::2] = t[:, 0::2] * S2
     t[:, 1::2] = t[:, 1::2] * S1
     if N % 2 == 0:
-        t[:, N - 1] = t[:, N - 1] + TWO_P1 * t[:, N - 2]
+        t[:, N - 1] = t[:, N - 1] + end2(t[:, N - 2])
     odd = np.arange(1, N - 2 + (N & 1), 2)
     t[:, odd] = t[:, odd] + P1 * (t[:, odd - 1] + t[:, odd + 1])
     return t
