@@ -28,13 +28,13 @@
  * Calls are asynchronous for device pointers (stream-ordered on the stream given to
  * dwt_hip_set_stream) and synchronous for host pointers.  A call whose pointers are all device memory
  * still WAITS for its stream where a value has to reach the host first, each said at its entry: the
- * feature entries (dwt_hip_features2d / _2d_batch / _1d_batch, dwt_hip_swt_features1d_batch: the sums are
- * finished on the host) and dwt_hip_rows_condition on its per-operation route (one flag per centring
- * iteration).  An entry that takes a small per-row array in either memory space (info, center, min, max, displ)
- * waits exactly when that array is host memory.  The results that are host memory by definition make their calls
- * wait as well: dwt_hip_universal_threshold_batch always (lambda), dwt_hip_keep_largest_batch / _keep_largest
- * whenever thr or kept is not NULL.  tests/test_hip_streams.py holds every entry to this on a busy stream
- * (DESIGN.md s23).
+ * feature entries (dwt_hip_features2d / _2d_batch / _1d_batch, dwt_hip_swt_features1d_batch,
+ * dwt_hip_wp_features1d_batch / _2d_batch: the sums are finished on the host) and dwt_hip_rows_condition on
+ * its per-operation route (one flag per centring iteration).  An entry that takes a small per-row array in
+ * either memory space (info, center, min, max, displ) waits exactly when that array is host memory.  The
+ * results that are host memory by definition make their calls wait as well:
+ * dwt_hip_universal_threshold_batch always (lambda), dwt_hip_keep_largest_batch / _keep_largest whenever thr or
+ * kept is not NULL.  tests/test_hip_streams.py holds every entry to this on a busy stream.
  *
  * Error rule: every int function returns 0 on success and non-zero on failure with
  * a message retrievable by dwt_hip_last_error().  There is NO CPU fallback: without
@@ -571,6 +571,53 @@ int dwt_hip_swt2d_level(int wavelet, const void *src, int stride_x, int stride_y
  * the other feature entries the call waits for its stream: the sums are finished on the host. */
 int dwt_hip_swt_features1d_batch(int wavelet, unsigned feature_mask, const void *src, size_t line_stride, size_t elem_stride,
 	int n_lines, int N, int levels, int band, float p, float *fv, int fv_line_stride);
+
+/* Wavelet packet transforms of row and image batches: every node is split again at every level, not only
+ * the L node.  An extension: the reference has no packet driver; a packet level is its own one-level transform applied to
+ * each node.  `wavelet` is DWT_HIP_CDF97_S, DWT_HIP_CDF53_S or DWT_HIP_INTERP53_S (anything else is an error).
+ *
+ * Node tree of a line of N samples, natural (Paley) order: level 0 has the node [0, N); the node [s, s+n) of level j has
+ * its L child at [s, s+ceil(n/2)) and its H child at [s+ceil(n/2), s+n) of level j+1.  The natural index k reads the path,
+ * first split in the most significant bit (0 = L).  Node k of level j has (N - bitrev_j(k) + 2^j - 1) >> j samples, the
+ * starts are the prefix sums.  Forward level j: one call of the reference's one-level line function
+ * (dwt_cdf97_f_ex_stride_s and its siblings) per node of level j, dst_l at s and dst_h at s + ceil(n/2); after `levels`
+ * levels the line holds its 2^levels leaves in natural order.  The inverse is the mirror, levels-1 .. 0, each node rebuilt
+ * by the one-level inverse line function.  1 <= levels <= floor(log2 N): every node that is split has two samples or more
+ * (anything else is an error, not clamped).  In 2-D the node rectangles are the product of the rule along x and along y,
+ * node (ky, kx); a forward level gives every node one level of dwt_cdf97_2f_s (dwt_cdf53_2f_s, dwt_interp53_2f_s) on an
+ * image of the node's size -- rows, then columns, LL | HL over LH | HH inside the node's rectangle --, the inverse one level
+ * of the matching _2i_s (rows, then columns);  1 <= levels <= min(floor(log2(min(size_x, size_y))), 8).
+ * The band of natural node k is not the k-th lowest: dwt_hip_wp_freq_order gives the Gray code perm[f] = f ^ (f >> 1), the
+ * natural index of the node with the f-th lowest band (per axis in 2-D).  Data is never permuted.
+ *
+ * src == dst is in place; otherwise dst receives the transform and src is left untouched (they must not overlap).  Both
+ * are host memory (synchronous) or both device memory (ordered on the context's stream, no synchronisation, no allocation
+ * after the first call of a shape).  Lines are line_stride bytes apart, their elements elem_stride; images batch_stride
+ * apart, rows stride_x, elements stride_y; only the frame's own elements are written.  Lines lie apart (line_stride >=
+ * (N-1)*elem_stride + 4) or interleaved inside one element step (n_lines*line_stride <= elem_stride: line y the channel y
+ * of an array of n_lines or more channels); anything else, where two lines would share a sample, is an error.  Device lines of up to 8192 samples
+ * take ONE kernel launch whatever `levels` and n_lines; dense device images (stride_y 4) one launch per level for the whole
+ * batch.  Longer lines, strided image elements and every call under option "wp_fused" = 0 run level by level through the
+ * exact line passes, node by node.  Same bits on every route: those of the reference's functions per node, over the whole
+ * float range. */
+/* natural-order node table of one level of an N-sample line: start[k], len[k] for k < 2^level (either may be NULL);
+ * returns 2^level, -1 for bad arguments (level > floor(log2 N)) */
+int dwt_hip_wp_nodes(int N, int level, int *start, int *len);
+/* perm[f] = natural index of the f-th lowest band (perm may be NULL); returns 2^level, -1 for a level outside 0 .. 30 */
+int dwt_hip_wp_freq_order(int level, int *perm);
+int dwt_hip_wp1d_batch(int wavelet, int inverse, const void *src, void *dst, size_t line_stride, size_t elem_stride,
+	int n_lines, int N, int levels);
+int dwt_hip_wp2d_batch(int wavelet, int inverse, const void *src, void *dst, size_t batch_stride, int batch,
+	int stride_x, int stride_y, int size_x, int size_y, int levels);
+/* statistics of every node of `level` of transformed packet lines / images, node order natural (order = 0) or
+ * frequency (1; 2-D: node (perm[fy], perm[fx]) at fy * 2^level + fx); the contracts of dwt_hip_features1d_batch /
+ * _2d_batch (fv in the memory space of ptr, fixed-order double sums, the Band's j = level): per line / image one block of
+ * 2^level (4^level) floats per feature of the mask in enum order.  At most 96 nodes: level <= 6 in 1-D, <= 3 in 2-D (more
+ * is an error). */
+int dwt_hip_wp_features1d_batch(unsigned feature_mask, const void *ptr, size_t line_stride, size_t elem_stride,
+	int n_lines, int N, int level, int order, float p, float *fv, size_t fv_stride);
+int dwt_hip_wp_features2d_batch(unsigned feature_mask, const void *ptr, size_t batch_stride, int batch, int stride_x,
+	int size_x, int size_y, int level, int order, float p, float *fv, size_t fv_stride);
 
 /* Time-frequency planes of line batches: the Gaussian-window STFT, the complex Morlet CWT and the S transform of
  * src/gabor.c (gabor_ft_s, gabor_wt_s, gabor_st_s and their _arg_ twins; include/gabor.h), DESIGN.md s14.

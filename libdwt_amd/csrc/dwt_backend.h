@@ -73,6 +73,7 @@ struct Ctx {
 	int tf_tiled = 1;  // time-frequency planes of dense lines through the LDS-tiled kernel (0: one thread per output, the cross-check)
 	int cond_fused = -1; // conditioning of dense rows of up to N1D_MAX samples: 1 in one launch, 0 one kernel per operation (the cross-check), -1 by batch size
 	int swt2d_fused = 1; // SWT levels of dense device images below SWT2D_FUSED_LEVELS in one launch each (0: a row pass and a column pass, the cross-check)
+	int wp_fused = 1; // wavelet packets: lines of up to N1D_MAX samples in one launch, dense device images one launch per level (0: every node through the exact line passes, the cross-check)
 	int swt_fused = 1; // SWT lines of up to N1D_MAX samples in one launch (0: one launch per level, the cross-check)
 	// options
 	SweepTuning tune;

@@ -587,6 +587,61 @@ int dwt_hip_swt_features1d_batch(int wavelet, unsigned feature_mask, const void 
 		[&](float *host) { return swt_features_device(w, feature_mask, d, ls, n_lines, N, levels, band, p, host, block); });
 }
 
+// The packet entries: the nodes of `level` of a transformed packet line / image as a Band table, node f of
+// the table the natural node perm(f) -- perm the identity (order 0) or the Gray code (order 1: rising frequency).
+static int wp_order(int order, int f) { return order ? f ^ (f >> 1) : f; }
+
+int dwt_hip_wp_features1d_batch(unsigned feature_mask, const void *ptr, size_t line_stride, size_t elem_stride, int n_lines, int N, int level,
+	int order, float p, float *fv, size_t fv_stride)
+{
+	if (check_inited() || check_request(feature_mask, ptr, fv, p))
+		return 1;
+	if (n_lines < 0 || N < 1 || line_stride > (size_t)LONG_MAX / 2 || elem_stride > INT_MAX || fv_stride > (size_t)LONG_MAX / 8 || order < 0 || order > 1)
+		return fail("packet features: bad arguments");
+	if (level < 0 || (N >> level) < 1)
+		return fail("packet features: level %d of a line of %d samples", level, N);
+	if (level > 30 || (1 << level) > FEAT_MAX_BANDS)
+		return fail("packet features: level %d has more than %d nodes", level, FEAT_MAX_BANDS);
+	if (elem_stride < 4 || (n_lines > 1 && line_stride < elem_stride * (size_t)N))
+		return fail("packet features: lines must be apart (line stride %zu, element stride %zu)", line_stride, elem_stride);
+	const Geom ge{N, 1, N, 1};
+	Band bands[FEAT_MAX_BANDS];
+	const int nb = 1 << level;
+	for (int f = 0; f < nb; f++) {
+		int s, n;
+		wp_node(N, level, wp_order(order, f), &s, &n);
+		bands[f] = Band{s, 0, n, 1, level};
+	}
+	return features(feature_mask, ptr, (long)line_stride, n_lines, (long)elem_stride * N, (long)elem_stride, ge, bands, nb, p, Moment{}, fv,
+		(long)fv_stride, true);
+}
+
+int dwt_hip_wp_features2d_batch(unsigned feature_mask, const void *ptr, size_t batch_stride, int batch, int stride_x, int size_x, int size_y,
+	int level, int order, float p, float *fv, size_t fv_stride)
+{
+	if (check_inited() || check_request(feature_mask, ptr, fv, p))
+		return 1;
+	if (batch < 0 || size_x < 1 || size_y < 1 || batch_stride > (size_t)LONG_MAX / 2 || fv_stride > (size_t)LONG_MAX / 8 || order < 0 || order > 1)
+		return fail("packet features: bad arguments");
+	if (level < 0 || (size_x >> level) < 1 || (size_y >> level) < 1)
+		return fail("packet features: level %d of images of %d x %d", level, size_x, size_y);
+	if (level > 15 || (1 << (2 * level)) > FEAT_MAX_BANDS)
+		return fail("packet features: level %d has more than %d nodes", level, FEAT_MAX_BANDS);
+	if (stride_x < 4l * size_x || (batch > 1 && batch_stride < (size_t)stride_x * size_y))
+		return fail("packet features: images must be dense and apart (stride %d, batch stride %zu)", stride_x, batch_stride);
+	const Geom ge{size_x, size_y, size_x, size_y};
+	Band bands[FEAT_MAX_BANDS];
+	const int nn = 1 << level;
+	for (int fy = 0; fy < nn; fy++)
+		for (int fx = 0; fx < nn; fx++) {
+			int sx, w, sy, h;
+			wp_node(size_x, level, wp_order(order, fx), &sx, &w);
+			wp_node(size_y, level, wp_order(order, fy), &sy, &h);
+			bands[fy * nn + fx] = Band{sx, sy, w, h, level};
+		}
+	return features(feature_mask, ptr, (long)batch_stride, batch, stride_x, 4, ge, bands, nn * nn, p, Moment{}, fv, (long)fv_stride, true);
+}
+
 int dwt_hip_band_feature(int feature, const void *ptr, int stride_x, int stride_y, int size_x, int size_y, int j, float p, float *value)
 {
 	if (feature < 0 || feature >= DWT_HIP_FEATURE_COUNT)

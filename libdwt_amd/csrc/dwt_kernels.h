@@ -190,6 +190,42 @@ constexpr int N1D_MAX = 8192; // LDS: 56 KiB per line of an inverse at this leng
 hipError_t launch_line_levels(Wavelet w, bool inverse, const void *src, void *dst, long line_stride, long elem_stride,
 	int n_lines, int N, int levels, hipStream_t s);
 
+// Wavelet packets (dwt_wp1d.hip, dwt_wp2d.hip): every node of a level is split again.  The node tree of
+// a line of N samples in natural order: the node [s, s+n) has its L child at [s, s+ceil(n/2)) and its H child behind it;
+// index k reads the path from the root, first split in the most significant of its `level` bits (0 = L).
+static __host__ __device__ inline void wp_node(int N, int level, int k, int *start, int *len)
+{
+	int s = 0, n = N;
+	for (int b = level - 1; b >= 0; b--) {
+		const int nl = (n + 1) >> 1;
+		if ((k >> b) & 1) {
+			s += nl;
+			n -= nl;
+		} else
+			n = nl;
+	}
+	*start = s;
+	*len = n;
+}
+// All `levels` packet levels of `n_lines` lines of 2 <= N <= N1D_MAX samples in one launch, 1 <= levels <= floor(log2 N):
+// line i at src + i*line_stride, elements `elem_stride` bytes apart (a multiple of 4); the leaves in natural order go to
+// the same places in dst, which may be src.  Inverse: the leaves of depth `levels` back to the line.
+hipError_t launch_wp_lines(Wavelet w, bool inverse, const void *src, void *dst, long line_stride, long elem_stride, int n_lines,
+	int N, int levels, hipStream_t s);
+// One packet level of a batch of dense images, out of place: the 4^level nodes of every W x H image of src are split
+// (inverse: rebuilt from their four quarters) into dst.  Strides in BYTES, multiples of 4.
+constexpr int WP2D_TILE_W = 128, WP2D_TILE_H = 32; // a workgroup's tile of one node, samples
+constexpr int WP2D_MAX_LEVELS = 8;
+struct Wp2dLevelArgs {
+	const char *src;
+	long src_pitch, src_bs;
+	char *dst;
+	long dst_pitch, dst_bs;
+	int W, H, batch, level;
+};
+bool wp2d_level_fits(const Wp2dLevelArgs &a); // aligned, every node of the level has two samples or more each way, a grid the launch can take
+hipError_t launch_wp2d_level(Wavelet w, bool inverse, const Wp2dLevelArgs &a, hipStream_t s);
+
 // Edge-avoiding 5/3 and 9/7 (dwt_eaw.hip).  One exact pass over n_lines lines (line l at src + l*ls, elements es bytes
 // apart, a multiple of 4) into the dense scratch tmp (n_lines x N floats, sample order); weights w[l*N + i] written
 // (forward) or read (inverse).  hoff: where the line's H half starts (Mallat), or -1 (interleaved: sample i at i).  The
