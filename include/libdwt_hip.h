@@ -619,6 +619,87 @@ int dwt_hip_wp_features1d_batch(unsigned feature_mask, const void *ptr, size_t l
 int dwt_hip_wp_features2d_batch(unsigned feature_mask, const void *ptr, size_t batch_stride, int batch, int stride_x,
 	int size_x, int size_y, int level, int order, float p, float *fv, size_t fv_stride);
 
+/* The pixel front end: pictures of 8- or 16-bit unsigned pixels <-> the planes the 2-D transforms take,
+ * with the DC level shift and the component transforms of ITU-T T.800 Annex G.  An extension: the reference's picture
+ * programs widen the pixels on the host and hand over one channel at a time.
+ *
+ * Pixels.  `fmt` DWT_HIP_PIX_U8 or _U16 (host byte order), `channels` 1, 3 or 4.  Channel c of pixel (x, y) of picture b
+ * lies at pix + b*pix_batch_stride + y*pix_row_pitch + x*pix_stride + c*chan_stride, all in bytes: interleaved RGB8 is
+ * pix_stride 3, chan_stride 1; BGRA8 is 4, 1 with order DWT_HIP_ORDER_BGR; planar is pix_stride = element size,
+ * chan_stride = plane bytes; three used channels of a 4-byte pixel is 4, 1, channels 3.  Any byte alignment is legal; no
+ * two elements may share a byte (the three steps must nest in some order).  `order` says which of the first three channels
+ * is R.  A fourth channel takes offset and scale only, never the component transform.
+ *
+ * Planes.  Plane (b, c) lies at planes + (b*channels + c)*plane_stride, rows plane_row_pitch bytes apart, elements
+ * adjacent; `plane_type` DWT_HIP_PLANE_I16, _I32, _H (binary16) or _S (binary32); addresses and strides are multiples of
+ * the element size.  After a component transform component 0 is Y, 1 is Cb / U, 2 is Cr / V whatever `order` was.
+ *
+ * Forward.  depth is 1 .. 8 (u8) or 1 .. 16 (u16); pixel values are used as stored.  v = pix - offset (offset an int,
+ * usually 2^(depth-1)).  Integer planes (scale must be 1): DWT_HIP_COLOUR_NONE stores v; _RCT stores Y = (R + 2G + B) >> 2,
+ * U = B - G, V = R - G in 32-bit wrapping arithmetic with an arithmetic shift, truncated to the plane's width.  Float
+ * planes: v converted to binary32 (to nearest even), times scale; _ICT then stores
+ *     Y  = (0.299f*R + 0.587f*G) + 0.114f*B
+ *     Cb = (-0.16875f*R + -0.33126f*G) + 0.5f*B
+ *     Cr = (0.5f*R + -0.41869f*G) + -0.08131f*B
+ * every product and sum rounded to binary32 on its own, in this order; _H planes round the result to binary16 once, to
+ * nearest even.
+ *
+ * Inverse.  Integer planes widen to int; _RCT: G = Y - ((U + V) >> 2), R = V + G, B = U + G, wrapping; + offset
+ * (wrapping), clamped to [0, 2^depth - 1].  Float planes widen exactly; _ICT: R = Y + 1.402f*Cr,
+ * G = (Y + -0.34413f*Cb) + -0.71414f*Cr, B = Y + 1.772f*Cb; times the call's scale (the caller passes the reciprocal of
+ * the forward one); rounded to the nearest integer, ties to even; + offset (exactly); clamped.  NaN gives 0, +-Inf the
+ * ends of the range.
+ *
+ * Errors (nonzero, dwt_hip_last_error, nothing written): RCT with float planes, ICT or scale != 1 with integer planes, a
+ * component transform with fewer than 3 channels, RCT into _I16 at depth 16 (U and V need depth + 1 bits), a depth
+ * outside the pixel type, 2 or 5+ channels, pixels and planes that overlap, elements that share bytes.
+ *
+ * Each side is host or device memory on its own.  Device sides are ordered on the context's stream: one kernel launch, no
+ * synchronisation, no allocation.  A host side is mirrored in a device buffer of the context (its whole region crosses
+ * PCIe; a written region with bytes outside the frame is uploaded first so that they come back as they were) and the call
+ * ends synchronised.  Only the frame's own elements change.  A lane converts DWT_HIP_PIXELS_PER_LANE consecutive pixels of
+ * a row; a side whose base, pitches and strides are multiples of 16 bytes moves by 16-byte accesses, any other side
+ * element by element (option "pixels_wide" = 0: every side): same bits.  dwt_hip_pixels_route tells which: the OR of
+ * DWT_HIP_PIXELS_WIDE_PIX and _WIDE_PLANES for a call with these addresses, -1 for arguments the entries refuse.  The answer
+ * holds for the device sides of the two conversion entries: a host side runs on its mirror, whose base is aligned whatever
+ * the host address was, and the composite entries convert into or out of their scratch stack, not the caller's planes.
+ * A wide load of an interleaved pixel that has more elements than channels (three channels of a 4-element pixel, grey
+ * at a 3- or 4-element step) reads the pixel's unused elements too, the last pixel's up to 3 (u8) or 6 (u16) bytes past the
+ * frame's last element -- inside the same aligned 16 bytes, never written. */
+enum dwt_hip_pixel_format { DWT_HIP_PIX_U8 = 0, DWT_HIP_PIX_U16 = 1 };
+enum dwt_hip_pixel_order { DWT_HIP_ORDER_RGB = 0, DWT_HIP_ORDER_BGR = 1 };
+enum dwt_hip_colour { DWT_HIP_COLOUR_NONE = 0, DWT_HIP_COLOUR_RCT = 1, DWT_HIP_COLOUR_ICT = 2 };
+enum dwt_hip_plane_type { DWT_HIP_PLANE_I16 = 0, DWT_HIP_PLANE_I32 = 1, DWT_HIP_PLANE_H = 2, DWT_HIP_PLANE_S = 3 };
+#define DWT_HIP_PIXELS_PER_LANE 16
+#define DWT_HIP_PIXELS_GRID_ROWS 16384 /* rows / pictures one trip of the kernel's loops covers */
+#define DWT_HIP_PIXELS_GRID_BATCH 4096
+#define DWT_HIP_PIXELS_WIDE_PIX 1
+#define DWT_HIP_PIXELS_WIDE_PLANES 2
+int dwt_hip_pixels_to_planes_batch(int fmt, const void *pix, size_t pix_batch_stride, size_t pix_row_pitch, size_t pix_stride,
+	size_t chan_stride, int batch, int channels, int order, int depth, int offset, float scale, int colour, int plane_type,
+	void *planes, size_t plane_stride, size_t plane_row_pitch, int size_x, int size_y);
+int dwt_hip_planes_to_pixels_batch(int fmt, void *pix, size_t pix_batch_stride, size_t pix_row_pitch, size_t pix_stride,
+	size_t chan_stride, int batch, int channels, int order, int depth, int offset, float scale, int colour, int plane_type,
+	const void *planes, size_t plane_stride, size_t plane_row_pitch, int size_x, int size_y);
+int dwt_hip_pixels_route(int fmt, int inverse, const void *pix, size_t pix_batch_stride, size_t pix_row_pitch, size_t pix_stride,
+	size_t chan_stride, int batch, int channels, int plane_type, const void *planes, size_t plane_stride,
+	size_t plane_row_pitch, int size_x, int size_y);
+/* The conversion and dwt_hip_transform2d_batch of the batch*channels planes (batch_stride = plane_stride, stride_x =
+ * plane_row_pitch) in one call: forward the pixels to transformed planes, *j as that entry takes it (levels wanted, -1
+ * all; levels done stored); inverse the planes, which are only read, to pixels.  The plane type follows from `wavelet`:
+ * DWT_HIP_CDF53_I16 -> _I16; _CDF53_I, _CDF97_I -> _I32; _CDF97_H -> _H; _CDF97_S, _CDF53_S, _INTERP53_S -> _S; the double
+ * wavelets are refused, and so are more than 65535 planes, a plane_stride below size_y rows and a plane_row_pitch of 2 GiB
+ * or more.  A call that runs no level (*j == 0, or a picture one pixel wide or high) is the conversion alone, *j = 0 stored.
+ * Otherwise the samples pass through
+ * a scratch stack of planes of the context with the caller's strides (the batched transform runs out of place).  Same bits
+ * as the two calls. */
+int dwt_hip_picture_forward_batch(int wavelet, int fmt, const void *pix, size_t pix_batch_stride, size_t pix_row_pitch,
+	size_t pix_stride, size_t chan_stride, int batch, int channels, int order, int depth, int offset, float scale, int colour,
+	void *planes, size_t plane_stride, size_t plane_row_pitch, int size_x, int size_y, int *j);
+int dwt_hip_picture_inverse_batch(int wavelet, int fmt, void *pix, size_t pix_batch_stride, size_t pix_row_pitch,
+	size_t pix_stride, size_t chan_stride, int batch, int channels, int order, int depth, int offset, float scale, int colour,
+	const void *planes, size_t plane_stride, size_t plane_row_pitch, int size_x, int size_y, int j);
+
 /* Time-frequency planes of line batches: the Gaussian-window STFT, the complex Morlet CWT and the S transform of
  * src/gabor.c (gabor_ft_s, gabor_wt_s, gabor_st_s and their _arg_ twins; include/gabor.h), DESIGN.md s14.
  *

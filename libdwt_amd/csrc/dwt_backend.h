@@ -56,10 +56,11 @@ struct Ctx {
 	Buf band_ws; // band operators: the per-image operator tables of a batch (dwt_backend_bandops.hip)
 	Buf nterm_ws; // N-term approximation: ranks, select histograms, records (dwt_backend_nterm.hip)
 	Buf half_f32; // float 9/7 on binary16 storage, line-pass route: the binary32 copies of a level's frame (dwt_backend.hip)
+	Buf px_pix, px_planes, px_tmp; // pixel front end: the device mirrors of a host call's pixels and planes, the composite entries' plane stack (dwt_backend_pixels.hip)
 	// every device scratch buffer above: a new one is declared there, listed here, and named nowhere else for freeing
 	auto bufs()
 	{
-		return std::array{&stage_img, &ll[0], &ll[1], &frame_a, &frame_b, &vol_out, &vol_host[0], &vol_host[1], &eaw_w, &eaw_ll[0], &eaw_ll[1], &feat_ws, &swt_ws, &cond_ws, &band_ws, &nterm_ws, &half_f32};
+		return std::array{&stage_img, &ll[0], &ll[1], &frame_a, &frame_b, &vol_out, &vol_host[0], &vol_host[1], &eaw_w, &eaw_ll[0], &eaw_ll[1], &feat_ws, &swt_ws, &cond_ws, &band_ws, &nterm_ws, &half_f32, &px_pix, &px_planes, &px_tmp};
 	}
 	hipEvent_t dl_ev[8] = {}; // strip events of the host downloads (dwt_host_xfer.hip), created once
 	hipEvent_t switch_ev = nullptr; // dwt_hip_set_stream: orders a newly set stream behind the old one's work
@@ -74,6 +75,7 @@ struct Ctx {
 	int cond_fused = -1; // conditioning of dense rows of up to N1D_MAX samples: 1 in one launch, 0 one kernel per operation (the cross-check), -1 by batch size
 	int swt2d_fused = 1; // SWT levels of dense device images below SWT2D_FUSED_LEVELS in one launch each (0: a row pass and a column pass, the cross-check)
 	int wp_fused = 1; // wavelet packets: lines of up to N1D_MAX samples in one launch, dense device images one launch per level (0: every node through the exact line passes, the cross-check)
+	int pixels_wide = 1; // pixel front end: aligned sides move by 16-byte accesses (0: element by element everywhere, the cross-check)
 	int swt_fused = 1; // SWT lines of up to N1D_MAX samples in one launch (0: one launch per level, the cross-check)
 	// options
 	SweepTuning tune;

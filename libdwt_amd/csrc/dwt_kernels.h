@@ -226,6 +226,30 @@ struct Wp2dLevelArgs {
 bool wp2d_level_fits(const Wp2dLevelArgs &a); // aligned, every node of the level has two samples or more each way, a grid the launch can take
 hipError_t launch_wp2d_level(Wavelet w, bool inverse, const Wp2dLevelArgs &a, hipStream_t s);
 
+// The pixel front end (dwt_pixels.hip): unsigned 8- / 16-bit pixels <-> wavelet planes, one launch per call.
+// Channel c of pixel (x, y) of picture b at pix + b*pix_bs + y*pix_pitch + x*pix_stride + c*chan_stride, plane (b, c) at
+// planes + (b*channels + c)*plane_stride with rows plane_pitch apart; all in bytes, checked by the driver.
+constexpr int PIXELS_PER_LANE = 16;     // consecutive pixels of a row per lane (DWT_HIP_PIXELS_PER_LANE)
+constexpr int PIXELS_WG_ROWS = 4;       // rows per workgroup: one per wave
+constexpr int PIXELS_GRID_ROWS = 16384; // rows one trip of the kernel's row loop covers (grid.y * PIXELS_WG_ROWS)
+constexpr int PIXELS_GRID_BATCH = 4096; // pictures one trip of its batch loop covers (grid.z)
+enum PixelPlane { kPlaneI16 = 0, kPlaneI32 = 1, kPlaneH = 2, kPlaneS = 3 }; // (DWT_HIP_PLANE_*)
+struct PixelsArgs {
+	char *pix;
+	long pix_bs, pix_pitch, pix_stride, chan_stride;
+	char *planes;
+	long plane_stride, plane_pitch;
+	int batch, channels, W, H;
+	int bgr, colour; // channel 0 of a pixel is B; the component transform of the plane type is applied (RCT / ICT)
+	int offset, maxv;
+	float scale;
+	int layout;   // wide pixel route: 3 / 4 elements per interleaved pixel, 0 one run per channel (planar, grey)
+	int wide_pix, wide_planes; // that side moves by 16-byte accesses (pixels_route)
+	int pix_al2;  // element route: 16-bit pixels lie on even addresses
+	int nt_out;   // the wide stores are non-temporal
+};
+hipError_t launch_pixels(int pix_bytes, int plane, bool inverse, const PixelsArgs &a, hipStream_t s);
+
 // Edge-avoiding 5/3 and 9/7 (dwt_eaw.hip).  One exact pass over n_lines lines (line l at src + l*ls, elements es bytes
 // apart, a multiple of 4) into the dense scratch tmp (n_lines x N floats, sample order); weights w[l*N + i] written
 // (forward) or read (inverse).  hoff: where the line's H half starts (Mallat), or -1 (interleaved: sample i at i).  The
