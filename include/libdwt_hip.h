@@ -150,8 +150,8 @@ void dwt_hip_alloc_batch_report(int *chunks, int *dst_tried, int *ll_tried, int 
  * (1 = policy 3 by itself when a launch's LL bands exceed 1 GiB), "fma" (1 = contracted lifting steps:
  * NOT the reference's rounding, within 1e-5), "fused_d" (0 = double precision through the exact line passes),
  * "fuse01" (forward float 9/7, Mallat, out of place, two levels or more, width and height multiples of 4 with both
- * levels of 64 x 64 or more: levels 0 and 1 in ONE launch over overlapped tiles, level 0's LL band never written --
- * 1 = where that pays (rows of 8192 columns and more in launches of 32768 tiles and more: 32 images of 8192^2), 0 = never, 2 = wherever
+ * levels of 64 x 64 or more: levels 0 and 1 in ONE launch, level 0's LL band never written --
+ * 1 = where that pays (launches of 32768 tiles of 512 columns x 64 row pairs and more: 32 images of 8192^2, 128 of 4096^2), 0 = never, 2 = wherever
  * the geometry is legal, for tests; same bits; not with "fma", "cpt" 4, "ring" 8, "nt" 15 or an odd "tile_pairs"),
  * "ride_copy" (1 = in-place Mallat calls on one image: the copy of level 0's staged subbands rides along with the deeper
  * levels' launches as extra workgroups; 0 = a launch of its own, the cross-check) and "ride_mib" (MiB of it per small level),

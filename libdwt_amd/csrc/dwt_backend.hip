@@ -282,19 +282,17 @@ bool level_fused_ok(const Call2d &c, const Geom &ge, int j)
 	return !g.force_generic && (c.es == 4 || (c.es == 2 ? c.aligned : g.fused_d != 0)) && ge.Wi(j) == ge.Wo(j) && ge.Hi(j) == ge.Ho(j) && ge.Wo(j) >= 2 &&
 		ge.Ho(j) >= 2;
 }
-// Levels 0 and 1 of a forward transform in ONE launch (launch_fwd01: overlapped tiles, level 0's LL band never written):
-// float 9/7 without contraction, Mallat layout, out of place (no staging detour, no copy riding along), two levels or
-// more, both fused, W and H multiples of 4 with both levels of 64 x 64 or more, and none of the sweep's geometry set by
-// hand to something the fused kernel is not (it is the 8-column, deep-ring tile).  Option fuse01: 0 never, 2 wherever
-// that holds, 1 (default) where it also pays:
-//   - the launch costs about level 0 x (ntx01 / ntx) x 1.05 (level 1's warm-up rows) x 1.02 (its arithmetic and stores)
-//     against level 0 + level 1 = 1.25 x level 0, so the overlapped tiles may cost up to 16 % more tiles per row; with a
-//     margin for what the overlap costs the caches the rule takes ntx01 / ntx <= 1.10: 8192 columns (17 for 16) and
-//     16384 (35 for 32) qualify, 4096 (9 for 8) and everything narrower do not;
+// Levels 0 and 1 of a forward transform in ONE launch (launch_fwd01: the level-0 sweep's own 512-column tiles, level 0's LL
+// band never written): float 9/7 without contraction, Mallat layout, out of place (no staging detour, no copy riding along),
+// two levels or more, both fused, W and H multiples of 4 with both levels of 64 x 64 or more, and none of the sweep's
+// geometry set by hand to something the fused kernel is not (it is the 8-column, deep-ring tile).  Option fuse01: 0 never,
+// 2 wherever that holds, 1 (default) where it also pays:
+//   - the launch costs about level 0 x 1.05 (level 1's warm-up rows) x 1.03 (its arithmetic, stores and phantom columns)
+//     against level 0 + level 1 = 1.25 x level 0, whatever the width: the tiles are level 0's, so no width is kept out;
 //   - only in launches of 32768 tiles of 512 columns x 64 pairs and more (32 images of 8192^2), the sizes it was measured
-//     to win at (profiles/fuse01_summary.md).  Below 3072 tiles level 0 does not take the deep ring itself -- a round or
-//     two of waves wants the shallow ring's 8 waves per CU --; in between nothing was measured, and a call on 16 images
-//     of 8192^2 is held to one launch per level (tests/test_hip_multi.py).
+//     to win at (profiles/fuse01_summary.md, profiles/fuse01_seams_summary.md).  Below 3072 tiles level 0 does not take
+//     the deep ring itself -- a round or two of waves wants the shallow ring's 8 waves per CU --; in between nothing was
+//     measured, and a call on 16 images of 8192^2 is held to one launch per level (tests/test_hip_multi.py).
 static bool pair01_ok(const Call2d &c, const Geom &ge, int J, int batch)
 {
 	const int W = ge.Wo(0), H = ge.Ho(0);
@@ -305,8 +303,8 @@ static bool pair01_ok(const Call2d &c, const Geom &ge, int J, int batch)
 		return false;
 	if (g.fuse01 >= 2)
 		return true;
-	const long ntx = (W + 511) / 512, nty = ((H >> 1) + 63) / 64;
-	return fwd01_tiles(W) * 10 <= ntx * 11 && ntx * nty * batch >= 32768;
+	const long ntx = fwd01_tiles(W), nty = ((H >> 1) + 63) / 64;
+	return ntx * nty * batch >= 32768;
 }
 
 // ---- the line-pass route of the float 9/7 on binary16 storage (kCdf97H) ----------------

@@ -150,6 +150,23 @@ static __device__ __forceinline__ void lds_read2o(unsigned a0, unsigned a1, u4 &
 		: "memory");
 }
 
+// Two windows of 9 words each (8-byte aligned; the phantom columns of the fused pair of levels), split like lds_issue3 /
+// lds_arrived3: the reads carry no wait, and the values may be used only behind lds_arrived_win9x2, which follows the
+// wave's next waited LDS read (LDS reads return in order).
+static __device__ __forceinline__ void lds_issue_win9x2(unsigned a0, unsigned a1, u4 &p0, u4 &p1, unsigned &p8, u4 &q0, u4 &q1, unsigned &q8)
+{
+	asm volatile("ds_read2_b64 %0, %6 offset1:1\n\tds_read2_b64 %1, %6 offset0:2 offset1:3\n\tds_read_b32 %2, %6 offset:32\n\t"
+				 "ds_read2_b64 %3, %7 offset1:1\n\tds_read2_b64 %4, %7 offset0:2 offset1:3\n\tds_read_b32 %5, %7 offset:32"
+		: "=&v"(p0), "=&v"(p1), "=&v"(p8), "=&v"(q0), "=&v"(q1), "=&v"(q8)
+		: "v"(a0), "v"(a1)
+		: "memory");
+}
+
+static __device__ __forceinline__ void lds_arrived_win9x2(u4 &p0, u4 &p1, unsigned &p8, u4 &q0, u4 &q1, unsigned &q8)
+{
+	asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(p0), "+v"(p1), "+v"(p8), "+v"(q0), "+v"(q1), "+v"(q8) : : "memory");
+}
+
 static __device__ __forceinline__ void lds_read2(unsigned a0, unsigned a1, u4 &r0, u4 &r1)
 {
 	asm volatile("ds_read_b128 %0, %2\n\tds_read_b128 %1, %3\n\ts_waitcnt lgkmcnt(0)"
@@ -168,6 +185,28 @@ static __device__ __forceinline__ unsigned from_left_lane(unsigned v)
 static __device__ __forceinline__ unsigned from_right_lane(unsigned v)
 {
 	return (unsigned)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x130 /* wave_shl:1 */, 0xf, 0xf, false);
+}
+
+// lane e (0..3, compile time after unrolling) of the lane's own quad, to all four of its lanes (DPP quad_perm)
+static __device__ __forceinline__ unsigned quad_lane(unsigned v, int e)
+{
+	switch (e) {
+	case 0: return (unsigned)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x00, 0xf, 0xf, false);
+	case 1: return (unsigned)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x55, 0xf, 0xf, false);
+	case 2: return (unsigned)__builtin_amdgcn_update_dpp((int)v, (int)v, 0xaa, 0xf, 0xf, false);
+	default: return (unsigned)__builtin_amdgcn_update_dpp((int)v, (int)v, 0xff, 0xf, 0xf, false);
+	}
+}
+
+// the same shifts with the value the wave's first / last lane takes instead (the instruction's `old` operand)
+static __device__ __forceinline__ unsigned from_left_lane(unsigned v, unsigned first)
+{
+	return (unsigned)__builtin_amdgcn_update_dpp((int)first, (int)v, 0x138 /* wave_shr:1 */, 0xf, 0xf, false);
+}
+
+static __device__ __forceinline__ unsigned from_right_lane(unsigned v, unsigned last)
+{
+	return (unsigned)__builtin_amdgcn_update_dpp((int)last, (int)v, 0x130 /* wave_shl:1 */, 0xf, 0xf, false);
 }
 
 static __device__ __forceinline__ unsigned lds_offset(const void *p)

@@ -148,8 +148,9 @@ struct InvLevelArgs {
 struct IlStripArgs;
 hipError_t launch_fwd_level(Wavelet w, const FwdLevelArgs &a, const SweepTuning &t, hipStream_t s, const IlStripArgs *strip = nullptr);
 
-// Levels 0 AND 1 of a forward float 9/7 transform (Mallat, out of place) in ONE sweep over overlapped tiles
-// (k_fwd_sweep01): `a` describes level 0, except that out_ll / ll_pitch / ll_bstride are LEVEL 1's LL band -- level 0's is
+// Levels 0 AND 1 of a forward float 9/7 transform (Mallat, out of place) in ONE sweep over the level-0 sweep's own tiles,
+// 512 columns apart, each wave computing the 8 LL columns beyond its seams again for itself (k_fwd_sweep01): `a`
+// describes level 0, except that out_ll / ll_pitch / ll_bstride are LEVEL 1's LL band -- level 0's is
 // never written -- and level 1's detail subbands go to their Mallat places relative to out_h as well.  Same bits as the
 // two launches.  fwd01_can: W and H multiples of 4, both levels of 64 x 64 or more; fwd01_tiles: tiles per row.
 bool fwd01_can(Wavelet w, int W, int H);

@@ -77,8 +77,8 @@ static inline dim3 sweep_grid(const SweepGeom &g, int nty, int waves, int batch)
 // The tile of this wave: column tx, row pairs [A, B) of the level's (H + 1) / 2; `live`: there is such a tile (else the
 // whole wave leaves; no barriers are used anywhere).  `first`, `tile_blocks`: the launch's workgroups that take no tiles
 // (tile_block_id).  wv is wave-uniform on purpose: tile geometry, row indices and row pointers then live in SGPRs.
-// RUN: consecutive waves take consecutive tiles across the rows' ends (the fused pair of levels: a row of 17 tiles leaves
-// no wave of a workgroup idle); otherwise g.wave_horiz says whether a workgroup's waves sit side by side or stacked.
+// RUN: consecutive waves take consecutive tiles across the rows' ends (the fused pair of levels: a row whose tiles are
+// no multiple of the workgroup's waves leaves no wave idle); otherwise g.wave_horiz says whether a workgroup's waves sit side by side or stacked.
 // (The float sweeps' test for a launch that computes a band of the level only stays with them: inside this function it
 // compiles to another layout of their code.)
 struct SweepTile {

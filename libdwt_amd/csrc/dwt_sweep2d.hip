@@ -142,19 +142,31 @@ hipError_t launch_line_pass(Wavelet w, bool inverse, const void *src, void *dst,
 // X (interleaved layout, phase-ordered wavelets): the tiles leave out the samples whose rounding depends on the
 // reference's phase order -- rows 0..7 and the last 8 columns of the level -- for the strip workgroups of the
 // same launch (dwt_il_strip.h).
-// F01 (float 9/7 by selection, 8 columns per lane, Mallat): levels 0 AND 1 in this one sweep.  The tiles keep their 512
-// columns but start 480 apart (15 lines of 128 bytes: every row load stays line-aligned), so that each seam of level 1 is
-// computed twice, inside a wave, and nothing passes between waves:
+// F01 (float 9/7 by selection, 8 columns per lane, Mallat): levels 0 AND 1 in this one sweep.  The tiles are the level-0
+// sweep's own -- 512 columns, 512 apart, every lane stores what it computes, every store of an interior tile a whole run of
+// 1 KiB (level 0) or 512 B (level 1) --, and nothing passes between waves:
 //   - after the vertical pass a lane holds 4 samples of the LL row its iteration completes; level 1's horizontal lift
 //     takes the 4 neighbours on either side from the adjacent lanes' registers (wavefront shifts).  Lanes 0 and 63 have
-//     no such neighbour: their level-1 results are valid only where the lane holds an end of the line, which takes the
-//     end form (selection, doubled coefficient) and needs none;
+//     no such neighbour in the wave: theirs are PHANTOM columns, the LL columns c0/2 - 4 .. c0/2 - 1 and c0/2 + 256 ..
+//     c0/2 + 259 of the neighbour tiles, which this wave computes again for itself, one LL sample per lane (lane & 7: 0..3
+//     the left ones, 4..7 the right ones; the other lanes repeat them): a window of 9 input columns from LDS for each of
+//     the iteration's two rows, the four lifting steps on the shrinking window (10 operations, both rows as packed
+//     halves), the scale and the streaming vertical lift of that one column (4 words of state).  The operations and
+//     their order are those of the main columns, so the value has the bits the neighbour tile computes for its own
+//     column; lanes 0 and 63 take them by a quad broadcast.  The last column of the line can lie in a right phantom's window
+//     (the tile before the last one when 0 < W mod 512 < 16): entries 5 and 7 of the window take the end form by
+//     selection like the main columns' candidates.  A phantom column that does not exist (left of tile 0, right of the
+//     last column) holds whatever LDS holds; level 1's end form (g0, g5, g7, g9: a select, not arithmetic) cuts it off;
+//   - the row slot in LDS is [main 512 | input columns c0 - 12 .. c0 + 3 | c0 + 508 .. c0 + 523]: both halo blocks are 16
+//     columns, 48 B of the neighbour tile's first or last 64-byte sector and 16 B of this tile's own, so that every
+//     phantom window (c0 - 12 + 2p .. c0 - 4 + 2p; c0 + 508 + 2p .. c0 + 516 + 2p) is contiguous there.  They come by ONE
+//     DMA instruction per row as the 4-column halo of the other sweeps does, 32 lanes active in place of 8: kDmaPerIter
+//     and with it the vmcnt ring count stay what they are.  Temporal, like every halo load;
 //   - every second iteration completes an LL row pair: level 1's horizontal lift of both rows, its vertical pass (a state
 //     of 4 columns) and the stores of its four quarter rows.  Its ends of a column take the end form too, the bottom one
 //     by dropping the NEWER tap: the rows this sweep computes beyond the last LL row mirror the level's input, not the band;
-//   - tile t stores the level-0 details of its first 480 columns (lanes 0..59) and level 1 of lanes 1..60 (LL columns
-//     240 t + 4 .. 240 t + 243); tile 0 also lane 0, the tile that holds the last column everything up to it.  Every
-//     sample is written once; the LL band of level 0 is never written.  `out_ll` is level 1's LL band;
+//   - every sample is written once (lanes right of the line's end are dropped by the row's buffer descriptor); the LL band
+//     of level 0 is never written.  `out_ll` is level 1's LL band;
 //   - vertically a tile warms level 1 up with 4 more iterations above (none at the top of the image: the end form cuts
 //     the dependence) and flushes it with 3 more below.
 // W and H are multiples of 4 and at least 128 (both levels of 64 x 64 or more); the last column of either level can then
@@ -176,7 +188,11 @@ static __device__ __forceinline__ void fwd_sweep_tile(const FwdLevelArgs &a, con
 	// wavefront shifts (DPP) instead of re-reading them from LDS
 	constexpr bool kShuffle = (NT & 8) != 0;
 	constexpr int TW = 64 * CPT;
-	constexpr int RS = TW + 8; // LDS row slot: [main TW | left halo 4 | right halo 4]
+	// LDS row slot: [main TW | left halo 4 | right halo 4]; F01: [main TW | columns c0 - 12 .. c0 + 3 | c0 + TW - 4 .. c0 + TW + 11]
+	constexpr int kHalo = F01 ? 16 : 4;
+	constexpr int RS = TW + 2 * kHalo;
+	constexpr int kHaloLanes = 2 * kHalo; // lanes of the row's one halo DMA
+	constexpr int kHaloL = F01 ? 8 : 0, kHaloR = F01 ? kHalo + 4 : 4; // where lane 0's / lane 63's four neighbour columns sit in the halo
 	// horizontal halo: K samples, rounded up to even so that the lane's window starts at an even column (a policy of one
 	// step: columns c - 2 .. c + CPT + 1, whose entry 1 is lifted in vain)
 	constexpr int HK = (K + 1) & ~1;
@@ -196,7 +212,7 @@ static __device__ __forceinline__ void fwd_sweep_tile(const FwdLevelArgs &a, con
 	[[maybe_unused]] const int ty = tile.ty;
 	const int img = blockIdx.y;
 	const int Wd = (a.W + 1) >> 1, Hd = (a.H + 1) >> 1;
-	const int c0 = tx * (F01 ? TW - 32 : TW);
+	const int c0 = tx * TW;
 	const int warm = (F01 && A > 0) ? K : 0; // level 1's warm-up above the tile
 	const int n_iter = (B - A) + K + warm + (F01 ? 3 : 0);
 	const int q0 = A - K / 2 - warm;
@@ -217,7 +233,7 @@ static __device__ __forceinline__ void fwd_sweep_tile(const FwdLevelArgs &a, con
 	const int n_edge = min(4, c0 + TW - a.W); // columns of this tile's main block right of the edge (<= 0: none)
 	// (SelEnds: levels of 64 x 64 and more -- no index is reflected twice, no integer division in the wave's instruction stream)
 	const int edge_col = kIsSelEnds<W> ? a.W - 2 - min(lane, 3) : reflect(a.W + min(lane, 3), a.W);
-	const int halo_i = lane < 4 ? c0 - 4 + lane : c0 + TW + (lane & 3);
+	const int halo_i = F01 ? (lane < 16 ? c0 - 12 + lane : c0 + TW - 4 + (lane & 15)) : lane < 4 ? c0 - 4 + lane : c0 + TW + (lane & 3);
 	const int halo_col = kIsSelEnds<W> ? reflect_near(halo_i, a.W) : reflect(halo_i, a.W);
 
 	int islot = 0, rslot = 0; // ring slots of the next rows to fill / to consume
@@ -237,7 +253,7 @@ static __device__ __forceinline__ void fwd_sweep_tile(const FwdLevelArgs &a, con
 			const int r = tall ? reflect1(ri, a.H) : reflect(ri, a.H);
 			char *lrow = ring + (size_t)(islot + rr) * RS * 4;
 			const T *grow = in + (long)r * a.in_pitch;
-			[[maybe_unused]] const T *hsrc = grow + halo_col; // lanes 0..7: the halo column
+			[[maybe_unused]] const T *hsrc = grow + halo_col; // lanes 0..7 (F01: 0..31): the halo column
 			// (in place) an own row read from the image: its last 8 columns -- the border strip waves of the launch may
 			// have written theirs already -- come from the snapshot `rgt + column`
 			[[maybe_unused]] const T *rgt = nullptr;
@@ -271,7 +287,7 @@ static __device__ __forceinline__ void fwd_sweep_tile(const FwdLevelArgs &a, con
 					dma4<0>(rgt + (a.W - kIlKeepRight + lane), lrow + (a.W - kIlKeepRight - c0) * 4);
 				if (lane < n_edge)
 					dma4<0>(esrc, lrow + (a.W - c0) * 4);
-				if (lane < 8)
+				if (lane < kHaloLanes)
 					dma4<0>(IL ? hsrc : grow + halo_col, lrow + TW * 4);
 			} else {
 #pragma unroll
@@ -282,7 +298,7 @@ static __device__ __forceinline__ void fwd_sweep_tile(const FwdLevelArgs &a, con
 				if (lane < n_edge)
 					dma4<kLdAux>(esrc, lrow + (a.W - c0) * 4);
 				// (the halo columns are the x-neighbour tiles' own lines, read by them at about the same time: temporal)
-				if (lane < 8)
+				if (lane < kHaloLanes)
 					dma4<0>(IL ? hsrc : grow + halo_col, lrow + TW * 4);
 			}
 		}
@@ -323,8 +339,12 @@ static __device__ __forceinline__ void fwd_sweep_tile(const FwdLevelArgs &a, con
 	// (F01) the last column in the middle of a lane's columns (a width that is 4 modulo 8); level 1's candidates in its
 	// window of 12 (the neighbours' 4, the lane's own 4): column 0 at entry 4, the last column at 5 or 7, or at 9 -- the
 	// right neighbour's second column, which this lane's results reach through step 0; the rows level 1 holds back
-	[[maybe_unused]] bool e1m = false, g0 = false, g5 = false, g7 = false, g9 = false, own0 = true, own1 = true;
-	[[maybe_unused]] T st1[K][4] = {}, held[4] = {};
+	// the lane's phantom LL column (input column pe, window pe - 4 .. pe + 4 at byte `pwin` of a row slot): the last column of
+	// the line at entry 5 or 7 of its window, its vertical state and the LL row it holds back
+	[[maybe_unused]] bool e1m = false, g0 = false, g5 = false, g7 = false, g9 = false, f5 = false, f7 = false;
+	[[maybe_unused]] T st1[K][4] = {}, held[4] = {}, stp[K] = {}, heldp = 0, lop = 0;
+	[[maybe_unused]] unsigned pwin = 0;
+	[[maybe_unused]] T kp[3] = {}; // the coefficients of entry 5 in steps 0 and 2, of entry 7 in step 0
 	if constexpr (F01) {
 		e1m = c0 + lane * CPT + 3 == a.W - 1;
 		const unsigned m1 = end_mask_long<12>((c0 >> 1) + lane * 4 - 4, a.W >> 1);
@@ -332,9 +352,15 @@ static __device__ __forceinline__ void fwd_sweep_tile(const FwdLevelArgs &a, con
 		g5 = (m1 >> 5) & 1;
 		g7 = (m1 >> 7) & 1;
 		g9 = (m1 >> 9) & 1;
-		const bool last_tile = tx == g.ntx - 1;
-		own0 = last_tile || lane < 60;
-		own1 = (tx == 0 || lane >= 1) && (last_tile || lane <= 60);
+		const int p = lane & 7;
+		const int pe = p < 4 ? c0 - 8 + 2 * p : c0 + TW + 2 * (p - 4);
+		pwin = (unsigned)(p < 4 ? TW + 2 * p : TW + kHalo + 2 * (p - 4)) * 4;
+		const unsigned mp = end_mask_long<9>(pe - 4, a.W);
+		f5 = (mp >> 5) & 1;
+		f7 = (mp >> 7) & 1;
+		kp[0] = f5 ? 2.0f * W::fk(0) : W::fk(0);
+		kp[1] = f5 ? 2.0f * W::fk(2) : W::fk(2);
+		kp[2] = f7 ? 2.0f * W::fk(0) : W::fk(0);
 	}
 	// (row_end_test of dwt_sweep2d.h written out, for the same reason)
 	// row r (any r the sweep meets) is an end of its column: r == 0 or r == H - 1 after reflection (one bounce when tall)
@@ -360,12 +386,21 @@ static __device__ __forceinline__ void fwd_sweep_tile(const FwdLevelArgs &a, con
 		// horizontal pass of the two rows (2q-1, 2q)
 		T row[2][CPT];
 		[[maybe_unused]] T xs[2][kPairRows ? NARR : 1];
+		// (F01) the lane's phantom column: the windows of both rows, issued ahead of the main columns' reads and complete
+		// with them (LDS reads return in order: no wait of their own)
+		[[maybe_unused]] u4 pw[2][2];
+		[[maybe_unused]] unsigned pw8[2];
+		[[maybe_unused]] T rowp[2] = {};
+		if constexpr (F01) {
+			const unsigned pa = ring_off + (unsigned)rslot * RS * 4 + pwin;
+			lds_issue_win9x2(pa, pa + RS * 4, pw[0][0], pw[0][1], pw8[0], pw[1][0], pw[1][1], pw8[1]);
+		}
 #pragma unroll
 		for (int rr = 0; rr < 2; rr++) {
 			const unsigned base = ring_off + (unsigned)(rslot + rr) * RS * 4;
 			const unsigned own = base + lane * CPT * 4;
-			const unsigned la = lane == 0 ? base + TW * 4 : own - 16;
-			const unsigned ra = lane == 63 ? base + TW * 4 + 16 : own + CPT * 4;
+			const unsigned la = lane == 0 ? base + (TW + kHaloL) * 4 : own - 16;
+			const unsigned ra = lane == 63 ? base + (TW + kHaloR) * 4 : own + CPT * 4;
 			T x[NARR];
 			u4 L4, R4, O0, O1;
 			if constexpr (kShuffle) {
@@ -437,6 +472,32 @@ static __device__ __forceinline__ void fwd_sweep_tile(const FwdLevelArgs &a, con
 			// both rows at once, as the halves of packed operations: the same steps, the same rounding (the compiler pairs
 			// within a row on its own, but not all of it, and the selects at the two candidate entries split its pairs)
 			typedef float f2 __attribute__((ext_vector_type(2)));
+			if constexpr (F01) {
+				// the phantom column: the four steps on the shrinking window as the main columns take them (entries 5 and 7 by
+				// selection, coefficients kp), the scale
+				const f2 nz = f2{-0.0f, -0.0f};
+				lds_arrived_win9x2(pw[0][0], pw[0][1], pw8[0], pw[1][0], pw[1][1], pw8[1]);
+				f2 w2[9];
+#pragma unroll
+				for (int j = 0; j < 8; j++)
+					w2[j] = f2{from_bits<T>(pw[0][j >> 2][j & 3]), from_bits<T>(pw[1][j >> 2][j & 3])};
+				w2[8] = f2{from_bits<T>(pw8[0]), from_bits<T>(pw8[1])};
+#pragma unroll
+				for (int s_ = 0; s_ < K; s_++) {
+#pragma unroll
+					for (int j = s_ + 1; j <= 7 - s_; j += 2) {
+						if (j == 5)
+							w2[j] = w2[j] + kp[s_ >> 1] * (w2[j - 1] + (f5 ? nz : w2[j + 1]));
+						else if (j == 7)
+							w2[j] = w2[j] + kp[2] * (w2[j - 1] + (f7 ? nz : w2[j + 1]));
+						else
+							w2[j] = w2[j] + W::fk(s_) * (w2[j - 1] + w2[j + 1]);
+					}
+				}
+				const f2 sc = w2[4] * W::fwd_scale(0, 1.0f);
+				rowp[0] = sc[0];
+				rowp[1] = sc[1];
+			}
 			f2 x2[NARR];
 #pragma unroll
 			for (int j = 0; j < NARR; j++)
@@ -503,11 +564,29 @@ static __device__ __forceinline__ void fwd_sweep_tile(const FwdLevelArgs &a, con
 				ve[s_] = row_is_end(2 * (q0 + it) - 1 - s_);
 				any = any || ve[s_];
 			}
+			// (F01) the phantom column's pass: the main columns' steps on its one column, in the form they take this iteration
+			[[maybe_unused]] auto vertical_phantom = [&](auto sel, const T *kv) {
+				if constexpr (F01) {
+					T n[K + 1];
+					n[0] = rowp[1];
+#pragma unroll
+					for (int s_ = 0; s_ < K; s_++) {
+						const bool e = decltype(sel)::value && ve[s_];
+						n[s_ + 1] = (s_ ? stp[s_ - 1] : rowp[0]) + (decltype(sel)::value ? kv[s_] : W::fk(s_)) * ((e ? T(-0.0) : stp[s_]) + n[s_]);
+					}
+					lop = n[K] * W::fwd_scale(0, 1.0f);
+#pragma unroll
+					for (int s_ = 0; s_ < K; s_++)
+						stp[s_] = n[s_];
+				}
+			};
 			auto vertical_sel = [&]() {
 				T kv[K];
 #pragma unroll
 				for (int s_ = 0; s_ < K; s_++)
 					kv[s_] = sel_coef<W, false>(s_, ve[s_]);
+				if constexpr (F01)
+					vertical_phantom(std::true_type{}, kv);
 				if constexpr (kPairRows && K != 1)
 					vertical_pairs<W, CPT, true>(row, st, lo, hi, ve, kv);
 				else
@@ -520,8 +599,11 @@ static __device__ __forceinline__ void fwd_sweep_tile(const FwdLevelArgs &a, con
 			else if (__builtin_expect(any, 0)) {
 				DWT_END_PATH();
 				vertical_sel();
-			} else
+			} else {
 				vertical(ColTag<kColNone>{});
+				if constexpr (F01)
+					vertical_phantom(std::false_type{}, nullptr);
+			}
 		} else {
 			vertical(ColTag<kColNone>{});
 		}
@@ -590,7 +672,7 @@ static __device__ __forceinline__ void fwd_sweep_tile(const FwdLevelArgs &a, con
 			typedef float f2 __attribute__((ext_vector_type(2)));
 			const f2 nz = f2{-0.0f, -0.0f};
 			const int k = q0 + it - K / 2; // the pair of level 0 this iteration completes (k and `it` are both even or both odd)
-			if (k >= A && k < B && own0) {
+			if (k >= A && k < B) {
 				const unsigned clb = (unsigned)((c0 + lane * CPT) >> 1) * 4;
 				const T *top = out_h + (long)k * a.h_pitch, *bot = out_h + (long)(Hd + k) * a.h_pitch;
 				const unsigned nb = (unsigned)Wd * 4;
@@ -603,16 +685,23 @@ static __device__ __forceinline__ void fwd_sweep_tile(const FwdLevelArgs &a, con
 #pragma unroll
 				for (int e = 0; e < 4; e++)
 					held[e] = lo[2 * e];
+				heldp = lop;
 			} else {
 				// level 1, iteration q1: its rows 2 q1 - 1 (held) and 2 q1 (this LL row), as the halves of packed operations
 				const int q1 = k >> 1, W1 = Wd, H1 = Hd;
 				f2 y[12];
+				const unsigned pb0 = to_bits(heldp), pb1 = to_bits(lop);
 #pragma unroll
 				for (int e = 0; e < 4; e++) {
 					const unsigned b0 = to_bits(held[e]), b1 = to_bits(lo[2 * e]);
-					y[e] = f2{from_bits<T>(from_left_lane(b0)), from_bits<T>(from_left_lane(b1))};
+					// (lanes 0 and 63: the phantom columns -- lane e of the lane's quad holds the e-th left one in lanes 0..3, the e-th
+					// right one in lanes 60..63: one quad broadcast serves both.  It goes in as the shift's `old` operand, not through
+					// a select on the lane: the compiler turns such a select into a branch and runs the shift with the lane masked
+					// out, which then no longer serves its neighbour as a source)
+					const unsigned q0e = quad_lane(pb0, e), q1e = quad_lane(pb1, e);
+					y[e] = f2{from_bits<T>(from_left_lane(b0, q0e)), from_bits<T>(from_left_lane(b1, q1e))};
 					y[4 + e] = f2{held[e], lo[2 * e]};
-					y[8 + e] = f2{from_bits<T>(from_right_lane(b0)), from_bits<T>(from_right_lane(b1))};
+					y[8 + e] = f2{from_bits<T>(from_right_lane(b0, q0e)), from_bits<T>(from_right_lane(b1, q1e))};
 				}
 #pragma unroll
 				for (int s_ = 0; s_ < K; s_++) {
@@ -664,7 +753,7 @@ static __device__ __forceinline__ void fwd_sweep_tile(const FwdLevelArgs &a, con
 					hi1[v + 2] = h2[1];
 				}
 				const int k1 = q1 - K / 2;
-				if (k1 >= (A >> 1) && k1 < (B >> 1) && own1) {
+				if (k1 >= (A >> 1) && k1 < (B >> 1)) {
 					// level 1's Mallat rows in the LL quadrant of level 0: [LL | HL] at row k1, [LH | HH] at row H1 / 2 + k1
 					const int W2 = W1 >> 1, H2 = H1 >> 1;
 					const unsigned cb = (unsigned)((c0 >> 2) + lane * 2) * 4, nb = (unsigned)W2 * 4;
@@ -725,7 +814,7 @@ __global__ __launch_bounds__(256) void k_fwd_sweep(FwdLevelArgs a, SweepGeom g)
 	fwd_sweep_any_tile<W, CPT, RING, NT, IL, false>(a, g);
 }
 
-// levels 0 and 1 of a float 9/7 transform in one sweep over overlapped tiles (fwd_sweep_tile, F01)
+// levels 0 and 1 of a float 9/7 transform in one sweep (fwd_sweep_tile, F01)
 template <int NT>
 __global__ __launch_bounds__(256) void k_fwd_sweep01(FwdLevelArgs a, SweepGeom g)
 {
@@ -891,9 +980,7 @@ bool fwd01_can(Wavelet w, int W, int H)
 
 int fwd01_tiles(int W)
 {
-	// tile t reaches LL column 240 t + 255: the first tile that holds the last LL column is the last one
-	const int W1 = W >> 1;
-	return W1 <= 256 ? 1 : (W1 - 256 + 239) / 240 + 1;
+	return (W + 511) / 512; // the level-0 sweep's own tiles
 }
 
 hipError_t launch_fwd01(const FwdLevelArgs &a, const SweepTuning &t, hipStream_t s)
@@ -915,7 +1002,7 @@ hipError_t launch_fwd01(const FwdLevelArgs &a, const SweepTuning &t, hipStream_t
 	}
 	const long tiles = (long)g.ntx * ((Hd + g.tile_pairs - 1) / g.tile_pairs);
 	const dim3 grid((unsigned)((tiles + waves - 1) / waves), a.batch);
-	const size_t lds = (size_t)waves * 16 * (64 * 8 + 8) * 4;
+	const size_t lds = (size_t)waves * 16 * (64 * 8 + 32) * 4; // (139 264 B of 160 KiB for four waves: one workgroup per CU, as the level-0 sweep's deep ring)
 	// Cache policy as fwd_pick reads `nt`: loads and detail stores non-temporal whatever its bits 0 and 1 say; bit 2 keeps
 	// the LL band's stores -- here level 1's -- temporal while the launch's bands fit the Infinity Cache (as fwd_level_t
 	// decides it).  Bit 3, a ring of 8 rows and 4 columns per lane have no fused kernel: pair01_ok keeps such settings
