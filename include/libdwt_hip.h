@@ -700,6 +700,95 @@ int dwt_hip_picture_inverse_batch(int wavelet, int fmt, void *pix, size_t pix_ba
 	size_t pix_stride, size_t chan_stride, int batch, int channels, int order, int depth, int offset, float scale, int colour,
 	const void *planes, size_t plane_stride, size_t plane_row_pitch, int size_x, int size_y, int j);
 
+/* Deadzone quantization of coefficient planes: the float coefficients of the irreversible path (ICT +
+ * DWT_HIP_CDF97_S / _H) <-> sign-magnitude integer indices, the deadzone scalar quantizer of ITU-T T.800 Annex E with one
+ * step per subband, plus the two summaries a coder asks for next.  An extension: the reference has no quantizer; this
+ * comment is the specification (tests/quant_model.py restates it in numpy, the device is held to it bit for bit).
+ *
+ * Frames.  `batch` dense Mallat frames of size_x x size_y samples (size_o == size_i, elements adjacent): sample (x, y) of
+ * frame b lies at coef + b*coef_batch_stride + y*coef_row_pitch + x*(2 or 4) and at index + b*index_batch_stride +
+ * y*index_row_pitch + x*(2 or 4), all in bytes.  `coef_type` DWT_HIP_COEF_S (binary32) or _H (binary16), `index_type`
+ * DWT_HIP_INDEX_I16 or _I32; addresses and strides are multiples of the element size.  Slots, level rules and geometry
+ * are those of dwt_hip_bands_apply_batch: 3J + 1 slots, HL, LH, HH of level 1 .. J and then LL(J), J =
+ * dwt_hip_band_levels(size_x, size_y, j_max) with j_max the count the forward transform returned, the rectangles those
+ * of dwt_hip_band_geometry.  `steps` is a HOST array with one step per slot; table_stride 0: one table for all frames,
+ * otherwise frame b reads steps + b*table_stride (at least the slot count).
+ *
+ * Quantize.  Per slot inv = 1.0f / step, an IEEE binary32 division made on the host.  Per sample c (binary16 widened
+ * to binary32 first, exactly): m = fabsf(c) * inv, ONE rounded product; k = (int)m by truncation, with NaN giving 0 and
+ * m >= 32768.0f (int16) or m >= 2147483648.0f (int32) giving 32767 or 2147483647 -- both cases count as CLIPPED; the index
+ * is -k where the sign bit of c is set and k otherwise, so -0.0f and everything inside the deadzone give 0.
+ *
+ * Dequantize.  q == 0 gives +0.0f.  Otherwise a = (float)|q|, the magnitude taken so that INT32_MIN gives 2147483648.0f;
+ * v = (a + r) * step, a rounded sum and a rounded product (never contracted); the sign of q is applied to v; a binary16
+ * destination rounds v once more, to nearest even.  r in [0, 1) is the reconstruction offset: with r = 0.5 (or any r that
+ * keeps (a + r) * step inside the index's cell) quantizing the result returns q; r = 0 is legal but puts the value on the
+ * cell's edge, where the product's rounding decides.
+ *
+ * `stats` (quantize; HOST memory, may be NULL): {nonzero indices, largest magnitude k, clipped samples} as three long
+ * long per slot per frame, frame b's at stats + 3*slots*b.  Summed with integer atomics only: every run gives the same
+ * values.  The magnitude bit-planes of a band are the bit length of its largest magnitude.
+ *
+ * dwt_hip_quant_norms (host code, no device): norm_l[j-1] and norm_h[j-1], j = 1 .. levels <= 16, the L2 norms of this
+ * library's 1-D synthesis functions: a 1 at coefficient 32 of the 64 L (resp. H) coefficients of level j of a line of
+ * 64 << j samples, every other coefficient 0, inverted j levels in double with the wavelet's binary32 constants widened
+ * (the scaling factors as the float kernels form them), the root of the sum of the squares.  DWT_HIP_CDF97_S (use it for
+ * _CDF97_H too), _CDF53_S and _INTERP53_S; any other wavelet is an error.
+ * dwt_hip_quant_steps (host code): steps[slot] = (float)((double)base_step / (n_x * n_y)) for the 3*levels + 1 slots,
+ * HL(j): n_x = norm_h[j], n_y = norm_l[j]; LH(j): n_x = norm_l[j], n_y = norm_h[j]; HH(j): both norm_h[j]; LL: both
+ * norm_l[levels].  levels 0 .. 16, base_step finite and > 0.  Both return 0, or nonzero with dwt_hip_last_error.
+ *
+ * Code-blocks.  A band is cut into blocks of 2^cb_log2_x x 2^cb_log2_y samples (each exponent 2 .. 10, their sum at most
+ * 12), anchored at the band's first sample, partial blocks at the right and at the bottom.  dwt_hip_codeblock_layout fills
+ * first[0 .. slots] (the prefix of the slots' block counts, the last entry the total) and blocks_x[0 .. slots-1] (blocks
+ * across; either may be NULL) and returns the total, -1 for bad arguments; an empty band has no blocks.
+ * dwt_hip_codeblock_bitplanes_batch stores planes[b*planes_frame_stride + first[slot] + by*blocks_x[slot] + bx] = the bit
+ * length (0 .. 32) of the largest |q| of block (bx, by): 0 for a block of zeros, 32 for one that holds INT32_MIN.  `planes`
+ * is host or device memory, planes_frame_stride at least the total (the bytes between the frames' maps are left alone).
+ * Index planes whose base, row pitch and batch stride are multiples of 16 bytes are read by whole aligned 16-byte chunks
+ * (option "quant_wide" = 0: element by element, like every other plane; same bytes out): the chunk that holds the last
+ * element of the last row is read whole, up to 15 bytes past that element inside the same aligned 16 bytes -- read, never
+ * used, never written.
+ *
+ * Each of coef, index and planes is host or device memory on its own.  Device sides are ordered on the context's stream:
+ * ONE kernel launch for the whole batch and the whole table (the tables cross in one small copy), no allocation after
+ * the first call of a size; a call on device memory without `stats` does not wait for the device.  A host side is mirrored
+ * in a device buffer of the context (a written region with bytes outside the frames is uploaded first, so that they come
+ * back as they were) and the call ends synchronised, and so does every call with `stats`.  Only the frames' own elements
+ * are written.  A lane moves a run of 16 / (the smaller element size) samples of a row; a side whose base, row pitch and
+ * batch stride are multiples of 16 bytes moves by 16-byte accesses, any other side element by element (option
+ * "quant_wide" = 0: every side): same bits.  dwt_hip_quant_route tells which: the OR of DWT_HIP_QUANT_WIDE_COEF and
+ * _WIDE_INDEX for a call with these addresses (either direction), -1 for arguments the entries refuse; it holds for device
+ * sides (a host side runs on its mirror, which is aligned).
+ * In place: binary32 <-> int32 with coef == index and equal pitches and batch strides IS supported, in both directions
+ * (a lane reads its run before it writes it).  Every other contact is refused: the two regions, from the first frame's
+ * first byte to the last frame's last, must not share a byte.
+ * Errors (nonzero, dwt_hip_last_error, nothing launched, nothing written): a step that is not finite or not > 0, r outside
+ * [0, 1), a null pointer, negative sizes, a pitch below its row, frames closer than they span, addresses or strides that
+ * are no multiple of the element size, unknown types, `stats` in device memory, regions that overlap. */
+enum dwt_hip_coef_type { DWT_HIP_COEF_S = 0, DWT_HIP_COEF_H = 1 };
+enum dwt_hip_index_type { DWT_HIP_INDEX_I16 = 0, DWT_HIP_INDEX_I32 = 1 };
+#define DWT_HIP_QUANT_MAX_LEVELS 16 /* of dwt_hip_quant_norms / _steps */
+#define DWT_HIP_QUANT_GRID_ROWS 16384 /* rows / frames one trip of the quantizer's loops covers */
+#define DWT_HIP_QUANT_GRID_BATCH 4096
+#define DWT_HIP_CODEBLOCK_GRID_BLOCKS 65536 /* code-blocks one trip of the bit-plane kernel's loop covers */
+#define DWT_HIP_QUANT_WIDE_COEF 1
+#define DWT_HIP_QUANT_WIDE_INDEX 2
+int dwt_hip_quant_norms(int wavelet, int levels, double *norm_l, double *norm_h);
+int dwt_hip_quant_steps(int wavelet, int levels, float base_step, float *steps);
+int dwt_hip_quantize_batch(int coef_type, const void *coef, size_t coef_batch_stride, size_t coef_row_pitch, int index_type,
+	void *index, size_t index_batch_stride, size_t index_row_pitch, int batch, int size_x, int size_y, int j_max,
+	const float *steps, size_t table_stride, long long *stats);
+int dwt_hip_dequantize_batch(int index_type, const void *index, size_t index_batch_stride, size_t index_row_pitch, int coef_type,
+	void *coef, size_t coef_batch_stride, size_t coef_row_pitch, int batch, int size_x, int size_y, int j_max,
+	const float *steps, size_t table_stride, float r);
+int dwt_hip_quant_route(int coef_type, const void *coef, size_t coef_batch_stride, size_t coef_row_pitch, int index_type,
+	const void *index, size_t index_batch_stride, size_t index_row_pitch, int batch, int size_x, int size_y);
+int dwt_hip_codeblock_layout(int size_x, int size_y, int j_max, int cb_log2_x, int cb_log2_y, int *first, int *blocks_x);
+int dwt_hip_codeblock_bitplanes_batch(int index_type, const void *index, size_t index_batch_stride, size_t index_row_pitch,
+	int batch, int size_x, int size_y, int j_max, int cb_log2_x, int cb_log2_y, unsigned char *planes,
+	size_t planes_frame_stride);
+
 /* Time-frequency planes of line batches: the Gaussian-window STFT, the complex Morlet CWT and the S transform of
  * src/gabor.c (gabor_ft_s, gabor_wt_s, gabor_st_s and their _arg_ twins; include/gabor.h), DESIGN.md s14.
  *

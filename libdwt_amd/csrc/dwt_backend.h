@@ -57,10 +57,11 @@ struct Ctx {
 	Buf nterm_ws; // N-term approximation: ranks, select histograms, records (dwt_backend_nterm.hip)
 	Buf half_f32; // float 9/7 on binary16 storage, line-pass route: the binary32 copies of a level's frame (dwt_backend.hip)
 	Buf px_pix, px_planes, px_tmp; // pixel front end: the device mirrors of a host call's pixels and planes, the composite entries' plane stack (dwt_backend_pixels.hip)
+	Buf q_coef, q_index, q_planes, q_ws; // quantization: the device mirrors of a host call's coefficients, indices and bit-plane maps; the step tables and the band counters (dwt_backend_quant.hip)
 	// every device scratch buffer above: a new one is declared there, listed here, and named nowhere else for freeing
 	auto bufs()
 	{
-		return std::array{&stage_img, &ll[0], &ll[1], &frame_a, &frame_b, &vol_out, &vol_host[0], &vol_host[1], &eaw_w, &eaw_ll[0], &eaw_ll[1], &feat_ws, &swt_ws, &cond_ws, &band_ws, &nterm_ws, &half_f32, &px_pix, &px_planes, &px_tmp};
+		return std::array{&stage_img, &ll[0], &ll[1], &frame_a, &frame_b, &vol_out, &vol_host[0], &vol_host[1], &eaw_w, &eaw_ll[0], &eaw_ll[1], &feat_ws, &swt_ws, &cond_ws, &band_ws, &nterm_ws, &half_f32, &px_pix, &px_planes, &px_tmp, &q_coef, &q_index, &q_planes, &q_ws};
 	}
 	hipEvent_t dl_ev[8] = {}; // strip events of the host downloads (dwt_host_xfer.hip), created once
 	hipEvent_t switch_ev = nullptr; // dwt_hip_set_stream: orders a newly set stream behind the old one's work
@@ -76,6 +77,7 @@ struct Ctx {
 	int swt2d_fused = 1; // SWT levels of dense device images below SWT2D_FUSED_LEVELS in one launch each (0: a row pass and a column pass, the cross-check)
 	int wp_fused = 1; // wavelet packets: lines of up to N1D_MAX samples in one launch, dense device images one launch per level (0: every node through the exact line passes, the cross-check)
 	int pixels_wide = 1; // pixel front end: aligned sides move by 16-byte accesses (0: element by element everywhere, the cross-check)
+	int quant_wide = 1; // quantization: aligned sides move by 16-byte accesses (0: element by element everywhere, the cross-check)
 	int swt_fused = 1; // SWT lines of up to N1D_MAX samples in one launch (0: one launch per level, the cross-check)
 	// options
 	SweepTuning tune;
@@ -263,6 +265,31 @@ int swt_device(Wavelet w, const char *src, long ls, long es, int n_lines, int N,
 	char *dst_l, long l_es, int l_mode, long plane_stride, long dls);
 // the median magnitude of one band of every frame of a batch, the frames only read (dwt_backend_features.hip) -> med (host)
 int band_abs_median(const void *ptr, long bstride, int batch, long stride_x, int fw, int fh, int x0, int y0, int w, int h, float *med);
+// A side of a call that lies in host or in device memory on its own (the pixel front end, the quantizer): a host side is
+// mirrored in a device buffer of the context -- its whole region crosses PCIe -- and a written one crosses back.
+struct Side {
+	const void *p; // as the caller gave it
+	size_t extent; // bytes from p to the end of the last element
+	bool dense;    // every byte of the region is an element of the frame
+};
+// *acc += count * stride, false on overflow
+inline bool mul_add(long *acc, long count, long stride)
+{
+	long t;
+	return !__builtin_mul_overflow(count, stride, &t) && !__builtin_add_overflow(*acc, t, acc);
+}
+inline bool all16(std::initializer_list<uintptr_t> v)
+{
+	uintptr_t o = 0;
+	for (uintptr_t x : v)
+		o |= x;
+	return o % 16 == 0;
+}
+// outputs that fit the Infinity Cache with room to spare are stored temporal: what reads them next -- level 0 of the
+// transform, the next operator, a copy to the host -- finds them there.  Larger ones would only push each other out
+inline int nt_for(size_t out_bytes) { return out_bytes > ((size_t)128 << 20); }
+int mirror(const Side &s, Buf &buf, bool upload, char **dev, bool *is_host); // a host side's mirror in `buf`; *dev: where the kernel finds the side
+int mirror_back(const Side &s, const Buf &buf);
 int prof_drain();
 void prof_before(int level = 0);
 void prof_after(int level = 0);

@@ -23,12 +23,6 @@ static_assert(PIXELS_PER_LANE == DWT_HIP_PIXELS_PER_LANE && PIXELS_GRID_ROWS == 
 static_assert((int)kPlaneI16 == DWT_HIP_PLANE_I16 && (int)kPlaneI32 == DWT_HIP_PLANE_I32 && (int)kPlaneH == DWT_HIP_PLANE_H && (int)kPlaneS == DWT_HIP_PLANE_S,
 	"plane types");
 
-struct Side {
-	const void *p; // as the caller gave it
-	size_t extent; // bytes from p to the end of the last element
-	bool dense;    // every byte of the region is an element of the frame
-};
-
 // a checked call: the kernel's arguments on the caller's pointers, and what the driver needs beyond them
 struct PixCall {
 	PixelsArgs a;
@@ -36,20 +30,6 @@ struct PixCall {
 	bool inverse;
 	Side pix, planes;
 };
-
-bool mul_add(long *acc, long count, long stride)
-{
-	long t;
-	return !__builtin_mul_overflow(count, stride, &t) && !__builtin_add_overflow(*acc, t, acc);
-}
-
-bool all16(std::initializer_list<uintptr_t> v)
-{
-	uintptr_t o = 0;
-	for (uintptr_t x : v)
-		o |= x;
-	return o % 16 == 0;
-}
 
 // Which side moves by 16-byte accesses (dwt_pixels.hip) -- from addresses and strides alone.  Strides that the call does
 // not use (one picture, one row, one channel, one plane) arrive as 0.
@@ -182,10 +162,6 @@ int pixels_check(PixCall *c, bool inverse, int fmt, const void *pix, size_t pix_
 	return 0;
 }
 
-// outputs that fit the Infinity Cache with room to spare are stored temporal: what reads them next -- level 0 of the
-// transform, a copy to the host -- finds them there.  Larger ones would only push each other out
-int nt_for(size_t out_bytes) { return out_bytes > ((size_t)128 << 20); }
-
 int convert(const PixCall &c, char *pix, char *planes)
 {
 	PixelsArgs a = c.a;
@@ -193,27 +169,6 @@ int convert(const PixCall &c, char *pix, char *planes)
 	pixels_route(&a, c.pt, c.inverse);
 	a.nt_out = nt_for(c.inverse ? c.pix.extent : c.planes.extent);
 	return launched(launch_pixels(c.pt, c.plane, c.inverse, a, g.stream), "pixels", c.inverse ? "planes to pixels" : "pixels to planes");
-}
-
-// a host side's mirror in `buf`; *dev: where the kernel finds the side
-int mirror(const Side &s, Buf &buf, bool upload, char **dev, bool *is_host)
-{
-	*is_host = !dwt_hip_is_device_pointer(s.p);
-	*dev = (char *)s.p;
-	if (!*is_host)
-		return 0;
-	if (grow(buf, s.extent))
-		return 1;
-	*dev = (char *)buf.p;
-	if (upload)
-		HIP_TRY(hipMemcpyAsync(buf.p, s.p, s.extent, hipMemcpyHostToDevice, g.stream));
-	return 0;
-}
-
-int mirror_back(const Side &s, const Buf &buf)
-{
-	HIP_TRY(hipMemcpyAsync((void *)s.p, buf.p, s.extent, hipMemcpyDeviceToHost, g.stream));
-	return 0;
 }
 
 // wavelet < 0: the conversion alone
@@ -284,6 +239,27 @@ int pixels_call(PixCall &c, int wavelet, int *j)
 }
 
 } // namespace
+
+// a host side's mirror in `buf`; *dev: where the kernel finds the side
+int mirror(const Side &s, Buf &buf, bool upload, char **dev, bool *is_host)
+{
+	*is_host = !dwt_hip_is_device_pointer(s.p);
+	*dev = (char *)s.p;
+	if (!*is_host)
+		return 0;
+	if (grow(buf, s.extent))
+		return 1;
+	*dev = (char *)buf.p;
+	if (upload)
+		HIP_TRY(hipMemcpyAsync(buf.p, s.p, s.extent, hipMemcpyHostToDevice, g.stream));
+	return 0;
+}
+
+int mirror_back(const Side &s, const Buf &buf)
+{
+	HIP_TRY(hipMemcpyAsync((void *)s.p, buf.p, s.extent, hipMemcpyDeviceToHost, g.stream));
+	return 0;
+}
 
 } // namespace dwtb
 

@@ -483,6 +483,57 @@ struct BandOpsArgs {
 };
 hipError_t launch_band_ops(const BandOpsArgs &a, hipStream_t s);
 
+// Deadzone quantization of coefficient planes (dwt_quant.hip): float coefficients <-> sign-magnitude
+// indices, one step per slot of a dense Mallat frame, one launch per call.  Sample (x, y) of frame b at
+// coef + b*coef_bs + y*coef_pitch + x*(coef element) and index + b*index_bs + y*index_pitch + x*(index element), bytes.
+constexpr int QUANT_WG_ROWS = 4;       // rows per workgroup: one per wave
+constexpr int QUANT_GRID_ROWS = 16384; // rows one trip of the kernel's row loop covers (grid.y * QUANT_WG_ROWS)
+constexpr int QUANT_GRID_BATCH = 4096; // frames one trip of its batch loop covers (grid.z)
+constexpr int QUANT_MAX_LEVELS = 31;
+constexpr int QUANT_STAT_WORDS = 3;    // per slot: nonzero indices, largest magnitude, clipped samples
+enum QuantCoef { kCoefS = 0, kCoefH = 1 };      // (DWT_HIP_COEF_*)
+enum QuantIndex { kIndexI16 = 0, kIndexI32 = 1 }; // (DWT_HIP_INDEX_*)
+constexpr int quant_coef_es(int t) { return t == kCoefH ? 2 : 4; }
+constexpr int quant_index_es(int t) { return t == kIndexI16 ? 2 : 4; }
+// samples of a lane's run: the narrower side is one 16-byte access
+constexpr int quant_run(int coef, int index) { return 16 / (quant_coef_es(coef) < quant_index_es(index) ? quant_coef_es(coef) : quant_index_es(index)); }
+struct QuantArgs {
+	char *coef;
+	long coef_pitch, coef_bs;
+	char *index;
+	long index_pitch, index_bs;
+	int batch, W, H, J;
+	// xb[j], yb[j]: the first column / row of the H half of level j = 1 .. J (the band table's x of HL(j), y of LH(j));
+	// a position's column level is the smallest j with x >= xb[j], J + 1 (L) where there is none; rows alike
+	int xb[QUANT_MAX_LEVELS + 1], yb[QUANT_MAX_LEVELS + 1];
+	const float *tab; // device: frame b reads tab[b*tstride + slot] -- 1 / step (quantize), step (dequantize)
+	long tstride;
+	float r;          // dequantize: the reconstruction offset
+	// quantize: null, or QUANT_STAT_WORDS counters per slot per frame per copy, cleared before the launch; workgroups
+	// spread over stat_copies (a power of two) copies, which the driver folds
+	unsigned long long *stats;
+	int stat_copies;
+	int wide_coef, wide_index; // that side moves by 16-byte accesses (quant_route)
+	int nt_out;                // the wide stores are non-temporal
+};
+hipError_t launch_quant(int coef, int index, bool inverse, const QuantArgs &a, hipStream_t s);
+// The magnitude bit-planes of every code-block: a band of slot k is cut into blocks of (1 << cbx) x (1 << cby) samples from
+// its first sample on; planes[b*planes_bs + first[k] + by*blocks_x[k] + bx] = bit length of the block's largest |q|.
+constexpr int CODEBLOCK_WG_BLOCKS = 4;      // code-blocks per workgroup: one per wave
+constexpr int CODEBLOCK_GRID = 16384;       // workgroups of one trip of the kernel's loop
+struct CodeblockArgs {
+	const char *index;
+	long index_pitch, index_bs;
+	int batch, nslots, cbx, cby;
+	int wide; // base, row pitch and batch stride are multiples of 16 bytes: rows are read by 16-byte chunks
+	int x0[BAND_MAX_SLOTS], y0[BAND_MAX_SLOTS], w[BAND_MAX_SLOTS], h[BAND_MAX_SLOTS];
+	int first[BAND_MAX_SLOTS + 1]; // prefix of the slots' block counts
+	int blocks_x[BAND_MAX_SLOTS];
+	unsigned char *planes;
+	long planes_bs;
+};
+hipError_t launch_codeblock_bitplanes(int index, const CodeblockArgs &a, hipStream_t s);
+
 // N-term approximation (dwt_nterm.hip): keep the coefficients of the n largest magnitudes of every group
 // of 1 .. 4 dense frames, zero the rest.  The key of a position is the uint32 image of its float magnitude (sign bit 0:
 // unsigned order is float order); a radix select over 11 + 10 + 10 bits finds the key of descending rank n, one
