@@ -91,8 +91,22 @@ void dwt_hip_set_stream(void *hip_stream);
 /* The running-LL scratch of the 2-D Mallat drivers (two bands: the level-1 band, ceil(W/2) x ceil(H/2)
  * elements per image, and the level-2 band) in memory the CALLER owns and places -- the library then
  * neither grows nor frees it (a call that needs more fails).  Two NULLs hand the scratch back to the
- * library.  Per thread, like the rest of the context. */
+ * library.  Per thread, like the rest of the context.
+ * The bytes a call needs of band k (k = 0, 1) for a batch of n images of W x H elements of es bytes, exactly:
+ *     align_up(ceil(W / 2^(k+1)), 4) * ceil(H / 2^(k+1)) * es * n + 64
+ * (rows of the band lie align_up(width, 4) elements apart, images one after the other; 64 bytes of slack behind them).
+ * A call that finds either band smaller is refused ("too small") before it writes anything.  The interleaved entries
+ * keep their pyramid in the library's own scratch and are refused while the caller owns the bands. */
 int dwt_hip_set_workspace(void *band0, size_t bytes0, void *band1, size_t bytes1);
+/* The scratch contract.  The content of every scratch buffer of a context -- a caller-owned workspace included -- is
+ * UNSPECIFIED on entry to any call and after it, and no result depends on it: every call writes what it reads.
+ * dwt_hip_fill_workspace holds the library to that: it stores `word` into every 32-bit word of every scratch buffer the
+ * calling thread's context holds at that moment (the caller-owned bands included; the trailing bytes of a buffer whose
+ * size is no multiple of 4 take the word's low bytes), on the context's stream, and does not synchronise.  It is a test
+ * instrument and an explicit call: nothing in the library calls it.  The one piece of state that outlives a call inside
+ * scratch are the counters behind dwt_hip_rows_warnings; after a fill that query answers as before any conditioning
+ * call (it fails).  Returns 0, or 1 with dwt_hip_last_error set. */
+int dwt_hip_fill_workspace(unsigned word);
 void dwt_hip_sync(void);
 
 /* Placement.  The rate of a forward level depends on where in PHYSICAL memory its three streams lie
@@ -408,7 +422,8 @@ int dwt_hip_rows_condition(unsigned ops, void *ptr, size_t line_stride, size_t e
 /* dwt_util_get_center1_s of every row */
 int dwt_hip_rows_center_index(const void *ptr, size_t line_stride, size_t elem_stride, int n_lines, int size, int *center);
 /* What the reference would have warned about in the centre evaluations of this thread's last dwt_hip_rows_condition or
- * dwt_hip_rows_center_index call: how many found a zero norm, how many found no crossing index (each optional) */
+ * dwt_hip_rows_center_index call: how many found a zero norm, how many found no crossing index (each optional).  The
+ * counters lie in scratch: after dwt_hip_fill_workspace the query fails as it does before any such call. */
 int dwt_hip_rows_warnings(int *zero_norm, int *no_index);
 /* dwt_util_find_min_max_s of every row (as values: which of +0 / -0 stands for an extreme zero is unspecified) */
 int dwt_hip_rows_min_max(const void *ptr, size_t line_stride, size_t elem_stride, int n_lines, int size, float *min, float *max);

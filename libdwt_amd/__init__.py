@@ -42,7 +42,64 @@ if not os.path.exists(LIB_PATH):
         "or `make -C libdwt_amd/csrc` (hipcc, gfx950). libdwt_amd has no CPU fallback."
     )
 
-lib = C.CDLL(LIB_PATH)
+_cdll = C.CDLL(LIB_PATH)
+
+# ---- the scratch contract: fill and poison mode (include/libdwt_hip.h) ---------------------------------
+# Entries that are NEVER preceded by a fill while poison_workspace is on.  A deny list, not an allow list: an entry added
+# later and forgotten here is poisoned like every transform, and fails loudly if it keeps state in scratch.
+NEVER_PREFILLED = frozenset((
+    "dwt_hip_fill_workspace",  # the fill itself
+    # lifecycle, device, stream and workspace setters, options
+    "dwt_hip_init", "dwt_hip_finish", "dwt_hip_sync", "dwt_hip_set_device", "dwt_hip_get_device", "dwt_hip_device_count",
+    "dwt_hip_device_name", "dwt_hip_set_stream", "dwt_hip_set_workspace", "dwt_hip_set_option", "dwt_hip_get_option",
+    "dwt_util_init", "dwt_util_finish", "dwt_util_set_accel", "dwt_util_get_accel",
+    # allocation and copies
+    "dwt_hip_malloc", "dwt_hip_free", "dwt_hip_malloc_host", "dwt_hip_free_host", "dwt_hip_alloc_batch", "dwt_hip_alloc_volumes",
+    "dwt_hip_grant_access", "dwt_hip_memcpy_h2d", "dwt_hip_memcpy_d2h",
+    # the bank objects
+    "dwt_hip_timefreq_bank_create", "dwt_hip_timefreq_bank_from_kernels", "dwt_hip_timefreq_bank_free", "dwt_hip_timefreq_bank_bins",
+    "dwt_hip_timefreq_bank_taps", "dwt_hip_timefreq_bank_query",
+    # queries of a previous call or of a pointer: a fill in front of them would change the answer or is pointless
+    "dwt_hip_last_error", "dwt_hip_is_device_pointer", "dwt_hip_rows_warnings", "dwt_hip_features_raw_sums", "dwt_hip_placement_report",
+    "dwt_hip_alloc_batch_note", "dwt_hip_alloc_batch_report", "dwt_hip_prof_enable", "dwt_hip_prof_read", "dwt_hip_prof_read_levels",
+))
+_poison = None  # the word, or None: off
+
+
+class _Prefilled:
+    """A library function behind a fill of the calling thread's scratch.  Attributes (argtypes, restype) are the function's."""
+
+    def __init__(self, fn):
+        object.__setattr__(self, "_fn", fn)
+
+    def __call__(self, *args):
+        if _poison is not None and _cdll.dwt_hip_fill_workspace(_poison):
+            raise DwtError("dwt_hip_fill_workspace: " + _cdll.dwt_hip_last_error().decode(errors="replace"))
+        return self._fn(*args)
+
+    def __getattr__(self, name):
+        return getattr(self._fn, name)
+
+    def __setattr__(self, name, value):
+        setattr(self._fn, name, value)
+
+
+class _Lib:
+    """A thin proxy over the CDLL: the same function objects, or -- while poison_workspace is on -- every function that is
+    not in NEVER_PREFILLED behind a fill.  It sees only the calls made from Python, that is top-level calls: a fill inside
+    the library would destroy the scratch of an entry that calls another entry (the picture entries, the 3-D host entries)."""
+
+    def __getattr__(self, name):
+        fn = getattr(_cdll, name)
+        if _poison is None or name in NEVER_PREFILLED or name.startswith("_"):
+            return fn
+        return _Prefilled(fn)
+
+    def __setattr__(self, name, value):
+        setattr(_cdll, name, value)
+
+
+lib = _Lib()
 
 _I, _P, _S = C.c_int, C.c_void_p, C.c_size_t
 _FWD = [_P, _I, _I, _I, _I, _I, _I, C.POINTER(_I), _I, _I]
@@ -72,6 +129,8 @@ lib.dwt_hip_last_error.restype = C.c_char_p
 lib.dwt_hip_set_stream.argtypes = [_P]
 lib.dwt_hip_set_workspace.argtypes = [_P, C.c_size_t, _P, C.c_size_t]
 lib.dwt_hip_set_workspace.restype = _I
+lib.dwt_hip_fill_workspace.argtypes = [C.c_uint]
+lib.dwt_hip_fill_workspace.restype = _I
 lib.dwt_hip_transform2d_batch_sharded.argtypes = [_I, _I, _P, _P, C.c_size_t, _I, _I, _I, _I, C.POINTER(_I), C.POINTER(_I), _I]
 lib.dwt_hip_transform2d_batch_sharded.restype = _I
 _PP = C.POINTER(_P)
@@ -220,6 +279,21 @@ def use_torch_stream():
 
 def sync():
     lib.dwt_hip_sync()
+
+
+def fill_workspace(word):
+    """dwt_hip_fill_workspace: `word` into every 32-bit word of every scratch buffer of this thread's context (a
+    caller-owned workspace included), on the context's stream, without a synchronise.  No result depends on it."""
+    _check(lib.dwt_hip_fill_workspace(int(word) & 0xFFFFFFFF), "dwt_hip_fill_workspace")
+
+
+def poison_workspace(word):
+    """The poison mode of the tests: while `word` is not None, every call made through `lib` -- except the entries of
+    NEVER_PREFILLED -- is preceded by fill_workspace(word) on the calling thread.  None turns it off.  Returns the
+    previous setting."""
+    global _poison
+    before, _poison = _poison, (None if word is None else int(word) & 0xFFFFFFFF)
+    return before
 
 
 def set_option(name, value):
@@ -818,7 +892,8 @@ def _vector_entry(name):
             fv = np.zeros(count_subbands(size_o_x, size_o_y, size_i_x, size_i_y, j_max), dtype=np.float32)
         if not lib.dwt_hip_is_device_pointer(_addr(ptr)) and lib.dwt_hip_init():
             raise DwtError(lib.dwt_hip_last_error().decode())  # (the C entry would abort)
-        fn(_addr(ptr), stride_x, stride_y, size_o_x, size_o_y, size_i_x, size_i_y, j_max, fv.ctypes.data, *[float(q) for q in p])
+        getattr(lib, "dwt_util_%s_s" % name)(_addr(ptr), stride_x, stride_y, size_o_x, size_o_y, size_i_x, size_i_y, j_max, fv.ctypes.data,
+                                             *[float(q) for q in p])
         return fv
 
     entry.__name__ = "dwt_util_%s_s" % name
@@ -837,7 +912,7 @@ def _band_entry(name, extra):
     def entry(ptr, stride_x, stride_y, size_x, size_y, *more):
         if lib.dwt_hip_init():
             raise DwtError(lib.dwt_hip_last_error().decode())
-        return fn(_addr(ptr), stride_x, stride_y, size_x, size_y, *more)
+        return getattr(lib, "dwt_util_band_%s_s" % name)(_addr(ptr), stride_x, stride_y, size_x, size_y, *more)
 
     entry.__name__ = "dwt_util_band_%s_s" % name
     return entry

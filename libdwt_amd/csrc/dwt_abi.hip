@@ -1,5 +1,5 @@
-// dwt_abi.hip -- the device-level C-ABI of include/libdwt_hip.h: lifecycle, options, memory helpers,
-// kernel timing and the 2-D transform entries (argument checks, host / device dispatch).
+// dwt_abi.hip -- the device-level C-ABI of include/libdwt_hip.h: lifecycle, options, the workspace (the caller's bands,
+// the fill), memory helpers, kernel timing and the 2-D transform entries (argument checks, host / device dispatch).
 #include "dwt_backend.h"
 
 #include <climits>
@@ -191,6 +191,25 @@ int dwt_hip_set_workspace(void *band0, size_t bytes0, void *band1, size_t bytes1
 	g.ll[0] = Buf{band0, bytes0};
 	g.ll[1] = Buf{band1, bytes1};
 	g.ll_external = true;
+	return 0;
+}
+
+// Every scratch buffer the context holds, through bufs() alone: a buffer declared later is filled without being named here.
+// Plain memsets on the stream: no kernel of the library, nothing counted in stat_launches or stat_allocs.
+int dwt_hip_fill_workspace(unsigned word)
+{
+	if (check_inited())
+		return 1;
+	for (Buf *b : g.bufs()) {
+		if (!b->p || !b->bytes)
+			continue;
+		const size_t words = b->bytes / 4;
+		if (words)
+			HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)b->p, (int)word, words, g.stream));
+		for (size_t k = 4 * words; k < b->bytes; k++) // the word's low bytes
+			HIP_TRY(hipMemsetD8Async((hipDeviceptr_t)((char *)b->p + k), (unsigned char)(word >> (8 * (k & 3))), 1, g.stream));
+	}
+	cond_forget_warnings();
 	return 0;
 }
 

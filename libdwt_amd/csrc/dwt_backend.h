@@ -263,6 +263,8 @@ int host_inverse_pipelined(const Call2d &c, const void *src, void *dst, int stri
 bool swt_fused_ok(const void *src, long ls, long es, int N);
 int swt_device(Wavelet w, const char *src, long ls, long es, int n_lines, int N, int level0, int levels, char *dst_h, long h_es,
 	char *dst_l, long l_es, int l_mode, long plane_stride, long dls);
+// the warning counters of dwt_hip_rows_warnings lie in cond_ws: forgotten when the scratch is overwritten (dwt_backend_condition.hip)
+void cond_forget_warnings();
 // the median magnitude of one band of every frame of a batch, the frames only read (dwt_backend_features.hip) -> med (host)
 int band_abs_median(const void *ptr, long bstride, int batch, long stride_x, int fw, int fh, int x0, int y0, int w, int h, float *med);
 // A side of a call that lies in host or in device memory on its own (the pixel front end, the quantizer): a host side is

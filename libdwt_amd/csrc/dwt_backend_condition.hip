@@ -155,6 +155,8 @@ bool use_fused(int n_lines, int size)
 
 } // namespace
 
+void cond_forget_warnings() { t_warn_valid = false; }
+
 } // namespace dwtb
 
 using namespace dwtb;

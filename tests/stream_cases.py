@@ -75,6 +75,7 @@ TABLE.update({
     "swt1d_batch": ASYNC, "swt_features1d_batch": _RECORDS, "swt2d_batch": ASYNC, "swt2d_level": ASYNC,
     "timefreq_batch": ASYNC, "phase_derivative": ASYNC, "detect_ridges": ASYNC,
     "transform3d": ASYNC, "transform3d_op": ASYNC,
+    "fill_workspace": ASYNC,  # (memsets on the context's stream: DESIGN.md s27)
 })
 
 _MIRROR = "a one-line mirror of %s, which is in the table"
@@ -93,6 +94,7 @@ EXCLUDED = {
     "dwt_util_count_subbands_s": _NO_WORK, "eaw53_weights_layout": _NO_WORK, "dwt_eaw53_2f_dummy_s": _NO_WORK, "feature_mask": _NO_WORK,
     "rows_op_mask": _NO_WORK, "device_count": _NO_WORK, "device_name": _NO_WORK, "get_device": _NO_WORK, "set_device": _NO_WORK,
     "get_option": _NO_WORK, "set_option": _NO_WORK, "last_error": _NO_WORK, "set_stream": _NO_WORK, "use_torch_stream": _NO_WORK,
+    "poison_workspace": "a switch of the Python package, no device work of its own: it puts fill_workspace, which is in the table, in front of the calls made through `lib`",
     "sync": "the synchronise itself", "dwt_util_init": _NO_WORK, "dwt_util_finish": "synchronises and frees the context",
     "dwt_util_get_accel": _NO_WORK, "dwt_util_set_accel": _NO_WORK, "dwt_util_viewport": _NO_WORK, "dwt_util_crop21": _NO_WORK,
     "dwt_util_subband_const_s": _NO_WORK, "volume_of": _NO_WORK, "timefreq_bank": "host tables; the bank's upload is a blocking hipMemcpy at first use",
@@ -157,10 +159,12 @@ class Case:
     values that go with the input; call(dwt, P, host) makes the call on the addresses P[name] and returns its host results;
     want(bufs) -> {buffer name: array after the call, "ret": host results}, from the CPU models alone; same: the family's
     comparison of one buffer (same_for: of the buffers named there); check_ret(got, want): of the host results; options: set
-    for the call, restored after it."""
+    for the call, restored after it; setup(dwt, P) / teardown(dwt): around the call, outside what is timed and while the
+    stream is idle (they may synchronise)."""
 
-    def __init__(self, name, entry, make, call, want, same=same_bytes, check_ret=None, options=None, same_for=None):
+    def __init__(self, name, entry, make, call, want, same=same_bytes, check_ret=None, options=None, same_for=None, setup=None, teardown=None):
         self.name, self.entry, self.make, self.call, self._want, self.same = name, entry, make, call, want, same
+        self.setup, self.teardown = setup, teardown
         self.same_for = same_for or {}
         self.check_ret = check_ret or (lambda got, want: got == want)
         self.options = options or {}
@@ -870,6 +874,22 @@ def _timefreq():
         cases.append(Case("detect_ridges %d" % kind, "detect_ridges", lambda s, kind=kind: planes_in(s, "ridges%d" % kind),
                           lambda dwt, P, h, kind=kind: dwt.detect_ridges(kind, P["x"], P["y"], N * 4, 4, N, rows, 0.5, 2, rows * N * 4),
                           op_want(lambda p, f=f: f(p, 0.5)), same_floats))
+    # The fill of the scratch, seen through a caller-owned workspace: the two bands are the case's buffers.
+    # Their "input" arrives behind the delay; a fill that ran early or on another stream is overwritten by it.
+    # (It stands in this family because no other case here uses the LL bands: handing them over frees the library's own.)
+    FILL = 0xA5C3F00D
+    sizes = {"b0": 1000, "b1": 77}
+
+    def own(dwt, P):
+        assert dwt.lib.dwt_hip_set_workspace(P["b0"], 4 * sizes["b0"], P["b1"], 4 * sizes["b1"]) == 0, dwt.last_error()
+
+    def hand_back(dwt):
+        assert dwt.lib.dwt_hip_set_workspace(None, 0, None, 0) == 0, dwt.last_error()
+    cases.append(Case(
+        "fill_workspace over a caller-owned workspace", "fill_workspace",
+        lambda s: {k: _rng(s, "fill" + k).integers(0, 1 << 31, size=n).astype(np.uint32) for k, n in sizes.items()},
+        lambda dwt, P, h: dwt.fill_workspace(FILL), lambda b: {k: np.full(n, FILL, np.uint32) for k, n in sizes.items()},
+        setup=own, teardown=hand_back))
     return cases
 
 
@@ -997,6 +1017,8 @@ class Harness:
         for name, value in case.options.items():
             dwt.set_option(name, value)
         try:
+            if case.setup:
+                case.setup(dwt, {k: v[0].data_ptr() for k, v in dev.items()})
             n0 = dwt.get_option("stat_launches")
             with t.cuda.stream(S):
                 t0 = time.perf_counter()
@@ -1015,6 +1037,8 @@ class Harness:
                 idle = S.query()
             launches = dwt.get_option("stat_launches") - n0
         finally:
+            if case.teardown:
+                case.teardown(dwt)
             for name in case.options:
                 dwt.set_option(name, DEFAULT_OPTIONS[name])
         return t1 - t0, launches, early, idle, ret

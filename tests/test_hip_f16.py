@@ -43,7 +43,9 @@ def dwt():
     import libdwt_amd as d
 
     d.dwt_util_init()
+    d.poison_workspace(0xFFFFFFFF)  # every call below starts on scratch that holds NaN / -1 in every word
     yield d
+    d.poison_workspace(None)
     for k, v in (("generic", 0), ("tile_pairs", 0), ("waves", 4), ("xcd_swizzle", 1), ("fuse01", 1), ("fma", 0)):
         d.set_option(k, v)
     d.dwt_util_finish()

@@ -44,7 +44,9 @@ def dwt():
     import libdwt_amd as d
 
     d.dwt_util_init()
+    d.poison_workspace(0xFFFFFFFF)  # every call below starts on scratch that holds NaN / -1 in every word
     yield d
+    d.poison_workspace(None)
     for k, v in (("fma", 0), ("vol_fused", 1), ("vol_tile_pairs", 0), ("il_exact_borders", 1)):
         d.set_option(k, v)
     d.dwt_util_set_accel(0)

@@ -31,7 +31,9 @@ def dwt():
     d.dwt_util_init()
     d.pixels = pixels
     assert pixels.PIXELS_PER_LANE == PPL
+    d.poison_workspace(0xFFFFFFFF)  # every call below starts on scratch that holds NaN / -1 in every word
     yield d
+    d.poison_workspace(None)
     d.set_option("pixels_wide", 1)
 
 

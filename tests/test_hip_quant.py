@@ -32,7 +32,9 @@ def dwt():
     d.dwt_util_init()
     d.quant = quant
     assert (quant.GRID_ROWS, quant.GRID_BATCH) == (16384, 4096) and (quant.S, quant.H, quant.I16, quant.I32) == (qm.S, qm.H, qm.I16, qm.I32)
+    d.poison_workspace(0xFFFFFFFF)  # every call below starts on scratch that holds NaN / -1 in every word
     yield d
+    d.poison_workspace(None)
     d.set_option("quant_wide", 1)
 
 

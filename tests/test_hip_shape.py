@@ -26,7 +26,9 @@ def dwt():
     import libdwt_amd as d
 
     d.dwt_util_init()
-    return d
+    d.poison_workspace(0xFFFFFFFF)  # every call below starts on scratch that holds NaN / -1 in every word
+    yield d
+    d.poison_workspace(None)
 
 
 @pytest.fixture(scope="module")

@@ -45,6 +45,45 @@ def test_every_public_entry_is_classified():
     assert sorted(f for fams in sc.THREAD_FAMILIES for f in fams) == sorted(sc.FAMILIES)
 
 
+def test_poison_mode_wraps_every_entry_that_is_not_denied():
+    """The poison mode of the package (libdwt_amd.poison_workspace): every name on its deny list is an exported
+    symbol of the library; every dwt_hip_* symbol the headers declare is on the list or comes back behind a fill while the
+    switch is on; with the switch off `lib` hands out the plain CDLL functions.  No device is touched."""
+    import re
+
+    import libdwt_amd as dwt
+
+    missing = sorted(n for n in dwt.NEVER_PREFILLED if not hasattr(dwt._cdll, n))
+    assert not missing, "on the deny list, not exported: %s" % missing
+    declared = set()
+    inc = os.path.join(ROOT, "include")
+    for header in os.listdir(inc):
+        if header.endswith(".h"):
+            declared.update(re.findall(r"\b(dwt_hip_\w+)\s*\(", open(os.path.join(inc, header)).read()))
+    exported = sorted(n for n in declared if hasattr(dwt._cdll, n))
+    assert len(exported) > 100 and "dwt_hip_fill_workspace" in exported and "dwt_hip_transform2d_batch" in exported
+    assert dwt.poison_workspace(None) is None, "the switch was left on"
+    for n in exported:
+        assert getattr(dwt.lib, n) is getattr(dwt._cdll, n), n
+    try:
+        dwt.poison_workspace(0xFFFFFFFF)
+        for n in exported:
+            fn = getattr(dwt.lib, n)
+            if n in dwt.NEVER_PREFILLED:
+                assert fn is getattr(dwt._cdll, n), n
+            else:
+                assert isinstance(fn, dwt._Prefilled) and fn._fn is getattr(dwt._cdll, n), n
+                assert fn.argtypes is getattr(dwt._cdll, n).argtypes  # (the function's own attributes)
+        assert isinstance(dwt.lib.dwt_cdf97_2f_s, dwt._Prefilled), "the libdwt.h entries are wrapped too"
+        for n in ("dwt_hip_fill_workspace", "dwt_hip_rows_warnings", "dwt_hip_memcpy_d2h", "dwt_hip_set_workspace", "dwt_hip_last_error"):
+            assert n in dwt.NEVER_PREFILLED
+        for n in ("dwt_hip_transform2d", "dwt_hip_rows_condition", "dwt_hip_quantize_batch", "dwt_hip_picture_forward_batch", "dwt_hip_tune"):
+            assert n not in dwt.NEVER_PREFILLED
+    finally:
+        assert dwt.poison_workspace(None) == 0xFFFFFFFF
+    assert dwt.lib.dwt_hip_transform2d is dwt._cdll.dwt_hip_transform2d
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("run", sc.RUNS)
 def test_entries_hold_to_the_callers_stream(run):

@@ -61,7 +61,9 @@ def dwt():
 
     d.dwt_util_init()
     DEFAULTS.update({k: d.get_option(k) for k in KNOBS})
+    d.poison_workspace(0xFFFFFFFF)  # every call below starts on scratch that holds NaN / -1 in every word
     yield d
+    d.poison_workspace(None)
     restore(d)
     d.dwt_util_finish()
 

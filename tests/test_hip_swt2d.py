@@ -28,7 +28,9 @@ def dwt():
 
     d.dwt_util_init()
     assert (d.SWT2D_FUSED_LEVELS, d.SWT2D_TILE_W, d.SWT2D_TILE_H) == (FUSED, TW, TH)
+    d.poison_workspace(0xFFFFFFFF)  # every call below starts on scratch that holds NaN / -1 in every word
     yield d
+    d.poison_workspace(None)
     d.set_option("swt2d_fused", 1)
 
 

@@ -33,7 +33,9 @@ def dwt():
     import libdwt_amd as d
 
     d.dwt_util_init()
+    d.poison_workspace(0xFFFFFFFF)  # every call below starts on scratch that holds NaN / -1 in every word
     yield d
+    d.poison_workspace(None)
     d.set_option("timefreq_tiled", 1)
 
 

@@ -29,7 +29,9 @@ def dwt():
 
     d.dwt_util_init()
     d.packets = packets
+    d.poison_workspace(0xFFFFFFFF)  # every call below starts on scratch that holds NaN / -1 in every word
     yield d
+    d.poison_workspace(None)
     d.set_option("wp_fused", 1)
 
 
