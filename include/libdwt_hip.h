@@ -44,6 +44,7 @@
 #define LIBDWT_HIP_H
 
 #include <stddef.h>
+#include <stdint.h>
 
 #ifdef __cplusplus
 extern "C" {
@@ -633,6 +634,61 @@ int dwt_hip_wp_features1d_batch(unsigned feature_mask, const void *ptr, size_t l
 	int n_lines, int N, int level, int order, float p, float *fv, size_t fv_stride);
 int dwt_hip_wp_features2d_batch(unsigned feature_mask, const void *ptr, size_t batch_stride, int batch, int stride_x,
 	int size_x, int size_y, int level, int order, float p, float *fv, size_t fv_stride);
+
+/* Best basis and pruned wavelet packet trees of row batches (1-D only).  An extension, like the packets
+ * themselves: a leaf of a pruned tree holds, bit for bit, what that node holds in the full tree of its depth.
+ *
+ * Trees.  A tree of depth `levels` (1 <= levels <= min(floor(log2 N), DWT_HIP_WP_TREE_MAX_LEVELS)) is a bitmap of
+ * DWT_HIP_WP_TREE_WORDS uint32_t (128 bytes whatever `levels`).  Node k (natural index) of level j has the heap index
+ * h = 2^j + k; bit h (word h >> 5, bit h & 31) set means "this node is split into (j+1, 2k) and (j+1, 2k+1)".  Bit 0 and the
+ * bits of levels >= `levels` mean nothing.  The EFFECTIVE tree is what can be reached from the root through set bits: a set
+ * bit below a clear one is ignored, on the host and on the device alike, so a tree in device memory needs no validation and
+ * no synchronisation.  Node geometry is that of dwt_hip_wp_nodes; the leaves of any effective tree tile [0, N), and a
+ * transformed line holds each leaf (j, k) at [start_j(k), start_j(k) + len_j(k)).
+ *
+ * Costs.  Additive, one term per coefficient c, evaluated in double with x = (double)c, e = x*x:
+ *   DWT_HIP_WP_COST_SHANNON     e == 0 ? 0 : -e*log(e)
+ *   DWT_HIP_WP_COST_LOG_ENERGY  e == 0 ? 0 : log(e)
+ *   DWT_HIP_WP_COST_LP          |x|^param, 0 < param < 2 (param == 1: fabs(x), no pow)
+ *   DWT_HIP_WP_COST_THRESHOLD   |c| > param ? 1 : 0, param >= 0, compared in float
+ * The term of a non-finite c is NaN; a bad kind or param is an error.  A node's cost is the sum of its terms in double, in
+ * an order that is fixed: the same bits on every run, for every batch size and every position of the line in the batch (no
+ * float atomics).  The one-launch route and the cross-check route may differ from each other in rounding.
+ *
+ * Selection, bottom-up: best[h] = cost[h] at level `levels`; above, c = best[2h] + best[2h+1] (L child first), the node is
+ * split iff c < cost[h], then best[h] = c, else best[h] = cost[h].  A tie keeps the parent; so does a NaN on either side
+ * (the comparison is false).  Trees that the library writes hold effective bits only.  The total is best[1]. */
+#define DWT_HIP_WP_TREE_MAX_LEVELS 10
+#define DWT_HIP_WP_TREE_WORDS 32
+enum dwt_hip_wp_cost {
+	DWT_HIP_WP_COST_SHANNON = 0,
+	DWT_HIP_WP_COST_LOG_ENERGY = 1,
+	DWT_HIP_WP_COST_LP = 2,
+	DWT_HIP_WP_COST_THRESHOLD = 3
+};
+/* Host helpers, no device.  The best tree of a table of 2^(levels+1) node costs in heap order ([0] unused): the tree
+ * (DWT_HIP_WP_TREE_WORDS words) and the total; either output may be NULL.  Returns 0, -1 for bad arguments. */
+int dwt_hip_wp_best_tree(int levels, const double *cost, uint32_t *tree, double *total);
+/* the leaves of the effective tree from left to right: level, natural index, start and length of each (any array may be
+ * NULL; at most 2^levels entries).  Returns the number of leaves, -1 for bad arguments. */
+int dwt_hip_wp_tree_leaves(int N, int levels, const uint32_t *tree, int *level, int *index, int *start, int *len);
+/* The search: the cost of every node of levels 0 .. `levels` of every line, the best tree of each line and, where dst is
+ * not NULL, the line in that tree.  Wavelets, stride rules, the apart-or-interleaved rule, in place (src == dst) and the
+ * overlap check are those of dwt_hip_wp1d_batch.  Outputs, each optional, at least one of the four not NULL, all in the
+ * memory space of src: dst; tree -- line i's at (char *)tree + i*tree_stride, tree_stride >= 128 bytes and a multiple of 4;
+ * total -- n_lines doubles; node_cost -- line i's 2^(levels+1) doubles in heap order, [0] = the total, at (char *)node_cost
+ * + i*cost_stride, cost_stride >= 8 * 2^(levels+1) bytes and a multiple of 8.  dst == NULL: costs and tree only, no
+ * coefficient is stored.  Device memory: everything is ordered on the context's stream; the entry neither waits for the
+ * stream nor reads anything back (the selection runs on the device).  Dense or strided device lines of up to 8192 samples
+ * take ONE launch; longer lines and every call under option "wp_fused" = 0 run level by level through the exact line passes
+ * and small helper kernels.  Host memory: synchronous, through the staging path. */
+int dwt_hip_wp_best1d_batch(int wavelet, int cost, float param, const void *src, void *dst, size_t line_stride, size_t elem_stride,
+	int n_lines, int N, int levels, uint32_t *tree, size_t tree_stride, double *total, double *node_cost, size_t cost_stride);
+/* The transform in a given tree, forward or inverse (the inverse rebuilds exactly the nodes that the tree splits).  tree in
+ * the memory space of src, line i's at (char *)tree + i*tree_stride; tree_stride 0: one tree for every line.  Everything
+ * else as dwt_hip_wp1d_batch; with the full tree of depth `levels` the bits are those of dwt_hip_wp1d_batch. */
+int dwt_hip_wp_tree1d_batch(int wavelet, int inverse, const void *src, void *dst, size_t line_stride, size_t elem_stride, int n_lines,
+	int N, int levels, const uint32_t *tree, size_t tree_stride);
 
 /* The pixel front end: pictures of 8- or 16-bit unsigned pixels <-> the planes the 2-D transforms take,
  * with the DC level shift and the component transforms of ITU-T T.800 Annex G.  An extension: the reference's picture

@@ -8,6 +8,9 @@
 //        src -> dst <-> one scratch frame, arranged so that the last level lands in dst;
 //   everything else -- longer lines, strided image elements, and every call under option "wp_fused" = 0 -- level by level in
 //        two dense staged frames, each node through the exact line passes (launch_line_pass).  Same bits.
+// Pruned trees and the best-basis search of lines: ONE launch of k_wp_tree / k_wp_best (dwt_wp_basis.hip)
+// where wp1d takes one launch; otherwise the full tree level by level as above, with small helper kernels after each level
+// (costs, the selection, the gathering of the leaves).  Nothing is read back on either route.
 #include "dwt_backend.h"
 
 #include <climits>
@@ -45,8 +48,10 @@ int line_pass(Wavelet w, bool inverse, const char *in, char *out, long ls, long 
 }
 
 // The cross-check route, 1-D: the dense frame A (n_lines rows of N samples) level by level, A <-> B; *res: where the
-// result lies.  A pass writes its node's samples only, and the nodes of a level tile the line.
-int lines_generic(Wavelet w, bool inverse, Img A, Img B, int n_lines, int N, int levels, Img *res)
+// result lies.  A pass writes its node's samples only, and the nodes of a level tile the line.  `after`: called behind
+// every level (the tree routes' helper kernels).
+int lines_generic(Wavelet w, bool inverse, Img A, Img B, int n_lines, int N, int levels, Img *res,
+	const std::function<int(int, Img)> &after = nullptr)
 {
 	Img in = A, out = B;
 	for (int step = 0; step < levels; step++) {
@@ -57,6 +62,8 @@ int lines_generic(Wavelet w, bool inverse, Img A, Img B, int n_lines, int N, int
 			if (line_pass(w, inverse, in.p + 4l * s, out.p + 4l * s, in.sx, 4, n_lines, n, false))
 				return 1;
 		}
+		if (after && after(lev, out)) // (the level just split / rebuilt, and the frame that holds it)
+			return 1;
 		std::swap(in, out);
 	}
 	*res = in;
@@ -243,6 +250,234 @@ int wp2d(int wavelet, bool inverse, const void *src, void *dst, long bs, int bat
 	return frame_unpack_stack(fd, batch, bs, A, pitch);
 }
 
+
+// ---- pruned trees and the best-basis search ------------------------------------------------------------
+
+// what wp1d checks, for the two tree entries; dst may be null where the entry allows it.  *ls: the stride the call runs with
+int tree_call_check(const char *what, int wavelet, Wavelet *w, const void *src, const void *dst, long *ls, long es, int n_lines, int N, int levels)
+{
+	if (wp_wavelet(wavelet, w))
+		return 1;
+	if (n_lines < 0 || N < 2)
+		return fail("%s: bad arguments (%d lines of %d samples; a line has 2 samples or more)", what, n_lines, N);
+	const int max_levels = std::min(floor_log2(N), WP_TREE_MAX_LEVELS);
+	if (levels < 1 || levels > max_levels)
+		return fail("%s: %d levels (a tree over a line of %d samples takes 1 .. %d)", what, levels, N, max_levels);
+	if (!src)
+		return fail("null pointer argument");
+	if (es < 4 || (n_lines > 1 && *ls < 4))
+		return fail("%s: bad strides (lines %ld bytes apart, elements %ld)", what, *ls, es);
+	if (n_lines <= 1)
+		*ls = es * N; // (not used: one line)
+	if (*ls < (N - 1l) * es + 4 && (*ls % 4 || *ls * n_lines > es))
+		return fail("%s: lines must be apart or interleaved within an element step (line stride %ld, element stride %ld, %d samples)", what,
+			*ls, es, N);
+	const size_t extent = (size_t)((std::max(n_lines, 1) - 1l) * *ls + (N - 1l) * es + 4);
+	if (dst && src != dst && overlap(src, extent, dst, extent))
+		return fail("%s: src and dst must be the same lines or not overlap", what);
+	return 0;
+}
+
+// every pointer of the list that is not null lies where src lies
+int same_space(bool dev, std::initializer_list<const void *> ptrs)
+{
+	for (const void *p : ptrs)
+		if (p && dev != (bool)dwt_hip_is_device_pointer(p))
+			return fail("src, dst and every table of the call must all be host or all be device pointers");
+	return 0;
+}
+
+// the scratch of the staged routes, carved from wp_ws: per line two tables of nt doubles, a total, a tree; the frame R
+struct TreeWs {
+	double *tab, *best, *total;
+	unsigned *tree;
+	Img R;
+};
+int tree_ws(int n_lines, int nt, long pitch, TreeWs *ws)
+{
+	const size_t tab = (size_t)n_lines * nt * 8, tot = (size_t)align_up(n_lines * 8l, 256), tr = (size_t)n_lines * 4 * WP_TREE_WORDS;
+	if (grow(g.wp_ws, 2 * tab + tot + tr + (size_t)pitch * n_lines + 256))
+		return 1;
+	char *p = (char *)g.wp_ws.p;
+	ws->tab = (double *)p, p += tab;
+	ws->best = (double *)p, p += tab;
+	ws->total = (double *)p, p += tot;
+	ws->tree = (unsigned *)p, p += align_up((long)tr, 256);
+	ws->R = Img{p, pitch, 4};
+	return 0;
+}
+
+// rows of `width` bytes between two places of one memory space or across PCIe, on the stream
+int copy_rows(void *dst, size_t dst_stride, const void *src, size_t src_stride, size_t width, int rows)
+{
+	HIP_TRY(hipMemcpy2DAsync(dst, dst_stride, src, src_stride, width, (size_t)rows, hipMemcpyDefault, g.stream));
+	return 0;
+}
+
+// the leaves of the trees out of the frame of one level (mode 0) / the spans of the nodes that are not split back into it (mode 1)
+int leaf_copy(Img from, Img to, int n_lines, int N, int levels, const unsigned *tree, long tree_words, int lev, int mode)
+{
+	return launched(launch_wp_leaf_copy(from.p, to.p, from.sx, n_lines, N, levels, tree, tree_words, lev, mode, g.stream), "packet tree", "leaf copy");
+}
+
+// The cross-check route of the transform in given trees (device memory, tree_words apart): the staged frame A, through
+// g.frame_b and ws.R.  Forward: the full tree level by level, the leaves of every level gathered in R.  Inverse: every node
+// of a level rebuilt, then the source spans of the nodes of that level that are not split put back -- what lies under a
+// leaf is rebuilt from garbage and overwritten on the way up.
+int tree_generic(Wavelet w, bool inverse, Img A, const TreeWs &ws, int n_lines, int N, int levels, const unsigned *tree, long tree_words, Img *res)
+{
+	if (grow(g.frame_b, (size_t)A.sx * n_lines))
+		return 1;
+	const Img B{(char *)g.frame_b.p, A.sx, 4};
+	if (!inverse) {
+		if (leaf_copy(A, ws.R, n_lines, N, levels, tree, tree_words, 0, 0))
+			return 1;
+		Img last;
+		if (lines_generic(w, false, A, B, n_lines, N, levels, &last,
+				[&](int lev, Img out) { return leaf_copy(out, ws.R, n_lines, N, levels, tree, tree_words, lev + 1, 0); }))
+			return 1;
+		*res = ws.R;
+		return 0;
+	}
+	HIP_TRY(hipMemcpyAsync(ws.R.p, A.p, (size_t)A.sx * n_lines, hipMemcpyDeviceToDevice, g.stream));
+	return lines_generic(w, true, A, B, n_lines, N, levels, res,
+		[&](int lev, Img out) { return leaf_copy(ws.R, out, n_lines, N, levels, tree, tree_words, lev, 1); });
+}
+
+int tree1d(int wavelet, bool inverse, const void *src, void *dst, long ls, long es, int n_lines, int N, int levels, const uint32_t *tree,
+	long tree_stride)
+{
+	Wavelet w;
+	if (tree_call_check("packet tree", wavelet, &w, src, dst, &ls, es, n_lines, N, levels))
+		return 1;
+	if (!dst || !tree)
+		return fail("null pointer argument");
+	if (tree_stride != 0 && (tree_stride < 4 * WP_TREE_WORDS || tree_stride % 4))
+		return fail("packet tree: trees are %d bytes or more apart, a multiple of 4, or 0 for one tree (got %ld)", 4 * WP_TREE_WORDS, tree_stride);
+	if (n_lines == 0)
+		return 0;
+	if (check_inited())
+		return 1;
+	const bool dev = dwt_hip_is_device_pointer(src);
+	if (same_space(dev, {dst, tree}))
+		return 1;
+	if (dev && check_dev_align({src, dst, tree}, {ls, es}))
+		return 1;
+	const bool fused = g.wp_fused && N <= N1D_MAX;
+	if (dev && fused)
+		return launched(launch_wp_tree(w, inverse, src, dst, ls, es, n_lines, N, levels, tree, tree_stride / 4, g.stream), "packet tree", "lines");
+
+	const Frame fs{(void *)src, ls, es, 4, N, n_lines, dev}, fd{dst, ls, es, 4, N, n_lines, dev};
+	if (frame_check(fs))
+		return 1;
+	Img A;
+	if (frame_stage(fs, g.frame_a, &A))
+		return 1;
+	TreeWs ws;
+	if (tree_ws(n_lines, 0, fused ? 0 : A.sx, &ws))
+		return 1;
+	const unsigned *d_tree = tree;
+	long d_words = tree_stride / 4;
+	if (!dev) { // the trees cross PCIe
+		if (copy_rows(ws.tree, 4 * WP_TREE_WORDS, tree, tree_stride ? tree_stride : 4 * WP_TREE_WORDS, 4 * WP_TREE_WORDS, tree_stride ? n_lines : 1))
+			return 1;
+		d_tree = ws.tree;
+		d_words = tree_stride ? WP_TREE_WORDS : 0;
+	}
+	Img res = A;
+	if (fused) {
+		if (launched(launch_wp_tree(w, inverse, A.p, A.p, A.sx, 4, n_lines, N, levels, d_tree, d_words, g.stream), "packet tree", "lines"))
+			return 1;
+	} else if (tree_generic(w, inverse, A, ws, n_lines, N, levels, d_tree, d_words, &res))
+		return 1;
+	return frame_unpack(fd, res.p, res.sx);
+}
+
+int best1d(int wavelet, int kind, float param, const void *src, void *dst, long ls, long es, int n_lines, int N, int levels, uint32_t *tree,
+	long tree_stride, double *total, double *node_cost, long cost_stride)
+{
+	Wavelet w;
+	if (tree_call_check("best basis", wavelet, &w, src, dst, &ls, es, n_lines, N, levels))
+		return 1;
+	if (kind < kWpCostShannon || kind > kWpCostThreshold)
+		return fail("best basis: cost %d (DWT_HIP_WP_COST_SHANNON .. _THRESHOLD)", kind);
+	if (kind == kWpCostLp && !(param > 0.0f && param < 2.0f))
+		return fail("best basis: the l^p cost takes 0 < param < 2 (got %g)", (double)param);
+	if (kind == kWpCostThreshold && !(param >= 0.0f && param <= 3.4028234663852886e38f))
+		return fail("best basis: the threshold cost takes a finite param >= 0 (got %g)", (double)param);
+	if (!dst && !tree && !total && !node_cost)
+		return fail("best basis: every output is NULL");
+	const int nt = 2 << levels;
+	if (tree && (tree_stride < 4 * WP_TREE_WORDS || tree_stride % 4))
+		return fail("best basis: trees are %d bytes or more apart, a multiple of 4 (got %ld)", 4 * WP_TREE_WORDS, tree_stride);
+	if (node_cost && (cost_stride < 8l * nt || cost_stride % 8))
+		return fail("best basis: cost tables of %d levels are %ld bytes or more apart, a multiple of 8 (got %ld)", levels, 8l * nt, cost_stride);
+	if (n_lines == 0)
+		return 0;
+	if (check_inited())
+		return 1;
+	const bool dev = dwt_hip_is_device_pointer(src);
+	if (same_space(dev, {dst, tree, total, node_cost}))
+		return 1;
+	if (dev && (check_dev_align({src, dst, tree}, {ls, es}) || (uintptr_t)total % 8 || (uintptr_t)node_cost % 8))
+		return fail("best basis: device memory takes addresses that are multiples of 4 bytes, of 8 for the doubles");
+	const bool fused = g.wp_fused && N <= N1D_MAX;
+	WpBestArgs a{};
+	a.n_lines = n_lines, a.N = N, a.levels = levels, a.kind = kind, a.param = param;
+	if (dev && fused) {
+		a.src = (const char *)src, a.dst = (char *)dst, a.line_stride = ls, a.elem_stride = es;
+		a.tree = tree, a.tree_words = tree_stride / 4, a.total = total, a.node_cost = node_cost, a.cost_doubles = cost_stride / 8;
+		return launched(launch_wp_best(w, a, g.stream), "best basis", "lines");
+	}
+
+	// the staging detour: the lines as a dense device frame, dense tables in the scratch, everything spread to the caller's
+	const Frame fs{(void *)src, ls, es, 4, N, n_lines, dev}, fd{dst, ls, es, 4, N, n_lines, dev};
+	if (frame_check(fs))
+		return 1;
+	Img A;
+	if (frame_stage(fs, g.frame_a, &A))
+		return 1;
+	TreeWs ws;
+	if (tree_ws(n_lines, nt, fused ? 0 : A.sx, &ws))
+		return 1;
+	Img res = A;
+	if (fused) {
+		a.src = A.p, a.dst = dst ? A.p : nullptr, a.line_stride = A.sx, a.elem_stride = 4;
+		a.tree = ws.tree, a.tree_words = WP_TREE_WORDS, a.total = ws.total, a.node_cost = ws.tab, a.cost_doubles = nt;
+		if (launched(launch_wp_best(w, a, g.stream), "best basis", "lines"))
+			return 1;
+	} else {
+		// sweep 1: the full tree, the costs of the nodes of every level behind it
+		auto costs = [&](int j, Img f) {
+			return launched(launch_wp_cost_level(f.p, f.sx, n_lines, N, j, kind, param, ws.tab, nt, g.stream), "best basis", "level costs");
+		};
+		if (grow(g.frame_b, (size_t)A.sx * n_lines))
+			return 1;
+		Img last;
+		if (costs(0, A) || lines_generic(w, false, A, Img{(char *)g.frame_b.p, A.sx, 4}, n_lines, N, levels, &last,
+				[&](int lev, Img out) { return costs(lev + 1, out); }))
+			return 1;
+		// the selection works on a copy: the costs stay for the caller, entry 0 takes the total
+		HIP_TRY(hipMemcpyAsync(ws.best, ws.tab, (size_t)n_lines * nt * 8, hipMemcpyDeviceToDevice, g.stream));
+		if (launched(launch_wp_select(ws.best, n_lines, levels, ws.tree, nullptr, 0, ws.total, ws.tab, nt, g.stream), "best basis", "selection"))
+			return 1;
+		// sweep 2: the lines again (in place too: dst has not been written yet), the leaves gathered level by level
+		if (dst && (frame_stage(fs, g.frame_a, &A) || tree_generic(w, false, A, ws, n_lines, N, levels, ws.tree, WP_TREE_WORDS, &res)))
+			return 1;
+	}
+	if (tree && copy_rows(tree, tree_stride, ws.tree, 4 * WP_TREE_WORDS, 4 * WP_TREE_WORDS, n_lines))
+		return 1;
+	if (total && copy_rows(total, 8l * n_lines, ws.total, 8l * n_lines, 8l * n_lines, 1))
+		return 1;
+	if (node_cost && copy_rows(node_cost, cost_stride, ws.tab, 8l * nt, 8l * nt, n_lines))
+		return 1;
+	if (dst && frame_unpack(fd, res.p, res.sx))
+		return 1;
+	if (!dev)
+		HIP_TRY(hipStreamSynchronize(g.stream));
+	return 0;
+}
+
 } // namespace
 
 } // namespace dwtb
@@ -290,6 +525,23 @@ int dwt_hip_wp2d_batch(int wavelet, int inverse, const void *src, void *dst, siz
 	if (batch_stride > (size_t)LONG_MAX / 2 || stride_x < 0 || stride_y < 0)
 		return fail("packets 2-D: bad strides");
 	return wp2d(wavelet, inverse != 0, src, dst, (long)batch_stride, batch, stride_x, stride_y, size_x, size_y, levels);
+}
+
+int dwt_hip_wp_best1d_batch(int wavelet, int cost, float param, const void *src, void *dst, size_t line_stride, size_t elem_stride,
+	int n_lines, int N, int levels, uint32_t *tree, size_t tree_stride, double *total, double *node_cost, size_t cost_stride)
+{
+	if (line_stride > (size_t)LONG_MAX / 2 || elem_stride > INT_MAX || tree_stride > (size_t)LONG_MAX / 2 || cost_stride > (size_t)LONG_MAX / 2)
+		return fail("best basis: bad strides");
+	return best1d(wavelet, cost, param, src, dst, (long)line_stride, (long)elem_stride, n_lines, N, levels, tree, (long)tree_stride, total,
+		node_cost, (long)cost_stride);
+}
+
+int dwt_hip_wp_tree1d_batch(int wavelet, int inverse, const void *src, void *dst, size_t line_stride, size_t elem_stride, int n_lines,
+	int N, int levels, const uint32_t *tree, size_t tree_stride)
+{
+	if (line_stride > (size_t)LONG_MAX / 2 || elem_stride > INT_MAX || tree_stride > (size_t)LONG_MAX / 2)
+		return fail("packet tree: bad strides");
+	return tree1d(wavelet, inverse != 0, src, dst, (long)line_stride, (long)elem_stride, n_lines, N, levels, tree, (long)tree_stride);
 }
 
 } // extern "C"

@@ -213,6 +213,38 @@ static __host__ __device__ inline void wp_node(int N, int level, int k, int *sta
 // the same places in dst, which may be src.  Inverse: the leaves of depth `levels` back to the line.
 hipError_t launch_wp_lines(Wavelet w, bool inverse, const void *src, void *dst, long line_stride, long elem_stride, int n_lines,
 	int N, int levels, hipStream_t s);
+// Pruned packet trees and the best-basis search of lines (dwt_wp_basis.hip).  A tree: WP_TREE_WORDS words,
+// bit 2^j + k set = node k of level j is split; only what can be reached from the root through set bits counts.
+constexpr int WP_TREE_WORDS = 32, WP_TREE_MAX_LEVELS = 10; // (DWT_HIP_WP_TREE_WORDS, DWT_HIP_WP_TREE_MAX_LEVELS)
+enum WpCost { kWpCostShannon = 0, kWpCostLogEnergy = 1, kWpCostLp = 2, kWpCostThreshold = 3 }; // (enum dwt_hip_wp_cost)
+// the lines of launch_wp_lines (N <= N1D_MAX, levels <= WP_TREE_MAX_LEVELS) in the tree of each: line i's at tree + i*tree_words
+// (tree_words 0: one tree for all), ONE launch
+hipError_t launch_wp_tree(Wavelet w, bool inverse, const void *src, void *dst, long line_stride, long elem_stride, int n_lines, int N,
+	int levels, const unsigned *tree, long tree_words, hipStream_t s);
+struct WpBestArgs {
+	const char *src;
+	char *dst; // null: costs and tree only
+	long line_stride, elem_stride;
+	int n_lines, N, levels;
+	int tpl, vec; // (set by the launcher)
+	int kind;     // WpCost
+	float param;
+	unsigned *tree;    // null, or line i's at tree + i*tree_words
+	long tree_words;
+	double *total;     // null, or n_lines doubles
+	double *node_cost; // null, or line i's 2^(levels+1) doubles (heap order, [0] = total) at node_cost + i*cost_doubles
+	long cost_doubles;
+};
+// the costs of every node, the best tree and the line in that tree, ONE launch
+hipError_t launch_wp_best(Wavelet w, const WpBestArgs &a, hipStream_t s);
+// the helpers of the cross-check route: dense frames of n_lines rows `pitch` bytes apart, tables of 2^(levels+1) doubles a line
+hipError_t launch_wp_cost_level(const void *frame, long pitch, long n_lines, int N, int j, int kind, float param, double *tab, long tab_doubles,
+	hipStream_t s);
+hipError_t launch_wp_select(double *tab, long n_lines, int levels, unsigned *tree_ws, unsigned *tree, long tree_words, double *total,
+	double *node_cost, long cost_doubles, hipStream_t s);
+// mode 0: the samples whose leaf has depth lev; mode 1: depth <= lev
+hipError_t launch_wp_leaf_copy(const void *from, void *to, long pitch, long n_lines, int N, int levels, const unsigned *tree, long tree_words,
+	int lev, int mode, hipStream_t s);
 // One packet level of a batch of dense images, out of place: the 4^level nodes of every W x H image of src are split
 // (inverse: rebuilt from their four quarters) into dst.  Strides in BYTES, multiples of 4.
 constexpr int WP2D_TILE_W = 128, WP2D_TILE_H = 32; // a workgroup's tile of one node, samples

@@ -12,33 +12,22 @@
 // 2^levels, the spectra case) take s = q * n by index arithmetic; any other N walks the j path bits of q (wp_node).
 // Each pair is lifted from the 2K+1 register window of k_line_levels -- the same steps, end forms and scaling, reflected
 // at the NODE's ends -- so the bits are those of the reference's one-level line function applied to each node.
+// The level body is wp_level (dwt_wp_level.h), shared with the pruned-tree kernels of dwt_wp_basis.hip.
 //
 // LDS per line: 2 * r4(N) floats; 64 KiB at N1D_MAX, two workgroups per CU.
 #include "dwt_kernels.h"
 #include "dwt_lift.h"
 #include "dwt_line_lds.h"
 #include "dwt_device.h"
+#include "dwt_wp_level.h"
 
 namespace dwt {
-
-static __host__ __device__ __forceinline__ int wp_r4(int n) { return (n + 3) & ~3; }
-
-// end_mask (dwt_lift.h) for the window of a pair of a node of n samples.  The deep levels of a tree are all short nodes,
-// where end_mask reflects every entry with an integer division; but a window of m = 2K+1 samples around a pair of a node
-// of n > m samples leaves the node by less than K + 2 on either side -- one bounce, which maps no other index onto sample
-// 0 or n - 1 -- so there a sample is an end iff it IS one of the two (the form end_mask itself takes from 64 samples on).
-template <int m>
-static __device__ __forceinline__ unsigned node_end_mask(int g0, int n)
-{
-	return n > m ? end_mask_long<m>(g0, n) : end_mask<m>(g0, n);
-}
 
 template <class W, bool INV>
 __global__ __launch_bounds__(256) void k_wp_lines(const char *__restrict__ src, char *__restrict__ dst, long line_stride,
 	long elem_stride, int n_lines, int N, int levels, int tpl, int vec)
 {
 	using T = typename W::T;
-	constexpr int K = W::K;
 	extern __shared__ float lds_f[];
 	T *const lds = (T *)lds_f;
 	const int sub = threadIdx.x / tpl, t = threadIdx.x % tpl;
@@ -56,62 +45,8 @@ __global__ __launch_bounds__(256) void k_wp_lines(const char *__restrict__ src, 
 	for (int step = 0; step < levels; step++) {
 		__syncthreads();
 		const int lev = INV ? levels - 1 - step : step; // the level whose nodes are split (forward) / rebuilt (inverse)
-		const int nn = 1 << lev, a = N >> lev;
-		const int P = (a + ((N & (nn - 1)) != 0) + 1) >> 1; // slots per node: pairs of the longest node
-		if (active) {
-			int q = t / P, k = t % P;
-			const int dq = tpl / P, dk = tpl % P;
-			while (q < nn) {
-				int s0 = q * a, n = a;
-				if (!uniform)
-					wp_node(N, lev, q, &s0, &n);
-				const int nl = (n + 1) >> 1;
-				if (k < nl) {
-					T w[2 * K + 1];
-					if (!INV) {
-						constexpr int F = K & 1;
-						const int g0 = 2 * k - K + F;
-						const T *const in = cur + s0;
-						if (g0 >= 0 && g0 + 2 * K < n) {
-#pragma unroll
-							for (int j = 0; j <= 2 * K; j++)
-								w[j] = in[g0 + j];
-						} else if (n > 2 * K + 1) {
-#pragma unroll
-							for (int j = 0; j <= 2 * K; j++)
-								w[j] = in[reflect1(g0 + j, n)];
-						} else {
-#pragma unroll
-							for (int j = 0; j <= 2 * K; j++)
-								w[j] = in[reflect(g0 + j, n)];
-						}
-						lift_fwd_regs<W, 2 * K + 1>(w, W::kEndForms ? node_end_mask<2 * K + 1>(g0, n) : 0u);
-						nxt[s0 + k] = W::fwd_scale(0, w[K - F]);
-						if (2 * k + 1 < n)
-							nxt[s0 + nl + k] = W::fwd_scale(1, w[K + 1 - F]);
-					} else {
-						const int g0 = 2 * k - K + 1;
-						const T *const L = cur + s0, *const H = L + nl;
-						const bool inner = g0 >= 0 && g0 + 2 * K < n;
-#pragma unroll
-						for (int j = 0; j <= 2 * K; j++) {
-							const int i = inner ? g0 + j : n > 2 * K + 1 ? reflect1(g0 + j, n) : reflect(g0 + j, n);
-							w[j] = W::inv_scale(i & 1, (i & 1) ? H[i >> 1] : L[i >> 1]);
-						}
-						lift_inv_regs<W, 2 * K + 1>(w, W::kEndForms ? node_end_mask<2 * K + 1>(g0, n) : 0u);
-						nxt[s0 + 2 * k] = w[K - 1];
-						if (2 * k + 1 < n)
-							nxt[s0 + 2 * k + 1] = w[K];
-					}
-				}
-				q += dq;
-				k += dk;
-				if (k >= P) {
-					k -= P;
-					q++;
-				}
-			}
-		}
+		if (active)
+			wp_level<W, INV, false>(cur, nxt, N, lev, t, tpl, uniform, nullptr);
 		T *const x = cur;
 		cur = nxt;
 		nxt = x;
@@ -120,16 +55,7 @@ __global__ __launch_bounds__(256) void k_wp_lines(const char *__restrict__ src, 
 	if (!active)
 		return;
 	// the whole line, once
-	if (vec) {
-		const int n4 = N >> 2;
-		for (int i = t; i < n4; i += tpl)
-			*(float4 *)(d + 16l * i) = *(const float4 *)(cur + 4 * i);
-		for (int i = 4 * n4 + t; i < N; i += tpl)
-			*(T *)(d + 4l * i) = cur[i];
-	} else {
-		for (int i = t; i < N; i += tpl)
-			*(T *)(d + (long)i * elem_stride) = cur[i];
-	}
+	wp_line_out(d, cur, N, elem_stride, t, tpl, vec);
 }
 
 template <class W>

@@ -3,6 +3,8 @@ every level, not only the L node.  A submodule of its own: import it as ``from l
 
     packets.wp1d_batch(dwt.CDF97_S, False, x, x, 4 * N, 4, n_lines, N, levels)   # in place, leaves in natural order
     packets.wp_features1d_batch("wps", x, 4 * N, 4, n_lines, N, levels, packets.FREQUENCY, fv, 1 << levels)
+    tree = packets.wp_joint_basis(dwt.CDF97_S, packets.COST_SHANNON, 0.0, x, 4 * N, 4, n_lines, N, levels)   # one tree for all rows
+    packets.wp_tree1d_batch(dwt.CDF97_S, False, x, x, 4 * N, 4, n_lines, N, levels, tree, 0)             # 
 
 Pointers are numpy arrays, torch tensors or integer addresses, host or device memory, as everywhere in libdwt_amd.
 """
@@ -17,6 +19,8 @@ WAVELETS = (CDF97_S, CDF53_S, INTERP53_S)
 NATURAL, FREQUENCY = 0, 1  # node order of the feature entries
 MAX_LEVELS_2D = 8
 MAX_FEATURE_NODES = 96  # FEAT_MAX_BANDS: level <= 6 in 1-D, <= 3 in 2-D
+TREE_MAX_LEVELS, TREE_WORDS = 10, 32  # DWT_HIP_WP_TREE_MAX_LEVELS, DWT_HIP_WP_TREE_WORDS
+COST_SHANNON, COST_LOG_ENERGY, COST_LP, COST_THRESHOLD = 0, 1, 2, 3  # enum dwt_hip_wp_cost
 
 lib.dwt_hip_wp_nodes.argtypes = [_I, _I, _IP, _IP]
 lib.dwt_hip_wp_nodes.restype = _I
@@ -30,6 +34,14 @@ lib.dwt_hip_wp_features1d_batch.argtypes = [C.c_uint, _P, _S, _S, _I, _I, _I, _I
 lib.dwt_hip_wp_features1d_batch.restype = _I
 lib.dwt_hip_wp_features2d_batch.argtypes = [C.c_uint, _P, _S, _I, _I, _I, _I, _I, _I, _F, _P, _S]
 lib.dwt_hip_wp_features2d_batch.restype = _I
+lib.dwt_hip_wp_best_tree.argtypes = [_I, C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.POINTER(C.c_double)]
+lib.dwt_hip_wp_best_tree.restype = _I
+lib.dwt_hip_wp_tree_leaves.argtypes = [_I, _I, C.POINTER(C.c_uint32), _IP, _IP, _IP, _IP]
+lib.dwt_hip_wp_tree_leaves.restype = _I
+lib.dwt_hip_wp_best1d_batch.argtypes = [_I, _I, _F, _P, _P, _S, _S, _I, _I, _I, _P, _S, _P, _P, _S]
+lib.dwt_hip_wp_best1d_batch.restype = _I
+lib.dwt_hip_wp_tree1d_batch.argtypes = [_I, _I, _P, _P, _S, _S, _I, _I, _I, _P, _S]
+lib.dwt_hip_wp_tree1d_batch.restype = _I
 
 
 def wp_nodes(size, level):
@@ -77,3 +89,94 @@ def wp_features2d_batch(features, ptr, batch_stride, batch, stride_x, size_x, si
     """dwt_hip_wp_features2d_batch: the same for images; node (ky, kx) at ky * 2^level + kx of a feature's block."""
     _check(lib.dwt_hip_wp_features2d_batch(feature_mask(features), _addr(ptr), batch_stride, batch, stride_x, size_x, size_y,
                                            level, order, float(p), _addr(fv), fv_stride), "dwt_hip_wp_features2d_batch")
+
+
+def _opt(p):
+    return None if p is None else _addr(p)
+
+
+def wp_best_tree(levels, cost):
+    """dwt_hip_wp_best_tree: (tree, total) of a table of 2^(levels+1) node costs in heap order ([0] unused); the tree is a
+    list of TREE_WORDS words holding effective bits only.  A tie and a NaN keep the parent.  Host only."""
+    cost = [float(c) for c in cost]
+    if not 1 <= levels <= TREE_MAX_LEVELS or len(cost) < (2 << levels):
+        raise DwtError("wp_best_tree: %d levels, a table of %d costs" % (levels, len(cost)))
+    table, tree, total = (C.c_double * len(cost))(*cost), (C.c_uint32 * TREE_WORDS)(), C.c_double()
+    if lib.dwt_hip_wp_best_tree(levels, table, tree, C.byref(total)) != 0:
+        raise DwtError("wp_best_tree: bad arguments")
+    return list(tree), total.value
+
+
+def wp_tree_leaves(size, levels, tree):
+    """dwt_hip_wp_tree_leaves: [(level, index, start, len)] of the leaves of the effective tree, left to right.  Host only."""
+    tree = [int(t) for t in tree]
+    if len(tree) != TREE_WORDS:
+        raise DwtError("wp_tree_leaves: a tree has %d words" % TREE_WORDS)
+    words = (C.c_uint32 * TREE_WORDS)(*tree)
+    n = lib.dwt_hip_wp_tree_leaves(size, levels, words, None, None, None, None)
+    if n < 0:
+        raise DwtError("wp_tree_leaves: %d levels over a line of %d samples" % (levels, size))
+    out = [(_I * n)() for _ in range(4)]
+    lib.dwt_hip_wp_tree_leaves(size, levels, words, *out)
+    return list(zip(*(list(o) for o in out)))
+
+
+def wp_best1d_batch(wavelet, cost, param, src, dst, line_stride, elem_stride, n_lines, size, levels, tree=None,
+                    tree_stride=4 * TREE_WORDS, total=None, node_cost=None, cost_stride=None):
+    """dwt_hip_wp_best1d_batch: the cost of every node, the best tree of every row and (dst not None) the row in that tree.
+    Every output is optional and lies where src lies; strides in bytes (cost_stride None: dense tables).  Device rows of up
+    to 8192 samples take one launch; nothing is read back."""
+    if cost_stride is None:
+        cost_stride = 8 * (2 << levels) if 0 <= levels <= 30 else 0
+    _check(lib.dwt_hip_wp_best1d_batch(wavelet, cost, float(param), _addr(src), _opt(dst), line_stride, elem_stride, n_lines, size,
+                                       levels, _opt(tree), tree_stride, _opt(total), _opt(node_cost), cost_stride),
+           "dwt_hip_wp_best1d_batch")
+
+
+def wp_tree1d_batch(wavelet, inverse, src, dst, line_stride, elem_stride, n_lines, size, levels, tree, tree_stride=0):
+    """dwt_hip_wp_tree1d_batch: the rows in given trees, forward or inverse; tree_stride 0 is one tree for every row.  The
+    trees lie where src lies -- except that a list of TREE_WORDS ints (what wp_best_tree returns) is taken for rows in
+    either memory space: for device rows it is copied to device memory for the length of the call."""
+    tmp = None
+    if isinstance(tree, (list, tuple)):
+        words = (C.c_uint32 * TREE_WORDS)(*[int(t) for t in tree])
+        tree, tree_stride = C.addressof(words), 0
+        if lib.dwt_hip_is_device_pointer(_addr(src)):
+            tmp = lib.dwt_hip_malloc(4 * TREE_WORDS)
+            if not tmp or lib.dwt_hip_memcpy_h2d(tmp, tree, 4 * TREE_WORDS) != 0:
+                raise DwtError("wp_tree1d_batch: no device memory for the tree")
+            tree = tmp
+    try:
+        _check(lib.dwt_hip_wp_tree1d_batch(wavelet, 1 if inverse else 0, _addr(src), _addr(dst), line_stride, elem_stride, n_lines,
+                                           size, levels, _addr(tree), tree_stride), "dwt_hip_wp_tree1d_batch")
+    finally:
+        if tmp:
+            lib.dwt_hip_sync()
+            lib.dwt_hip_free(tmp)
+
+
+def wp_joint_basis(wavelet, cost, param, src, line_stride, elem_stride, n_lines, size, levels):
+    """One tree for all rows: the search for the cost tables alone, the tables summed over the rows on the host in float64
+    (row order), wp_best_tree of the sum.  Returns the tree (a list of TREE_WORDS words) for wp_tree1d_batch(...,
+    tree_stride=0); src is only read."""
+    import numpy as np
+
+    nt = 2 << levels
+    table = np.zeros((max(n_lines, 0), nt), np.float64)
+    if lib.dwt_hip_is_device_pointer(_addr(src)):
+        dev = lib.dwt_hip_malloc(max(table.nbytes, 16))
+        if not dev:
+            raise DwtError("wp_joint_basis: no device memory for the cost tables")
+        try:
+            wp_best1d_batch(wavelet, cost, param, src, None, line_stride, elem_stride, n_lines, size, levels, node_cost=dev)
+            lib.dwt_hip_sync()
+            if table.nbytes and lib.dwt_hip_memcpy_d2h(table.ctypes.data, dev, table.nbytes) != 0:
+                raise DwtError("wp_joint_basis: the cost tables could not be read")
+        finally:
+            lib.dwt_hip_free(dev)
+    else:
+        wp_best1d_batch(wavelet, cost, param, src, None, line_stride, elem_stride, n_lines, size, levels, node_cost=table)
+    joint = np.zeros(nt, np.float64)
+    for row in table:
+        joint += row
+    return wp_best_tree(levels, joint)[0]
