@@ -559,7 +559,8 @@ int dwt_hip_swt1d_level(int wavelet, const void *src, void *dst_l, void *dst_h, 
  * row, Lr = conv_x(A, low), Hr = conv_x(A, high), and then along y for every column: LL = conv_y(Lr, low), LH =
  * conv_y(Lr, high), HL = conv_y(Hr, low), HH = conv_y(Hr, high); borders replicated, no direction ever skipped (a 1-row
  * image takes its column pass with N = 1), every plane size_x x size_y.  Band names as enum dwt_subbands: HL is high-pass
- * along a row.  Forward only.  stride_x is the row pitch and stride_y the element pitch of src in bytes; images are
+ * along a row.  The inverse is dwt_hip_iswt2d_batch, under the symmetric border of dwt_hip_swt2d_batch_ex (replicated
+ * borders do not reconstruct).  stride_x is the row pitch and stride_y the element pitch of src in bytes; images are
  * batch_stride bytes apart.  Detail band k (HL = 1, LH = 2, HH = 3) of level l of image b goes to
  *     dst_h + b*dst_batch_stride + (3*l + k-1)*plane_stride + y*dst_stride_x + 4*x.
  * l_mode 0: no LL is written (dst_l may be NULL); 1: the last level's LL, to plane 0 of dst_l + b*dst_batch_stride;
@@ -580,6 +581,53 @@ int dwt_hip_swt2d_batch(int wavelet, const void *src, size_t batch_stride, int b
  * apart; level 0 .. DWT_HIP_SWT_MAX_LEVELS-1.  src and the four planes must not overlap. */
 int dwt_hip_swt2d_level(int wavelet, const void *src, int stride_x, int stride_y, int size_x, int size_y, int level, void *dst_ll,
 	void *dst_hl, void *dst_lh, void *dst_hh, int dst_stride_x, int dst_stride_y);
+/* The border rule of the stationary transforms.  REPLICATE is the reference's: x[clamp(i)].  SYMMETRIC is whole-sample
+ * symmetric extension, x[reflect(i)] with reflect(i, N) = 0 for N = 1 and otherwise m = i mod 2(N-1) taken non-negative,
+ * m > N-1 ? 2(N-1) - m : m: an extension, and the rule under which the transform has an inverse -- the
+ * filters are symmetric and of odd length, so every plane of a symmetrically extended input is itself symmetric about
+ * samples 0 and N-1 at every dilation.  Away from the borders (CL * (2^J - 1) samples after J levels) both rules give the
+ * same coefficients. */
+enum dwt_hip_swt_border {
+	DWT_HIP_SWT_BORDER_REPLICATE = 0,
+	DWT_HIP_SWT_BORDER_SYMMETRIC = 1
+};
+/* dwt_hip_swt1d_batch / dwt_hip_swt2d_batch with the border rule as their last argument; border 0 is those entries. */
+int dwt_hip_swt1d_batch_ex(int wavelet, const void *src, size_t line_stride, size_t elem_stride, int n_lines, int N, int levels,
+	void *dst_h, void *dst_l, int l_mode, size_t plane_stride, size_t dst_line_stride, int border);
+int dwt_hip_swt2d_batch_ex(int wavelet, const void *src, size_t batch_stride, int batch, int stride_x, int stride_y, int size_x, int size_y,
+	int levels, void *dst_h, void *dst_l, int l_mode, size_t dst_batch_stride, size_t plane_stride, int dst_stride_x, int border);
+/* The inverse stationary transform of rows (an extension: the reference has none).  `border` must be
+ * DWT_HIP_SWT_BORDER_SYMMETRIC: replicated borders do not reconstruct (an error).  src_h is laid out as dwt_hip_swt1d_batch
+ * writes dst_h -- H of level l of line y at src_h + l*plane_stride + y*src_line_stride, dense -- and src_l holds the last
+ * level's L lines src_line_stride bytes apart (a caller with an l_mode 2 buffer passes the address of its last plane).
+ * Levels run from levels-1 down to 0, level l at dilation u = 1 << l:
+ *     x = 0.5f * (conv(L, sl, u) + conv(H, sh, u)),   sl[i] = (-1)^(i-CH) * gh[i],   sh[i] = (-1)^(i-CL) * gl[i],
+ * every conv the forward's tap sum over reflected indices (float32, each product and sum rounded on its own).  The result
+ * goes to dst, lines dst_line_stride and elements dst_elem_stride bytes apart.  `ops` and `params` are optional host tables
+ * of `levels` entries, one operator (DWT_HIP_BAND_KEEP, _ZERO, _SCALE, _HARD, _SOFT; _COMPRESS is an error) and one
+ * parameter per H plane, both NULL for KEEP everywhere: a detail coefficient passes through its operator as it is read, and
+ * the result is bit for bit that of applying the operator to the stored plane first.  A ZERO plane is never read.
+ * levels = 0 copies src_l to dst.  All pointers are host memory or all device memory; dst must not overlap src_h or src_l;
+ * levels 0 .. DWT_HIP_SWT_MAX_LEVELS; a refused call writes nothing.  Dense device lines of up to 8192 samples take ONE
+ * kernel launch whatever `levels` and n_lines; longer lines, strided dst elements and option "swt_fused" = 0 one per level.
+ * A forward transform under the symmetric border followed by this call returns the input within 1e-6 * max|x| for normal
+ * inputs (the filters' 8-digit literals and float32 rounding; it is no bit-exact pair). */
+int dwt_hip_iswt1d_batch(int wavelet, int border, const void *src_h, const void *src_l, size_t plane_stride, size_t src_line_stride,
+	int n_lines, int N, int levels, const int *ops, const float *params, void *dst, size_t dst_line_stride, size_t dst_elem_stride);
+/* The inverse stationary transform of image batches: columns first, then rows (the forward order reversed),
+ *     Lr = 0.5f*(conv_y(LL, sl) + conv_y(LH, sh))   Hr = 0.5f*(conv_y(HL, sl) + conv_y(HH, sh))   A = 0.5f*(conv_x(Lr, sl) + conv_x(Hr, sh)).
+ * The detail planes are laid out as dwt_hip_swt2d_batch writes them -- band k of level l of image b at
+ * src_h + b*src_batch_stride + (3*l + k-1)*plane_stride + y*src_stride_x + 4*x -- and src_l is the last level's LL of
+ * every image, at src_l + b*src_batch_stride + y*src_stride_x + 4*x.  The result goes to dst + b*dst_batch_stride +
+ * y*dst_stride_x + x*dst_stride_y.  `ops` / `params`: as above with 3 * levels entries, the plane's at index 3*l + k-1.  The
+ * intermediate LL planes live in library scratch.  Dense device destinations take ONE kernel launch per level for the whole
+ * batch on levels 0 .. DWT_HIP_ISWT2D_FUSED_LEVELS-1; deeper levels, strided dst elements and option "swt2d_fused" = 0 take
+ * two (a column pass and a row pass through library scratch).  Otherwise the rules of the row entry.  Round trip of normal
+ * inputs: within 2e-6 * max|x|. */
+#define DWT_HIP_ISWT2D_FUSED_LEVELS 5
+int dwt_hip_iswt2d_batch(int wavelet, int border, const void *src_h, const void *src_l, size_t src_batch_stride, size_t plane_stride,
+	int src_stride_x, int batch, int size_x, int size_y, int levels, const int *ops, const float *params, void *dst,
+	size_t dst_batch_stride, int dst_stride_x, int dst_stride_y);
 /* The feature statistics of the transform's planes without the planes: feature k of the mask (enum order) of level l of
  * line y at fv[y*fv_line_stride + k*levels + l] (floats).  band 0: the H planes, 1: the L planes.  Each value is what
  * dwt_util_band_<name>_s(plane, 0, sizeof(float), N, 1[, p]) gives for that plane, wps with j = l.  fv lies where src

@@ -263,7 +263,7 @@ int host_inverse_pipelined(const Call2d &c, const void *src, void *dst, int stri
 // dst_h + l*plane_stride + y*dls with elements h_es bytes apart, L by l_mode; level l at dilation 1 << (level0 + l)
 bool swt_fused_ok(const void *src, long ls, long es, int N);
 int swt_device(Wavelet w, const char *src, long ls, long es, int n_lines, int N, int level0, int levels, char *dst_h, long h_es,
-	char *dst_l, long l_es, int l_mode, long plane_stride, long dls);
+	char *dst_l, long l_es, int l_mode, long plane_stride, long dls, int border = kSwtReplicate);
 // the warning counters of dwt_hip_rows_warnings lie in cond_ws: forgotten when the scratch is overwritten (dwt_backend_condition.hip)
 void cond_forget_warnings();
 // the median magnitude of one band of every frame of a batch, the frames only read (dwt_backend_features.hip) -> med (host)

@@ -19,7 +19,7 @@ bool swt_fused_ok(const void *src, long ls, long es, int N)
 // Device memory on every side.  H of level l of line y at dst_h + l*plane_stride + y*dls, elements h_es bytes apart; L
 // likewise by l_mode.  Level l has dilation 1 << (level0 + l).  dst_h may be null where the level passes run (no H stored).
 int swt_device(Wavelet w, const char *src, long ls, long es, int n_lines, int N, int level0, int levels, char *dst_h, long h_es,
-	char *dst_l, long l_es, int l_mode, long plane_stride, long dls)
+	char *dst_l, long l_es, int l_mode, long plane_stride, long dls, int border)
 {
 	if (n_lines <= 0 || levels <= 0 || N <= 0)
 		return 0;
@@ -39,6 +39,7 @@ int swt_device(Wavelet w, const char *src, long ls, long es, int n_lines, int N,
 		a.plane_stride = plane_stride;
 		a.dst_line_stride = dls;
 		a.l_mode = l_mode;
+		a.border = border;
 		return launched(launch_swt_lines(w, false, a, g.stream), "SWT", "line");
 	}
 	// level by level: the L chain through two dense scratch images
@@ -68,6 +69,7 @@ int swt_device(Wavelet w, const char *src, long ls, long es, int n_lines, int N,
 		a.out_h = dst_h ? dst_h + (long)l * plane_stride : nullptr; // (null: the level passes of an L-only caller)
 		a.h_ls = dls;
 		a.h_es = h_es;
+		a.border = border;
 		if (launched(launch_swt_level(w, a, g.stream), "SWT", "level"))
 			return 1;
 	}
@@ -76,11 +78,13 @@ int swt_device(Wavelet w, const char *src, long ls, long es, int n_lines, int N,
 
 // Host or device memory (all sides alike); the checks of the C-ABI entries.
 int swt1d(int wavelet, const void *src, long ls, long es, int n_lines, int N, int level0, int levels, void *dst_h, long h_es, void *dst_l,
-	long l_es, int l_mode, long plane_stride, long dls)
+	long l_es, int l_mode, long plane_stride, long dls, int border)
 {
 	Wavelet w;
 	if (!wavelet_of(wavelet, &w) || (w != kCdf97S && w != kCdf53S))
 		return fail("the SWT takes DWT_HIP_CDF97_S or DWT_HIP_CDF53_S (got wavelet %d)", wavelet);
+	if (border != DWT_HIP_SWT_BORDER_REPLICATE && border != DWT_HIP_SWT_BORDER_SYMMETRIC)
+		return fail("SWT: border %d (0: replicated, 1: symmetric)", border);
 	if (n_lines < 0 || N < 0 || levels < 0 || level0 < 0 || level0 + (long)levels > SWT_MAX_LEVELS)
 		return fail("SWT: bad arguments (%d lines of %d samples, levels %d .. %ld; at most %d levels)", n_lines, N, level0,
 			level0 + (long)levels, SWT_MAX_LEVELS);
@@ -110,7 +114,7 @@ int swt1d(int wavelet, const void *src, long ls, long es, int n_lines, int N, in
 		return fail("src, dst_h and dst_l must all be host or all be device pointers");
 	if (dev)
 		return swt_device(w, (const char *)src, ls, es, n_lines, N, level0, levels, (char *)dst_h, h_es, (char *)dst_l, l_es, l_mode,
-			plane_stride, dls);
+			plane_stride, dls, border);
 
 	// host memory: a dense device image of the lines, dense device planes, each plane spread back
 	const Frame fs{(void *)src, ls, es, 4, N, n_lines, false}, fh{dst_h, dls, h_es, 4, N, n_lines, false}, fl{dst_l, dls, l_es, 4, N, n_lines, false};
@@ -122,7 +126,7 @@ int swt1d(int wavelet, const void *src, long ls, long es, int n_lines, int N, in
 	if (grow(g.frame_b, (size_t)plane * (levels + l_planes)) || frame_stage(fs, g.frame_a, &A))
 		return 1;
 	char *dh = (char *)g.frame_b.p, *dl = dh + (size_t)plane * levels;
-	if (swt_device(w, A.p, pitch, 4, n_lines, N, level0, levels, dh, 4, dl, 4, l_mode, plane, pitch))
+	if (swt_device(w, A.p, pitch, 4, n_lines, N, level0, levels, dh, 4, dl, 4, l_mode, plane, pitch, border))
 		return 1;
 	return frame_unpack_stack(fh, levels, plane_stride, dh, pitch) || frame_unpack_stack(fl, l_planes, plane_stride, dl, pitch);
 }
@@ -134,13 +138,20 @@ using namespace dwtb;
 #pragma GCC visibility push(default)
 extern "C" {
 
-int dwt_hip_swt1d_batch(int wavelet, const void *src, size_t line_stride, size_t elem_stride, int n_lines, int N, int levels, void *dst_h,
-	void *dst_l, int l_mode, size_t plane_stride, size_t dst_line_stride)
+int dwt_hip_swt1d_batch_ex(int wavelet, const void *src, size_t line_stride, size_t elem_stride, int n_lines, int N, int levels, void *dst_h,
+	void *dst_l, int l_mode, size_t plane_stride, size_t dst_line_stride, int border)
 {
 	if (line_stride > (size_t)LONG_MAX / 2 || elem_stride > INT_MAX || plane_stride > (size_t)LONG_MAX / 64 || dst_line_stride > (size_t)LONG_MAX / 2)
 		return fail("SWT: bad strides");
 	return swt1d(wavelet, src, (long)line_stride, (long)elem_stride, n_lines, N, 0, levels, dst_h, 4, dst_l, 4, l_mode, (long)plane_stride,
-		(long)dst_line_stride);
+		(long)dst_line_stride, border);
+}
+
+int dwt_hip_swt1d_batch(int wavelet, const void *src, size_t line_stride, size_t elem_stride, int n_lines, int N, int levels, void *dst_h,
+	void *dst_l, int l_mode, size_t plane_stride, size_t dst_line_stride)
+{
+	return dwt_hip_swt1d_batch_ex(wavelet, src, line_stride, elem_stride, n_lines, N, levels, dst_h, dst_l, l_mode, plane_stride, dst_line_stride,
+		DWT_HIP_SWT_BORDER_REPLICATE);
 }
 
 int dwt_hip_swt1d_level(int wavelet, const void *src, void *dst_l, void *dst_h, int N, int stride, int level)
@@ -150,7 +161,7 @@ int dwt_hip_swt1d_level(int wavelet, const void *src, void *dst_l, void *dst_h, 
 	if (N < 0 || level < 0 || level >= SWT_MAX_LEVELS)
 		return fail("SWT: bad arguments (%d samples, level %d; levels 0 .. %d)", N, level, SWT_MAX_LEVELS - 1);
 	const long line = (long)N * stride;
-	return swt1d(wavelet, src, line, stride, 1, N, level, 1, dst_h, stride, dst_l, stride, 1, line, line);
+	return swt1d(wavelet, src, line, stride, 1, N, level, 1, dst_h, stride, dst_l, stride, 1, line, line, DWT_HIP_SWT_BORDER_REPLICATE);
 }
 
 } // extern "C"

@@ -28,7 +28,7 @@ int swt2d_level_device(Wavelet w, Swt2dLevelArgs a, char *passes)
 // Every level of a batch in device memory.  Detail band k of level l of image b at dst_h + b*h_bs + (3*l + k-1)*ps, rows
 // dsx bytes apart, dense; LL by l_mode at dst_l + b*l_bs (+ l*ps).  Source elements sy bytes apart.
 int swt2d_device(Wavelet w, const char *src, long sbs, long sx, long sy, int batch, int W, int H, int levels, char *dst_h, long h_bs,
-	char *dst_l, long l_bs, int l_mode, long ps, long dsx)
+	char *dst_l, long l_bs, int l_mode, long ps, long dsx, int border)
 {
 	if (check_dev_align({src, dst_h, l_mode ? dst_l : nullptr}, {sbs, sx, sy, h_bs, l_mode ? l_bs : 0, ps, dsx}))
 		return 1;
@@ -73,6 +73,7 @@ int swt2d_device(Wavelet w, const char *src, long sbs, long sx, long sy, int bat
 		a.d_bs = h_bs;
 		a.d_sx = dsx;
 		a.d_sy = 4;
+		a.border = border;
 		if (swt2d_level_device(w, a, pass_ws))
 			return 1;
 	}
@@ -90,11 +91,13 @@ int swt2d_wavelet(int wavelet, Wavelet *w)
 size_t frame_extent(long sx, long sy, int w, int h) { return (size_t)((h - 1l) * sx + (w - 1l) * sy + 4); }
 
 int swt2d_batch(int wavelet, const void *src, long sbs, int batch, long sx, long sy, int W, int H, int levels, void *dst_h, void *dst_l,
-	int l_mode, long dbs, long ps, long dsx)
+	int l_mode, long dbs, long ps, long dsx, int border)
 {
 	Wavelet w;
 	if (swt2d_wavelet(wavelet, &w))
 		return 1;
+	if (border != DWT_HIP_SWT_BORDER_REPLICATE && border != DWT_HIP_SWT_BORDER_SYMMETRIC)
+		return fail("SWT 2-D: border %d (0: replicated, 1: symmetric)", border);
 	if (batch < 1 || W < 1 || H < 1 || levels < 0 || levels > SWT_MAX_LEVELS)
 		return fail("SWT 2-D: bad arguments (%d images of %d x %d, %d levels; at least one image and sample, at most %d levels)", batch, W, H,
 			levels, SWT_MAX_LEVELS);
@@ -130,7 +133,7 @@ int swt2d_batch(int wavelet, const void *src, long sbs, int batch, long sx, long
 	if (dev != (bool)dwt_hip_is_device_pointer(dst_h) || (l_mode && dev != (bool)dwt_hip_is_device_pointer(dst_l)))
 		return fail("src, dst_h and dst_l must all be host or all be device pointers");
 	if (dev)
-		return swt2d_device(w, (const char *)src, sbs, sx, sy, batch, W, H, levels, (char *)dst_h, dbs, (char *)dst_l, dbs, l_mode, ps, dsx);
+		return swt2d_device(w, (const char *)src, sbs, sx, sy, batch, W, H, levels, (char *)dst_h, dbs, (char *)dst_l, dbs, l_mode, ps, dsx, border);
 
 	// host memory: dense device images of the batch, dense device planes, each plane spread back
 	const Frame fs{(void *)src, sx, sy, 4, W, H, false}, fh{dst_h, dsx, 4, 4, W, H, false}, fl{dst_l, dsx, 4, 4, W, H, false};
@@ -142,7 +145,7 @@ int swt2d_batch(int wavelet, const void *src, long sbs, int batch, long sx, long
 	char *const ds = (char *)g.frame_a.p, *const dh = (char *)g.frame_b.p, *const dl = dh + (size_t)dplane * batch * 3 * levels;
 	if (frame_pack_stack(fs, batch, sbs, ds, pitch))
 		return 1;
-	if (swt2d_device(w, ds, dplane, pitch, 4, batch, W, H, levels, dh, dplane * 3 * levels, dl, dplane * l_planes, l_mode, dplane, pitch))
+	if (swt2d_device(w, ds, dplane, pitch, 4, batch, W, H, levels, dh, dplane * 3 * levels, dl, dplane * l_planes, l_mode, dplane, pitch, border))
 		return 1;
 	for (int b = 0; b < batch; b++) {
 		Frame h = fh, l = fl;
@@ -228,14 +231,21 @@ using namespace dwtb;
 #pragma GCC visibility push(default)
 extern "C" {
 
-int dwt_hip_swt2d_batch(int wavelet, const void *src, size_t batch_stride, int batch, int stride_x, int stride_y, int size_x, int size_y,
-	int levels, void *dst_h, void *dst_l, int l_mode, size_t dst_batch_stride, size_t plane_stride, int dst_stride_x)
+int dwt_hip_swt2d_batch_ex(int wavelet, const void *src, size_t batch_stride, int batch, int stride_x, int stride_y, int size_x, int size_y,
+	int levels, void *dst_h, void *dst_l, int l_mode, size_t dst_batch_stride, size_t plane_stride, int dst_stride_x, int border)
 {
 	if (batch_stride > (size_t)LONG_MAX / 2 || dst_batch_stride > (size_t)LONG_MAX / 2 || plane_stride > (size_t)LONG_MAX / 128 || stride_x < 0 ||
 		stride_y < 0 || dst_stride_x < 0)
 		return fail("SWT 2-D: bad strides");
 	return swt2d_batch(wavelet, src, (long)batch_stride, batch, stride_x, stride_y, size_x, size_y, levels, dst_h, dst_l, l_mode,
-		(long)dst_batch_stride, (long)plane_stride, dst_stride_x);
+		(long)dst_batch_stride, (long)plane_stride, dst_stride_x, border);
+}
+
+int dwt_hip_swt2d_batch(int wavelet, const void *src, size_t batch_stride, int batch, int stride_x, int stride_y, int size_x, int size_y,
+	int levels, void *dst_h, void *dst_l, int l_mode, size_t dst_batch_stride, size_t plane_stride, int dst_stride_x)
+{
+	return dwt_hip_swt2d_batch_ex(wavelet, src, batch_stride, batch, stride_x, stride_y, size_x, size_y, levels, dst_h, dst_l, l_mode,
+		dst_batch_stride, plane_stride, dst_stride_x, DWT_HIP_SWT_BORDER_REPLICATE);
 }
 
 int dwt_hip_swt2d_level(int wavelet, const void *src, int stride_x, int stride_y, int size_x, int size_y, int level, void *dst_ll, void *dst_hl,

@@ -27,29 +27,7 @@ namespace {
 
 typedef float f4 __attribute__((ext_vector_type(4)));
 
-template <int OP>
-static __device__ __forceinline__ float band_op(float c, float a)
-{
-	if constexpr (OP == kBandZero)
-		return 0.f;
-	if (c != c)
-		return c;
-	if constexpr (OP == kBandScale)
-		return c * a;
-	if constexpr (OP == kBandHard)
-		return fabsf(c) > a ? c : 0.f;
-	if constexpr (OP == kBandSoft)
-		return c > a ? c - a : (c < -a ? c + a : 0.f);
-	if constexpr (OP == kBandCompress) { // hdr.c:101-104: the sign of +0 is -1 there too
-		const float s = c > 0.f ? 1.f : -1.f;
-		return s * (float)pow((double)fabsf(c), (double)a);
-	}
-	if constexpr (OP == kMapLog)
-		return (float)log((double)(c + a));
-	if constexpr (OP == kMapExp)
-		return (float)exp((double)c) - a;
-	return c;
-}
+#include "dwt_band_op.h"
 
 // `rows` rows of `w` elements from `p` on, `pitch` bytes apart: a power of two of lanes along a row, the others on
 // further rows

@@ -631,6 +631,7 @@ hipError_t launch_info_init(int *info, int n_lines, hipStream_t s);
 // The stationary (undecimated) wavelet transform of rows (dwt_swt1d.hip): level l filters the previous
 // level's low-pass plane with both filters dilated by 1 << (level0 + l), borders replicated; every plane has N samples.
 constexpr int SWT_MAX_LEVELS = 24; // level0 + levels <= 24: (half a filter) << level stays far inside int
+enum SwtBorder { kSwtReplicate = 0, kSwtSymmetric = 1 }; // DWT_HIP_SWT_BORDER_*: clamp (the reference's), whole-sample reflection (invertible)
 struct SwtLineArgs {
 	const char *src;  // dense lines of N <= N1D_MAX floats
 	long line_stride; // bytes
@@ -646,6 +647,7 @@ struct SwtLineArgs {
 	int band; // 0: the H planes, 1: the L planes
 	int work, pmode;
 	float p;
+	int border; // SwtBorder (coefficient mode; feature mode is replicate only)
 };
 // every level of every line in ONE launch, the L chain in LDS
 hipError_t launch_swt_lines(Wavelet w, bool features, const SwtLineArgs &a, hipStream_t s);
@@ -657,6 +659,7 @@ struct SwtLevelArgs {
 	int n_lines, N, level;
 	char *out_l, *out_l2, *out_h;
 	long l_ls, l_es, l2_ls, l2_es, h_ls, h_es;
+	int border; // SwtBorder
 };
 hipError_t launch_swt_level(Wavelet w, const SwtLevelArgs &a, hipStream_t s);
 
@@ -673,11 +676,54 @@ struct Swt2dLevelArgs {
 	long d_bs, d_sx;         // HL, LH, HH
 	long d_sy;               // the element stride of all four outputs
 	char *lr, *hr;           // the two passes: dense scratch planes, pitch 4*W, image b at + b*H*4*W
+	int border;              // SwtBorder
 };
 bool swt2d_fused_fits(const Swt2dLevelArgs &a); // dense elements, level below SWT2D_FUSED_LEVELS, a grid the launch can take
 hipError_t launch_swt2d_fused(Wavelet w, const Swt2dLevelArgs &a, hipStream_t s); // one launch: src read once, four planes written once
 hipError_t launch_swt2d_rows(Wavelet w, const Swt2dLevelArgs &a, hipStream_t s);  // src -> lr, hr; one thread per sample, any strides
 hipError_t launch_swt2d_cols(Wavelet w, const Swt2dLevelArgs &a, hipStream_t s);  // lr, hr -> ll, hl, lh, hh
+
+// The inverse stationary transforms under the symmetric border (dwt_iswt1d.hip, dwt_iswt2d.hip).  A detail
+// coefficient passes through its plane's operator (BandOp: KEEP, ZERO, SCALE, HARD, SOFT) as it is read.
+struct IswtLineArgs {
+	const char *src_h, *src_l; // H of level l of line y at src_h + l*plane_stride + y*src_line_stride; the last level's L at src_l + y*src_line_stride
+	long plane_stride, src_line_stride;
+	int n_lines, N, levels, vec; // dense lines of N <= N1D_MAX floats; vec: 16-byte loads of every source line are aligned
+	int op[SWT_MAX_LEVELS];      // per level
+	float param[SWT_MAX_LEVELS];
+	char *dst; // dense lines
+	long dst_line_stride;
+};
+// every level of every line in ONE launch, the L chain in LDS
+hipError_t launch_iswt_lines(Wavelet w, const IswtLineArgs &a, hipStream_t s);
+// one level through global memory, one thread per output sample: dense source lines, dst elements d_es bytes apart
+struct IswtLevelArgs {
+	const char *src_l, *src_h;
+	long l_ls, h_ls;
+	int n_lines, N, level, op;
+	float param;
+	char *dst;
+	long d_ls, d_es;
+};
+hipError_t launch_iswt_level(Wavelet w, const IswtLevelArgs &a, hipStream_t s);
+// One 2-D level at dilation 1 << level, columns first and then rows (the forward order reversed): Lr from (LL, LH), Hr from
+// (HL, HH) along y, the output from (Lr, Hr) along x.  Every plane is W x H, dense elements.
+constexpr int ISWT2D_TILE_W = 256;     // the fused kernel's tile: output columns ...
+constexpr int ISWT2D_FUSED_LEVELS = 5; // ... and it runs levels 0 .. 4 (dilations 1 .. 16; DESIGN.md s29 on why)
+struct Iswt2dLevelArgs {
+	const char *ll, *hl, *lh, *hh; // element (x, y) of image b at ll + b*ll_bs + y*ll_sx + 4*x; the details by d_bs, d_sx
+	long ll_bs, ll_sx, d_bs, d_sx;
+	int W, H, batch, level;
+	int op[3]; // of HL, LH, HH
+	float param[3];
+	char *dst; // element (x, y) of image b at dst + b*dst_bs + y*dst_sx + x*dst_sy
+	long dst_bs, dst_sx, dst_sy;
+	char *lr, *hr; // the two passes: dense scratch planes, pitch 4*W, image b at + b*H*4*W
+};
+bool iswt2d_fused_fits(const Iswt2dLevelArgs &a); // dense dst elements, level below ISWT2D_FUSED_LEVELS, a grid the launch can take
+hipError_t launch_iswt2d_fused(Wavelet w, const Iswt2dLevelArgs &a, hipStream_t s); // one launch: four planes read once, dst written once
+hipError_t launch_iswt2d_cols(Wavelet w, const Iswt2dLevelArgs &a, hipStream_t s);  // ll, hl, lh, hh -> lr, hr; one thread per sample
+hipError_t launch_iswt2d_rows(Wavelet w, const Iswt2dLevelArgs &a, hipStream_t s);  // lr, hr -> dst, any dst strides
 
 // Time-frequency planes (dwt_timefreq.hip): every line of a batch correlated with a bank of complex kernels,
 //   out(line, bin, t) = sum over the kernel's taps i, ascending, of x[t - center + i] * conj(k[i])   (taps inside [0, N) only),

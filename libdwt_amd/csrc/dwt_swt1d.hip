@@ -7,7 +7,8 @@
 //     y = 0.0f;  for k = -c .. +c:  y = y + x[clamp(p - u*k, 0, N-1)] * g[k + c];   out[p] = y
 //
 // float32, product and sum rounded separately, from +0.0f, taps from the right neighbour to the left one, borders
-// replicated.  Level l+1 filters the low-pass plane of level l.  Every plane has N samples: J levels turn N samples into
+// replicated (the reference's rule, SwtClamp) or, an extension, extended symmetrically (SwtReflect: the rule under which
+// the transform has an inverse, dwt_iswt1d.hip; the border rule is a template parameter of the coefficient kernels).  Level l+1 filters the low-pass plane of level l.  Every plane has N samples: J levels turn N samples into
 // 2*J*N coefficients.
 //
 // k_swt_lines: a line of up to N1D_MAX samples is loaded into LDS once; two LDS buffers hold the L chain, ping-ponged.
@@ -34,7 +35,7 @@ namespace {
 
 #include "dwt_swt_taps.h"
 
-template <class F, bool FEAT, int NT, int CAP>
+template <class F, class B, bool FEAT, int NT, int CAP>
 __global__ __launch_bounds__(256) void k_swt_lines(SwtLineArgs a)
 {
 	constexpr int LPW = 256 / NT;
@@ -65,7 +66,7 @@ __global__ __launch_bounds__(256) void k_swt_lines(SwtLineArgs a)
 			                                                          : nullptr;
 			for (int p = t; p < N; p += NT) {
 				float lo, hi;
-				swt_point<F, int>(x, p, u, N, &lo, &hi);
+				swt_point<F, int, B>(x, p, u, N, &lo, &hi);
 				nxt[p] = lo;
 				if (active) {
 					h_out[p] = hi;
@@ -98,7 +99,7 @@ __global__ __launch_bounds__(256) void k_swt_lines(SwtLineArgs a)
 	}
 }
 
-template <class F>
+template <class F, class B>
 __global__ __launch_bounds__(256) void k_swt_level(SwtLevelArgs a)
 {
 	const long p = (long)blockIdx.x * 256 + threadIdx.x, N = a.N, u = 1l << a.level;
@@ -108,7 +109,7 @@ __global__ __launch_bounds__(256) void k_swt_level(SwtLevelArgs a)
 		const char *s = a.src + y * a.src_ls;
 		const long es = a.src_es;
 		float lo, hi;
-		swt_point<F, long>([&](long i) { return *(const float *)(s + i * es); }, p, u, N, &lo, &hi);
+		swt_point<F, long, B>([&](long i) { return *(const float *)(s + i * es); }, p, u, N, &lo, &hi);
 		if (a.out_l)
 			*(float *)(a.out_l + y * a.l_ls + p * a.l_es) = lo;
 		if (a.out_l2)
@@ -118,17 +119,17 @@ __global__ __launch_bounds__(256) void k_swt_level(SwtLevelArgs a)
 	}
 }
 
-template <class F, bool FEAT>
+template <class F, class B, bool FEAT>
 hipError_t swt_lines_t(const SwtLineArgs &a, hipStream_t s)
 {
 	// threads per line and LDS capacity: as k_feat_lines splits (64 threads up to 1024 samples), which fixes the order
 	// of the feature sums; 32 KiB of LDS per workgroup up to 4096 samples, 64 KiB up to N1D_MAX
 	if (a.N <= 1024)
-		k_swt_lines<F, FEAT, 64, 1024><<<(unsigned)((a.n_lines + 3l) / 4), 256, 0, s>>>(a);
+		k_swt_lines<F, B, FEAT, 64, 1024><<<(unsigned)((a.n_lines + 3l) / 4), 256, 0, s>>>(a);
 	else if (a.N <= 4096)
-		k_swt_lines<F, FEAT, 256, 4096><<<a.n_lines, 256, 0, s>>>(a);
+		k_swt_lines<F, B, FEAT, 256, 4096><<<a.n_lines, 256, 0, s>>>(a);
 	else
-		k_swt_lines<F, FEAT, 256, N1D_MAX><<<a.n_lines, 256, 0, s>>>(a);
+		k_swt_lines<F, B, FEAT, 256, N1D_MAX><<<a.n_lines, 256, 0, s>>>(a);
 	return hipGetLastError();
 }
 
@@ -140,10 +141,14 @@ hipError_t launch_swt_lines(Wavelet w, bool features, const SwtLineArgs &a, hipS
 		return hipSuccess;
 	if (a.N < 1 || a.N > N1D_MAX || a.level0 < 0 || a.level0 + a.levels > SWT_MAX_LEVELS)
 		return hipErrorInvalidValue;
+	if (a.border != kSwtReplicate && (a.border != kSwtSymmetric || features)) // (the feature planes are the reference's: replicated)
+		return hipErrorInvalidValue;
 	if (w == kCdf97S)
-		return features ? swt_lines_t<Swt97, true>(a, s) : swt_lines_t<Swt97, false>(a, s);
+		return features ? swt_lines_t<Swt97, SwtClamp, true>(a, s)
+		                : a.border ? swt_lines_t<Swt97, SwtReflect, false>(a, s) : swt_lines_t<Swt97, SwtClamp, false>(a, s);
 	if (w == kCdf53S)
-		return features ? swt_lines_t<Swt53, true>(a, s) : swt_lines_t<Swt53, false>(a, s);
+		return features ? swt_lines_t<Swt53, SwtClamp, true>(a, s)
+		                : a.border ? swt_lines_t<Swt53, SwtReflect, false>(a, s) : swt_lines_t<Swt53, SwtClamp, false>(a, s);
 	return hipErrorInvalidValue;
 }
 
@@ -151,13 +156,17 @@ hipError_t launch_swt_level(Wavelet w, const SwtLevelArgs &a, hipStream_t s)
 {
 	if (a.n_lines <= 0 || a.N <= 0)
 		return hipSuccess;
-	if (a.level < 0 || a.level >= SWT_MAX_LEVELS)
+	if (a.level < 0 || a.level >= SWT_MAX_LEVELS || (a.border != kSwtReplicate && a.border != kSwtSymmetric))
 		return hipErrorInvalidValue;
 	const dim3 grid((unsigned)((a.N + 255l) / 256), (unsigned)(a.n_lines < 65535 ? a.n_lines : 65535)); // (past the cap: tests/test_hip_grid_limits.py)
-	if (w == kCdf97S)
-		k_swt_level<Swt97><<<grid, 256, 0, s>>>(a);
+	if (w == kCdf97S && a.border)
+		k_swt_level<Swt97, SwtReflect><<<grid, 256, 0, s>>>(a);
+	else if (w == kCdf97S)
+		k_swt_level<Swt97, SwtClamp><<<grid, 256, 0, s>>>(a);
+	else if (w == kCdf53S && a.border)
+		k_swt_level<Swt53, SwtReflect><<<grid, 256, 0, s>>>(a);
 	else if (w == kCdf53S)
-		k_swt_level<Swt53><<<grid, 256, 0, s>>>(a);
+		k_swt_level<Swt53, SwtClamp><<<grid, 256, 0, s>>>(a);
 	else
 		return hipErrorInvalidValue;
 	return hipGetLastError();

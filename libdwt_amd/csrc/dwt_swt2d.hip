@@ -12,9 +12,10 @@
 // k_swt2d_fused: dense device images, dilations 1 .. 16.  A workgroup of 256 lanes owns SWT2D_TILE_W contiguous columns
 // and SWT2D_TILE_H rows of the level's ROW LATTICE r0 + u*i (r0 = residue + u*i0): the vertical filter of those rows
 // reads rows r0 + u*(i - k) only, so TILE_H + 2c input rows serve the tile at ANY dilation (a tile of adjacent rows would
-// need TILE_H + 2cu).  LDS slot j holds row clamp(r0 + u*(j - c), 0, H-1) -- the clamp is monotone, so tap k of output
-// row i finds its (replicated) row in slot i + c - k -- with its c*u columns of halo on both sides, addresses clamped
-// per element; only the raw input is staged.  One barrier.  Then a lane owns one column and marches down the slots: 2c+1
+// need TILE_H + 2cu).  LDS slot j holds row B(r0 + u*(j - c)) with B the border rule (SwtClamp, or SwtReflect for the
+// invertible transform of DESIGN.md s29): tap k of output row i needs row B(r0 + u*i - u*k) = B(r0 + u*((i + c - k) - c)),
+// which is slot i + c - k by the slot rule itself, whatever B is -- with its c*u columns of halo on both sides, addresses
+// mapped by B per element; only the raw input is staged.  One barrier.  Then a lane owns one column and marches down the slots: 2c+1
 // LDS reads (consecutive lanes, consecutive addresses at every dilation) give Lr and Hr of the slot, which enter a
 // register window of 2c+1 pairs (Lr, Hr) indexed at compile time; once the window is full every new slot emits one
 // output row: (LL, HL) is one packed sum under g_low and (LH, HH) one under g_high (v_pk_mul_f32 / v_pk_add_f32), four
@@ -41,7 +42,7 @@ static_assert(TW == 256, "one column per lane of the workgroup");
 static __host__ __device__ inline int lattice_rows(int H, int level) { return (int)((H + (1l << level) - 1) >> level); }
 static __host__ __device__ inline int class_tiles(int H, int level) { return (lattice_rows(H, level) + TH - 1) / TH; }
 
-template <class F>
+template <class F, class B>
 __global__ __launch_bounds__(256, 4) void k_swt2d_fused(Swt2dLevelArgs a)
 {
 	constexpr int C = F::CL, NW = 2 * C + 1;
@@ -57,12 +58,10 @@ __global__ __launch_bounds__(256, 4) void k_swt2d_fused(Swt2dLevelArgs a)
 	const int t = threadIdx.x;
 
 	for (int j = 0; j < n_slots; j++) {
-		long r = (long)r0 + (long)u * (j - C);
-		r = r < 0 ? 0 : r > H - 1 ? H - 1 : r;
+		const long r = B::map((long)r0 + (long)u * (j - C), (long)H);
 		const float *const row = (const float *)(s + r * a.src_sx);
 		for (int m = t; m < pitch; m += 256) {
-			int c = x0 - halo + m;
-			c = c < 0 ? 0 : c > W - 1 ? W - 1 : c;
+			const int c = B::map(x0 - halo + m, W);
 			tile[j * pitch + m] = row[c];
 		}
 	}
@@ -111,7 +110,7 @@ __global__ __launch_bounds__(256, 4) void k_swt2d_fused(Swt2dLevelArgs a)
 }
 
 // the two passes through global memory: thread (x, q) with q = b*H + y over grid.y
-template <class F>
+template <class F, class B>
 __global__ __launch_bounds__(256) void k_swt2d_rows(Swt2dLevelArgs a)
 {
 	const long x = (long)blockIdx.x * 256 + threadIdx.x, W = a.W, H = a.H, u = 1l << a.level;
@@ -122,13 +121,13 @@ __global__ __launch_bounds__(256) void k_swt2d_rows(Swt2dLevelArgs a)
 		const char *const s = a.src + b * a.src_bs + y * a.src_sx;
 		const long es = a.src_sy;
 		float lo, hi;
-		swt_point<F, long>([&](long i) { return *(const float *)(s + i * es); }, x, u, W, &lo, &hi);
+		swt_point<F, long, B>([&](long i) { return *(const float *)(s + i * es); }, x, u, W, &lo, &hi);
 		*(float *)(a.lr + (q * W + x) * 4) = lo;
 		*(float *)(a.hr + (q * W + x) * 4) = hi;
 	}
 }
 
-template <class F>
+template <class F, class B>
 __global__ __launch_bounds__(256) void k_swt2d_cols(Swt2dLevelArgs a)
 {
 	const long x = (long)blockIdx.x * 256 + threadIdx.x, W = a.W, H = a.H, u = 1l << a.level;
@@ -138,8 +137,8 @@ __global__ __launch_bounds__(256) void k_swt2d_cols(Swt2dLevelArgs a)
 		const long b = q / H, y = q % H;
 		const char *const lr = a.lr + (b * H * W + x) * 4, *const hr = a.hr + (b * H * W + x) * 4;
 		float ll, lh, hl, hh;
-		swt_point<F, long>([&](long i) { return *(const float *)(lr + i * W * 4); }, y, u, H, &ll, &lh);
-		swt_point<F, long>([&](long i) { return *(const float *)(hr + i * W * 4); }, y, u, H, &hl, &hh);
+		swt_point<F, long, B>([&](long i) { return *(const float *)(lr + i * W * 4); }, y, u, H, &ll, &lh);
+		swt_point<F, long, B>([&](long i) { return *(const float *)(hr + i * W * 4); }, y, u, H, &hl, &hh);
 		const long off = b * a.d_bs + y * a.d_sx + x * a.d_sy;
 		if (a.ll)
 			*(float *)(a.ll + b * a.ll_bs + y * a.ll_sx + x * a.d_sy) = ll;
@@ -149,23 +148,24 @@ __global__ __launch_bounds__(256) void k_swt2d_cols(Swt2dLevelArgs a)
 	}
 }
 
-static bool pass_args_ok(const Swt2dLevelArgs &a) { return a.level >= 0 && a.level < SWT_MAX_LEVELS && a.lr && a.hr && a.hl && a.lh && a.hh; }
+static bool border_ok(const Swt2dLevelArgs &a) { return a.border == kSwtReplicate || a.border == kSwtSymmetric; }
+static bool pass_args_ok(const Swt2dLevelArgs &a) { return a.level >= 0 && a.level < SWT_MAX_LEVELS && a.lr && a.hr && a.hl && a.lh && a.hh && border_ok(a); }
 static dim3 pass_grid(const Swt2dLevelArgs &a)
 {
 	const long lines = (long)a.H * a.batch;
 	return dim3((unsigned)((a.W + 255l) / 256), (unsigned)(lines < 65535 ? lines : 65535)); // (past the cap: tests/test_hip_grid_limits.py)
 }
 
-template <class F>
+template <class F, class B>
 hipError_t swt2d_fused_t(const Swt2dLevelArgs &a, hipStream_t s)
 {
 	const int rows = std::min(TH, lattice_rows(a.H, a.level)) + 2 * F::CL;
 	const size_t lds = (size_t)rows * (TW + 2 * F::CL * (1 << a.level)) * sizeof(float);
-	if (hipError_t e = allow_lds((const void *)k_swt2d_fused<F>, lds))
+	if (hipError_t e = allow_lds((const void *)k_swt2d_fused<F, B>, lds))
 		return e;
 	const long classes = std::min<long>(1l << a.level, a.H);
 	const dim3 grid((unsigned)((a.W + TW - 1l) / TW), (unsigned)(classes * class_tiles(a.H, a.level)), (unsigned)a.batch);
-	k_swt2d_fused<F><<<grid, 256, lds, s>>>(a);
+	k_swt2d_fused<F, B><<<grid, 256, lds, s>>>(a);
 	return hipGetLastError();
 }
 
@@ -182,12 +182,12 @@ hipError_t launch_swt2d_fused(Wavelet w, const Swt2dLevelArgs &a, hipStream_t s)
 {
 	if (a.batch <= 0 || a.W <= 0 || a.H <= 0)
 		return hipSuccess;
-	if (!swt2d_fused_fits(a) || !a.hl || !a.lh || !a.hh)
+	if (!swt2d_fused_fits(a) || !a.hl || !a.lh || !a.hh || !border_ok(a))
 		return hipErrorInvalidValue;
 	if (w == kCdf97S)
-		return swt2d_fused_t<Swt97>(a, s);
+		return a.border ? swt2d_fused_t<Swt97, SwtReflect>(a, s) : swt2d_fused_t<Swt97, SwtClamp>(a, s);
 	if (w == kCdf53S)
-		return swt2d_fused_t<Swt53>(a, s);
+		return a.border ? swt2d_fused_t<Swt53, SwtReflect>(a, s) : swt2d_fused_t<Swt53, SwtClamp>(a, s);
 	return hipErrorInvalidValue;
 }
 
@@ -197,10 +197,14 @@ hipError_t launch_swt2d_rows(Wavelet w, const Swt2dLevelArgs &a, hipStream_t s)
 		return hipSuccess;
 	if (!pass_args_ok(a))
 		return hipErrorInvalidValue;
-	if (w == kCdf97S)
-		k_swt2d_rows<Swt97><<<pass_grid(a), 256, 0, s>>>(a);
+	if (w == kCdf97S && a.border)
+		k_swt2d_rows<Swt97, SwtReflect><<<pass_grid(a), 256, 0, s>>>(a);
+	else if (w == kCdf97S)
+		k_swt2d_rows<Swt97, SwtClamp><<<pass_grid(a), 256, 0, s>>>(a);
+	else if (w == kCdf53S && a.border)
+		k_swt2d_rows<Swt53, SwtReflect><<<pass_grid(a), 256, 0, s>>>(a);
 	else if (w == kCdf53S)
-		k_swt2d_rows<Swt53><<<pass_grid(a), 256, 0, s>>>(a);
+		k_swt2d_rows<Swt53, SwtClamp><<<pass_grid(a), 256, 0, s>>>(a);
 	else
 		return hipErrorInvalidValue;
 	return hipGetLastError();
@@ -212,10 +216,14 @@ hipError_t launch_swt2d_cols(Wavelet w, const Swt2dLevelArgs &a, hipStream_t s)
 		return hipSuccess;
 	if (!pass_args_ok(a))
 		return hipErrorInvalidValue;
-	if (w == kCdf97S)
-		k_swt2d_cols<Swt97><<<pass_grid(a), 256, 0, s>>>(a);
+	if (w == kCdf97S && a.border)
+		k_swt2d_cols<Swt97, SwtReflect><<<pass_grid(a), 256, 0, s>>>(a);
+	else if (w == kCdf97S)
+		k_swt2d_cols<Swt97, SwtClamp><<<pass_grid(a), 256, 0, s>>>(a);
+	else if (w == kCdf53S && a.border)
+		k_swt2d_cols<Swt53, SwtReflect><<<pass_grid(a), 256, 0, s>>>(a);
 	else if (w == kCdf53S)
-		k_swt2d_cols<Swt53><<<pass_grid(a), 256, 0, s>>>(a);
+		k_swt2d_cols<Swt53, SwtClamp><<<pass_grid(a), 256, 0, s>>>(a);
 	else
 		return hipErrorInvalidValue;
 	return hipGetLastError();
