@@ -971,6 +971,58 @@ int dwt_hip_phase_derivative(const void *angle, void *derivative, int stride_x, 
 int dwt_hip_detect_ridges(int kind, const void *src, void *ridges, int stride_x, int stride_y, int size_x, int size_y, int n_planes,
 	size_t plane_stride, float threshold);
 
+/* ---- Windowed and reduced-resolution inverse 2-D transforms ----
+ * A Mallat pyramid is a random-access format: a window of the reconstruction needs only the coefficients under it plus a
+ * halo of K samples per level, and the frame at 1 / 2^r of its resolution -- LL(r) -- needs only the levels above r.
+ *
+ * Levels: J = ceil(log2(min(size_x, size_y))), cut by j_max when 0 <= j_max < J -- the count of the inverse 2-D drivers.
+ * `discard` is r in 0 .. J.  The window [x0, x0 + w) x [y0, y0 + h) is in the coordinates of LL(r), a band of
+ * Wo(r) x Ho(r) = ceil(size / 2^r) samples, and lies inside it with w, h >= 1.
+ *
+ * dwt_hip_window_regions: the rectangle of every subband that the window depends on, in elements from the frame's
+ * origin, {x, y, size_x, size_y} per slot in the slot order of dwt_hip_band_geometry (3(l-1) + {0, 1, 2} = HL, LH, HH of
+ * level l, slot 3J = LL(J)).  Returns 3J + 1, or -1 for arguments it refuses (a wavelet without a windowed inverse, sizes
+ * below 1, discard outside 0 .. J, a window that is empty or leaves LL(r), a null table).  The slots of the discarded
+ * levels l <= r hold {0, 0, 0, 0}; an empty rectangle has zero sizes.  Plain host arithmetic, no device.
+ * The rule.  One line of N samples, the samples [a, b) wanted, K the wavelet's halo (4 for CDF 9/7, 2 for CDF 5/3 in
+ * float, int32 and int16, 1 for the interpolating 5/3): a line of one sample needs L index 0 and no H; otherwise take the
+ * interleaved indices 2 floor(a / 2) - K + 1 .. 2 floor((b - 1) / 2) + K + 1, fold each into [0, N) by whole-sample
+ * reflection, let lo and hi be the least and the greatest folded index: L needs ceil(lo / 2) .. floor(hi / 2), H needs
+ * floor(lo / 2) .. floor((hi - 1) / 2).  The levels: from X = [x0, x0 + w), Y = [y0, y0 + h), for l = r + 1 .. J,
+ * (Lx, Hx) = need(X, Wo(l-1)), (Ly, Hy) = need(Y, Ho(l-1)); HL(l) is columns Wo(l) + Hx, rows Ly; LH(l) columns Lx, rows
+ * Ho(l) + Hy; HH(l) columns Wo(l) + Hx, rows Ho(l) + Hy; then X = Lx, Y = Ly; LL(J) is X x Y.
+ * The contract: dwt_hip_inverse_window_batch reads no element outside these rectangles -- a caller may upload only them
+ * and leave the rest of the frame unwritten.
+ *
+ * dwt_hip_inverse_window_batch: `batch` dense Mallat frames in device memory, laid out as for dwt_hip_transform2d_batch
+ * (frame b at src + b * batch_stride, rows stride_x bytes apart), only read.  Element (y, x) of destination frame b
+ * (dst + b * dst_batch_stride, rows dst_stride_x bytes apart; y < h, x < w) is bit for bit element (y0 + y, x0 + x) of
+ * dwt_hip_transform2d_batch(wavelet, 1, ...) at J - r levels on the top-left Wo(r) x Ho(r) rectangle of frame b; r == J
+ * copies the window of LL(J).  Only those w x h elements of each destination frame are written; the destination takes any
+ * base, pitch and batch stride that are multiples of the element size.
+ * Wavelets: DWT_HIP_CDF97_S, _CDF53_S, _INTERP53_S, _CDF53_I, _CDF53_I16.  DWT_HIP_CDF97_H, _CDF97_I and the double
+ * wavelets are out of scope: they are refused like any other id.
+ * Routes, option "window_fused": 2 the window kernels wherever there is a level to undo -- one launch per level
+ * l = J .. r + 1 for the whole batch, a workgroup per tile of DWT_HIP_WINDOW_TILE^2 samples of the level's region, the
+ * halo recomputed per tile; 0 the cross-check, the inverse driver out of place into the context's scratch and a rectangle
+ * copy (what a caller without this entry does); 1 (default) the kernels where they were measured to win -- a window of up
+ * to 1 / 16 of LL(r) whose band, over the batch, has 2^26 samples (one 8192 x 8192 frame) or more; DESIGN.md s30 --, else
+ * the cross-check.  Every route gives the same bits.  dwt_hip_window_route returns the route (0 or 2) a call with these
+ * arguments takes under the calling thread's option, -1 for arguments dwt_hip_window_regions refuses or a batch below 1.
+ * Ordered on the context's stream; no synchronisation, no copy between host and device, nothing allocated after the
+ * first call of a shape; no result depends on what the scratch held (dwt_hip_fill_workspace).  A batch beyond
+ * DWT_HIP_WINDOW_GRID_BATCH frames is covered by a loop inside the kernels.
+ * Errors (nonzero, dwt_hip_last_error, nothing launched, nothing written): an unsupported wavelet, what
+ * dwt_hip_window_regions refuses, a batch outside 1 .. 65535, null or host pointers, addresses or strides that are not
+ * multiples of the element size, rows or frames that run into each other, a destination that shares a byte with any
+ * source frame. */
+#define DWT_HIP_WINDOW_TILE 64
+#define DWT_HIP_WINDOW_GRID_BATCH 4096
+int dwt_hip_window_regions(int wavelet, int size_x, int size_y, int j_max, int discard, int x0, int y0, int w, int h, int *xywh);
+int dwt_hip_inverse_window_batch(int wavelet, const void *src, size_t batch_stride, int batch, int stride_x, int size_x, int size_y,
+	int j_max, int discard, int x0, int y0, int w, int h, void *dst, size_t dst_batch_stride, int dst_stride_x);
+int dwt_hip_window_route(int wavelet, int batch, int size_x, int size_y, int j_max, int discard, int x0, int y0, int w, int h);
+
 /* dwt_util_perf_cdf97_2_s's protocol (src/libdwt.c:21444-21476) with the M images
  * resident in HBM: seconds per transform, minimum over N loops. */
 void dwt_hip_perf_cdf97_2_s(int stride_x, int stride_y, int size_o_big_x, int size_o_big_y,

@@ -771,4 +771,30 @@ hipError_t launch_strided_unpack(void *strided, long sx, long sy, const void *de
 hipError_t launch_conv_show(bool is_int, const void *src, void *dst, long pitch, int w, int h, hipStream_t s);
 hipError_t launch_compare(bool is_int, const void *p1, const void *p2, long pitch, int w, int h, unsigned *result, hipStream_t s);
 
+// ---- windows of the inverse 2-D transform (dwt_window2d.hip) ----
+// One reconstruction level over a REGION: the samples [xa, xb) x [ya, yb) of LL(l-1) -- a frame of W x H samples -- from
+// the coefficients under them and a halo of K samples.  The detail bands are read at their Mallat places in the frame
+// (`det`: the frame's origin; H halves from column Wd / row Hd on); the LL band from `ll`, whose element (0, 0) is sample
+// (ll_y0, ll_x0) of LL(l) (the frame itself with a zero origin, or the region a deeper level left in scratch); the result
+// goes to `out`, whose element (0, 0) is sample (ya, xa).  A workgroup owns one tile of 64 x 64 samples of LL(l-1), the
+// tiles starting at multiples of 64 of the level's own coordinates.  Pitches and batch strides in ELEMENTS.
+constexpr int WINDOW_TILE = 64;
+constexpr int WINDOW_GRID_BATCH = 4096; // frames one trip of the kernels' batch loop covers (grid.z)
+struct WindowLevelArgs {
+	const void *ll;
+	long ll_pitch, ll_bs;
+	int ll_x0, ll_y0;
+	const void *det;
+	long det_pitch, det_bs;
+	void *out;
+	long out_pitch, out_bs;
+	int W, H, Wd, Hd;
+	int xa, xb, ya, yb;
+	int batch;
+};
+hipError_t launch_window_level(Wavelet w, const WindowLevelArgs &a, hipStream_t s);
+// the w x h elements of es bytes at src (of every frame of the batch) -> dst; pitches and batch strides in ELEMENTS
+hipError_t launch_window_copy(int es, const void *src, long src_pitch, long src_bs, void *dst, long dst_pitch, long dst_bs, int w, int h,
+	int batch, hipStream_t s);
+
 } // namespace dwt
