@@ -168,6 +168,9 @@ void dwt_hip_alloc_batch_report(int *chunks, int *dst_tried, int *ll_tried, int 
  * levels of 64 x 64 or more: levels 0 and 1 in ONE launch, level 0's LL band never written --
  * 1 = where that pays (launches of 32768 tiles of 512 columns x 64 row pairs and more: 32 images of 8192^2, 128 of 4096^2), 0 = never, 2 = wherever
  * the geometry is legal, for tests; same bits; not with "fma", "cpt" 4, "ring" 8, "nt" 15 or an odd "tile_pairs"),
+ * "fuse01_ring" (the LDS ring rows per wave of that one launch: 16 = one workgroup of four waves per CU, 8 = two of them, two
+ * waves per SIMD; 0 = the launcher's rule -- 8 from 32768 tiles on, else 16 -- or what dwt_hip_tune measured; any other value is
+ * refused; same bits),
  * "ride_copy" (1 = in-place Mallat calls on one image: the copy of level 0's staged subbands rides along with the deeper
  * levels' launches as extra workgroups; 0 = a launch of its own, the cross-check) and "ride_mib" (MiB of it per small level),
  * "host_pipeline" (1 = host-pointer calls on images of 64 MiB and more run band by band under their own

@@ -285,8 +285,9 @@ bool level_fused_ok(const Call2d &c, const Geom &ge, int j)
 // Levels 0 and 1 of a forward transform in ONE launch (launch_fwd01: the level-0 sweep's own 512-column tiles, level 0's LL
 // band never written): float 9/7 without contraction, Mallat layout, out of place (no staging detour, no copy riding along),
 // two levels or more, both fused, W and H multiples of 4 with both levels of 64 x 64 or more, and none of the sweep's
-// geometry set by hand to something the fused kernel is not (it is the 8-column, deep-ring tile).  Option fuse01: 0 never,
-// 2 wherever that holds, 1 (default) where it also pays:
+// geometry set by hand to something the fused kernel is not (its tiles are the 8-column ones of the deep-ring level sweep; the
+// depth of its OWN ring -- 16 rows, or 8 for two workgroups per CU -- is option fuse01_ring, the tuner's choice or the rule
+// above launch_fwd01, never `ring`).  Option fuse01: 0 never, 2 wherever that holds, 1 (default) where it also pays:
 //   - the launch costs about level 0 x 1.05 (level 1's warm-up rows) x 1.03 (its arithmetic, stores and phantom columns)
 //     against level 0 + level 1 = 1.25 x level 0, whatever the width: the tiles are level 0's, so no width is kept out;
 //   - only in launches of 32768 tiles of 512 columns x 64 pairs and more (32 images of 8192^2), the sizes it was measured
@@ -462,8 +463,14 @@ int forward2d(const Call2d &c, Img src, Img dst, const Geom &ge, int *jp, int de
 				a.ll_bstride = a.ll_pitch * ge.Ho(jl + 1);
 			}
 			SweepTuning tune = g.tune;
-			if (es == 4 && tune.tile_pairs <= 0)
-				apply_tile_choice(pair ? tuned_tile_pairs01(w, a) : tuned_tile_pairs(w, a), &tune, false); // (nothing measured: the launcher's own rule)
+			if (pair)
+				g.stat_choice01 = 0;
+			if (es == 4 && tune.tile_pairs <= 0) {
+				const int choice = pair ? tuned_tile_pairs01(w, a) : tuned_tile_pairs(w, a); // (0, nothing measured: the launcher's own rule)
+				apply_tile_choice(choice, &tune, pair ? kTileFwd01 : kTileFwd);
+				if (pair)
+					g.stat_choice01 = choice;
+			}
 			if (ride.on && ride.next < ride.total && es == 4 && sweep_ride_ok(tune, Wo, Ho, batch, false)) {
 				a.ride = &ride.r;
 				a.ride_lo = ride.next;
@@ -629,7 +636,7 @@ int inverse2d(const Call2d &c, Img src, Img dst, const Geom &ge, int j_max, int 
 			if (tune.inv_pairs <= 0)
 				tune.inv_pairs = src.p == dst.p ? 32 : 16; // (in place: 32 pairs, 230.7 against 234.0 us; scripts/r06/inv_call_ab.py)
 			if (es == 4 && tune.tile_pairs <= 0)
-				apply_tile_choice(tuned_tile_pairs(w, a), &tune, true);
+				apply_tile_choice(tuned_tile_pairs(w, a), &tune, kTileInv);
 			if (ride.on && !last && ride.next < ride.total && sweep_ride_ok(tune, Wo, Ho, batch, true)) {
 				int after = 0;
 				for (int m = j - 1; m >= 2; m--)

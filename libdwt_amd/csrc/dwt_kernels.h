@@ -57,6 +57,8 @@ struct SweepTuning {
 	int ring_inv = 8;    // inverse sweep ring rows (8 or 16)
 	int inv_pairs = 0;   // inverse: tile height (row pairs) of the large levels under the launcher's rule; 0 = 16 (32 for the levels of an in-place call)
 	int inv_ll_temporal = 1; // inverse: a level that is not the last stores its result temporal when it fits the Infinity Cache
+	int fuse01_ring = 0; // the fused pair of levels 0 and 1 (launch_fwd01): its ring rows per wave, 16 or 8; 0 = the launcher's rule.
+	                     // Its own knob: `ring` = 8 keeps a call level by level
 };
 
 // In-place level of the interleaved layout (input image == output image): a snapshot of what a tile reads of its
@@ -155,6 +157,7 @@ hipError_t launch_fwd_level(Wavelet w, const FwdLevelArgs &a, const SweepTuning 
 // two launches.  fwd01_can: W and H multiples of 4, both levels of 64 x 64 or more; fwd01_tiles: tiles per row.
 bool fwd01_can(Wavelet w, int W, int H);
 int fwd01_tiles(int W);
+bool fwd01_has_ring(int ring); // SweepTuning::fuse01_ring: a depth the sweep has a kernel for
 hipError_t launch_fwd01(const FwdLevelArgs &a, const SweepTuning &t, hipStream_t s);
 
 hipError_t launch_inv_level(Wavelet w, const InvLevelArgs &a, const SweepTuning &t, hipStream_t s, const IlStripArgs *strip = nullptr);

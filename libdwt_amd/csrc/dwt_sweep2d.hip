@@ -171,7 +171,9 @@ hipError_t launch_line_pass(Wavelet w, bool inverse, const void *src, void *dst,
 //     the dependence) and flushes it with 3 more below.
 // W and H are multiples of 4 and at least 128 (both levels of 64 x 64 or more); the last column of either level can then
 // be a lane's last own column or the one in the middle of its columns, and both are candidates of the selection.
-template <class W, int CPT, int RING, int NT, bool IL, bool X, bool F01 = false>
+// SELV: the vertical pass takes its select form in EVERY iteration (the shallow ring of the level sweeps, see there); the
+// fused pair's shallow ring is for launches of tens of rounds and keeps the deep ring's two bodies.
+template <class W, int CPT, int RING, int NT, bool IL, bool X, bool F01 = false, bool SELV = (RING == 8)>
 static __device__ __forceinline__ void fwd_sweep_tile(const FwdLevelArgs &a, const SweepGeom &g)
 {
 	static_assert(!F01 || (kIsSelEnds<W> && CPT == 8 && !IL && !X && W::K == 4 && !(NT & 8)), "the fused pair: float 9/7 by selection, Mallat");
@@ -594,7 +596,7 @@ static __device__ __forceinline__ void fwd_sweep_tile(const FwdLevelArgs &a, con
 			};
 			// (shallow ring: the launches of a few rounds of waves, bound by the longest wave -- the top tiles', for whom a
 			// second body means instructions fetched cold from HBM, 1 us a launch; there every iteration selects)
-			if constexpr (RING == 8 && has_coef_ends<W>::value)
+			if constexpr (SELV && has_coef_ends<W>::value)
 				vertical_sel();
 			else if (__builtin_expect(any, 0)) {
 				DWT_END_PATH();
@@ -814,11 +816,12 @@ __global__ __launch_bounds__(256) void k_fwd_sweep(FwdLevelArgs a, SweepGeom g)
 	fwd_sweep_any_tile<W, CPT, RING, NT, IL, false>(a, g);
 }
 
-// levels 0 and 1 of a float 9/7 transform in one sweep (fwd_sweep_tile, F01)
-template <int NT>
-__global__ __launch_bounds__(256) void k_fwd_sweep01(FwdLevelArgs a, SweepGeom g)
+// levels 0 and 1 of a float 9/7 transform in one sweep (fwd_sweep_tile, F01).  RING: the ring rows of a wave -- 16: one
+// workgroup of four waves per CU, one wave per SIMD; 8: built for two such workgroups per CU, two waves per SIMD
+template <int NT, int RING = 16>
+__global__ __launch_bounds__(256, RING == 16 ? 1 : 2) void k_fwd_sweep01(FwdLevelArgs a, SweepGeom g)
 {
-	fwd_sweep_tile<SelEnds<Cdf97S>, 8, 16, NT, false, false, true>(a, g);
+	fwd_sweep_tile<SelEnds<Cdf97S>, 8, RING, NT, false, false, true, false>(a, g);
 }
 
 // a level with a rectangle copy riding along: the workgroups behind the tiles' copy blocks of `r` (FwdLevelArgs::ride)
@@ -983,9 +986,31 @@ int fwd01_tiles(int W)
 	return (W + 511) / 512; // the level-0 sweep's own tiles
 }
 
+bool fwd01_has_ring(int ring)
+{
+	return ring == 16 || ring == 8;
+}
+
+// The ring rows of the fused pair's launch: option fuse01_ring or the tuner's choice (SweepTuning::fuse01_ring, never `ring`:
+// that one set to 8 keeps a call level by level, pair01_ok), else this rule: 8 rows -- two workgroups per CU, a second wave on
+// every SIMD to issue while the first one waits -- in the launches the pair engages in by itself, 32768 tiles of 64 pairs and
+// more; 16 rows, as before, below that, where only fuse01 = 2 brings the pair and nothing was measured.  The fused launch of
+// the whole 5-level call, 16 against 8 rows, one process, alternated, buffers placed by dwt_hip_alloc_batch: 64 x 8192^2
+// 6.77 -> 6.16 ms, 256 x 4096^2 6.81 -> 6.22 ms (the 16-row launches within 0.09 ms of each other); on plain allocations and
+// the two levels alone 6.87 -> 6.93 ms (a tie) and 6.99 -> 6.61 ms.  profiles/fuse01_ring_summary.md.
+static int fwd01_ring(const SweepTuning &t, int W, int H, int batch)
+{
+	if (t.fuse01_ring)
+		return t.fuse01_ring;
+	return (long)fwd01_tiles(W) * (((H >> 1) + 63) / 64) * batch >= 32768 ? 8 : 16;
+}
+
 hipError_t launch_fwd01(const FwdLevelArgs &a, const SweepTuning &t, hipStream_t s)
 {
 	if (!fwd01_can(kCdf97S, a.W, a.H) || a.batch < 1 || a.interleaved || a.ride || a.pair_hi > 0 || (t.tile_pairs & 1))
+		return hipErrorInvalidValue;
+	const int ring = fwd01_ring(t, a.W, a.H, a.batch);
+	if (!fwd01_has_ring(ring))
 		return hipErrorInvalidValue;
 	const int waves = sweep_waves(t);
 	const int Hd = a.H >> 1;
@@ -1002,22 +1027,23 @@ hipError_t launch_fwd01(const FwdLevelArgs &a, const SweepTuning &t, hipStream_t
 	}
 	const long tiles = (long)g.ntx * ((Hd + g.tile_pairs - 1) / g.tile_pairs);
 	const dim3 grid((unsigned)((tiles + waves - 1) / waves), a.batch);
-	const size_t lds = (size_t)waves * 16 * (64 * 8 + 32) * 4; // (139 264 B of 160 KiB for four waves: one workgroup per CU, as the level-0 sweep's deep ring)
+	// (16 rows: 139 264 B of 160 KiB for four waves, one workgroup per CU, as the level-0 sweep's deep ring; 8 rows: 69 632 B, two
+	// workgroups per CU)
+	const size_t lds = (size_t)waves * ring * (64 * 8 + 32) * 4;
 	// Cache policy as fwd_pick reads `nt`: loads and detail stores non-temporal whatever its bits 0 and 1 say; bit 2 keeps
 	// the LL band's stores -- here level 1's -- temporal while the launch's bands fit the Infinity Cache (as fwd_level_t
-	// decides it).  Bit 3, a ring of 8 rows and 4 columns per lane have no fused kernel: pair01_ok keeps such settings
-	// level by level; `ring` 16 is what this kernel is.
+	// decides it).  Bit 3, the sweep option `ring` = 8 and 4 columns per lane have no fused kernel: pair01_ok keeps such settings
+	// level by level; `ring` 16 is what this kernel's tiles are, whatever the depth of its own ring.
 	const bool ll_nt = !(t.nt & 4) || (t.nt_auto && (size_t)a.batch * (a.W >> 2) * (a.H >> 2) * sizeof(float) >= ((size_t)1 << 30));
-	if (ll_nt) {
-		if (hipError_t e = allow_lds((const void *)k_fwd_sweep01<3>, lds))
+	auto launch = [&](auto k) {
+		if (hipError_t e = allow_lds((const void *)k, lds))
 			return e;
-		k_fwd_sweep01<3><<<grid, 64 * waves, lds, s>>>(a, g);
-	} else {
-		if (hipError_t e = allow_lds((const void *)k_fwd_sweep01<7>, lds))
-			return e;
-		k_fwd_sweep01<7><<<grid, 64 * waves, lds, s>>>(a, g);
-	}
-	return hipGetLastError();
+		k<<<grid, 64 * waves, lds, s>>>(a, g);
+		return hipGetLastError();
+	};
+	if (ring == 16)
+		return ll_nt ? launch(k_fwd_sweep01<3, 16>) : launch(k_fwd_sweep01<7, 16>);
+	return ll_nt ? launch(k_fwd_sweep01<3, 8>) : launch(k_fwd_sweep01<7, 8>);
 }
 
 // whether launch_fwd_level / launch_inv_level would take a kernel that can carry a copy along for this level

@@ -30,7 +30,13 @@ struct TileCand {
 };
 static int pack_choice(const TileCand &c) { return c.pairs | (c.cpt << 16) | (c.ring << 24); }
 
-void apply_tile_choice(int choice, SweepTuning *t, bool inverse)
+// which knob a candidate's ring rows are: the forward level's, the inverse level's, the fused pair's
+static int &ring_of(SweepTuning &t, TileUse use)
+{
+	return use == kTileInv ? t.ring_inv : use == kTileFwd01 ? t.fuse01_ring : t.ring;
+}
+
+void apply_tile_choice(int choice, SweepTuning *t, TileUse use)
 {
 	if (choice <= 0)
 		return;
@@ -38,7 +44,7 @@ void apply_tile_choice(int choice, SweepTuning *t, bool inverse)
 	if ((choice >> 16) & 0xff)
 		t->cpt = (choice >> 16) & 0xff;
 	if ((choice >> 24) & 0xff)
-		(inverse ? t->ring_inv : t->ring) = (choice >> 24) & 0xff;
+		ring_of(*t, use) = (choice >> 24) & 0xff;
 }
 
 // One measurement at a time per device: several contexts on one GPU (the slots of dwt_multi.hip, a caller's own threads)
@@ -51,7 +57,7 @@ static std::recursive_mutex &measure_mutex()
 	return per_device[g.device & 63];
 }
 
-static int tune_tile_pairs(unsigned long long key, bool inverse, std::initializer_list<TileCand> cands, const std::function<hipError_t(const SweepTuning &)> &launch)
+static int tune_tile_pairs(unsigned long long key, TileUse use, std::initializer_list<TileCand> cands, const std::function<hipError_t(const SweepTuning &)> &launch)
 {
 	auto it = g.tile_cache.find(key);
 	if (it != g.tile_cache.end())
@@ -65,11 +71,22 @@ static int tune_tile_pairs(unsigned long long key, bool inverse, std::initialize
 	int best = 0;
 	float best_ms = 0;
 	static const bool verbose = getenv("DWT_HIP_TUNE_VERBOSE") != nullptr;
-	for (const TileCand &c : cands) {
-		if ((c.cpt && g.tune.cpt) || (c.ring && (inverse ? g.tune.ring_inv != 8 : g.tune.ring != 0)))
-			continue; // a width / ring depth set by hand stands
+	std::vector<int> tried;
+	for (TileCand c : cands) {
+		if (c.cpt && g.tune.cpt)
+			continue; // a width set by hand stands
+		if (c.ring && ring_of(g.tune, use) != (use == kTileInv ? 8 : 0)) {
+			// a ring depth set by hand stands.  The fused pair's candidates all name their depth: its heights are then
+			// measured once each, at the depth set by hand
+			if (use != kTileFwd01)
+				continue;
+			c.ring = 0;
+		}
+		if (std::find(tried.begin(), tried.end(), pack_choice(c)) != tried.end())
+			continue;
+		tried.push_back(pack_choice(c));
 		SweepTuning t = g.tune;
-		apply_tile_choice(pack_choice(c), &t, inverse);
+		apply_tile_choice(pack_choice(c), &t, use);
 		// three launches, the faster of the last two (the first one warms the caches it can)
 		float ms = 0;
 		bool ok = true;
@@ -84,7 +101,7 @@ static int tune_tile_pairs(unsigned long long key, bool inverse, std::initialize
 				ms = one;
 		}
 		if (verbose)
-			fprintf(stderr, "tune %s W %d: %d pairs, cpt %d, ring %d: %.1f us%s\n", inverse ? "inv" : "fwd", (int)((key >> 38) & 0xfffff), c.pairs, c.cpt, c.ring,
+			fprintf(stderr, "tune %s W %d: %d pairs, cpt %d, ring %d: %.1f us%s\n", use == kTileInv ? "inv" : use == kTileFwd01 ? "fwd01" : "fwd", (int)((key >> 38) & 0xfffff), c.pairs, c.cpt, c.ring,
 				ms * 1e3, ok ? "" : " (failed)");
 		if (ok && (!best || ms < best_ms)) {
 			best = pack_choice(c);
@@ -120,17 +137,20 @@ int tuned_tile_pairs(Wavelet w, const FwdLevelArgs &a)
 	const Wavelet wk = sweep32_wavelet(w);
 	// (round 5 also tried 128 pairs and the 256-column tile with the deep ring: never the fastest on a batch, and on one
 	// image -- 100.5 against 105.1 us in a variant scan -- inside the noise of where the image lies; scripts/r05/tuned_single.py)
-	return tune_tile_pairs(tile_key(w, false, a.W, a.H, a.batch), false, {{64, 0, 0}, {32, 0, 0}, {16, 0, 0}},
+	return tune_tile_pairs(tile_key(w, false, a.W, a.H, a.batch), kTileFwd, {{64, 0, 0}, {32, 0, 0}, {16, 0, 0}},
 		[&](const SweepTuning &t) { return launch_fwd_level(wk, a, t, g.stream); });
 }
 
 // the fused pair of levels 0 and 1 (launch_fwd01; a key of its own): 7 iterations of every tile are level 1's warm-up,
-// so 128 pairs join the candidates; idempotent like a single level -- it reads the image and writes elsewhere
+// so 128 pairs join the candidates; idempotent like a single level -- it reads the image and writes elsewhere.  Every height
+// at both ring depths (option fuse01_ring; one set by hand stands): which depth wins depends on where the buffers lie -- the
+// 8-row ring by 9 % on a placed 64 x 8192^2 batch, a tie on plain allocations (profiles/fuse01_ring_summary.md) -- and at 32
+// pairs the shallow ring is the faster one by 8 % wherever it was measured
 int tuned_tile_pairs01(Wavelet w, const FwdLevelArgs &a)
 {
 	if (!tunable(a.W, a.H, a.batch, a.interleaved))
 		return 0;
-	return tune_tile_pairs(tile_key(w, false, a.W, a.H, a.batch) ^ (1ull << 63), false, {{64, 0, 0}, {128, 0, 0}, {32, 0, 0}},
+	return tune_tile_pairs(tile_key(w, false, a.W, a.H, a.batch) ^ (1ull << 63), kTileFwd01, {{64, 0, 8}, {128, 0, 8}, {32, 0, 8}, {64, 0, 16}, {128, 0, 16}, {32, 0, 16}},
 		[&](const SweepTuning &t) { return launch_fwd01(a, t, g.stream); });
 }
 
@@ -141,7 +161,7 @@ int tuned_tile_pairs(Wavelet w, const InvLevelArgs &a)
 		return 0;
 	const Wavelet wk = sweep32_wavelet(w);
 	// (round 6: the 512-column tile joins the candidates; the launcher's rule is 16 pairs)
-	return tune_tile_pairs(tile_key(w, true, a.W, a.H, a.batch), true, {{16, 0, 0}, {32, 0, 0}, {8, 0, 0}, {16, 8, 0}, {32, 8, 0}},
+	return tune_tile_pairs(tile_key(w, true, a.W, a.H, a.batch), kTileInv, {{16, 0, 0}, {32, 0, 0}, {8, 0, 0}, {16, 8, 0}, {32, 8, 0}},
 		[&](const SweepTuning &t) { return launch_inv_level(wk, a, t, g.stream); });
 }
 // ---- placement of the LL scratch ------------------------------------------------------------------
