@@ -686,7 +686,7 @@ int dwt_hip_wp_features1d_batch(unsigned feature_mask, const void *ptr, size_t l
 int dwt_hip_wp_features2d_batch(unsigned feature_mask, const void *ptr, size_t batch_stride, int batch, int stride_x,
 	int size_x, int size_y, int level, int order, float p, float *fv, size_t fv_stride);
 
-/* Best basis and pruned wavelet packet trees of row batches (1-D only).  An extension, like the packets
+/* Best basis and pruned wavelet packet trees of row batches (images: further down).  An extension, like the packets
  * themselves: a leaf of a pruned tree holds, bit for bit, what that node holds in the full tree of its depth.
  *
  * Trees.  A tree of depth `levels` (1 <= levels <= min(floor(log2 N), DWT_HIP_WP_TREE_MAX_LEVELS)) is a bitmap of
@@ -740,6 +740,59 @@ int dwt_hip_wp_best1d_batch(int wavelet, int cost, float param, const void *src,
  * else as dwt_hip_wp1d_batch; with the full tree of depth `levels` the bits are those of dwt_hip_wp1d_batch. */
 int dwt_hip_wp_tree1d_batch(int wavelet, int inverse, const void *src, void *dst, size_t line_stride, size_t elem_stride, int n_lines,
 	int N, int levels, const uint32_t *tree, size_t tree_stride);
+
+/* Best basis and pruned packet QUADTREES of image batches: the 2-D twin of the four entries above.
+ *
+ * Quadtrees.  Node (ky, kx) of level j has the rectangle that dwt_hip_wp_nodes gives along y (index ky, of size_y) and along
+ * x (index kx, of size_x): the geometry of dwt_hip_wp2d_batch.  Its quadtree index is q = (4^j - 1)/3 + ky*2^j + kx; the
+ * root is 0.  Its children, in this order: LL (j+1, 2ky, 2kx), HL (j+1, 2ky, 2kx+1), LH (j+1, 2ky+1, 2kx), HH (j+1, 2ky+1,
+ * 2kx+1).  A tree of depth `levels` is a bitmap of DWT_HIP_WP_QTREE_WORDS uint32_t (64 bytes whatever `levels`): bit q
+ * (word q >> 5, bit q & 31) set means "this node is split into its four children".  The bits of levels >= `levels` mean
+ * nothing.  The EFFECTIVE tree is what can be reached from the root through set bits: a set bit below a clear one is
+ * ignored, on the host and in every kernel, so a tree in device memory needs no validation and no synchronisation, and
+ * the library writes effective bits only.  1 <= levels <= min(floor(log2(min(size_x, size_y))),
+ * DWT_HIP_WP_QTREE_MAX_LEVELS); anything else is an error, not a clamp.  The leaves of any effective tree tile the image,
+ * and a leaf (j, ky, kx) holds, bit for bit, what that node holds after dwt_hip_wp2d_batch with levels = j, at the
+ * node's place.
+ *
+ * Costs are the four kinds of enum dwt_hip_wp_cost with the terms and parameter checks stated above: double, NaN for a
+ * non-finite coefficient.  A node's cost is the double sum of its terms in a fixed order that is a function of size_x,
+ * size_y, the level and the node alone -- not of the batch size, the image's position in the batch or the run (no float
+ * or double atomics).  The fused route and the cross-check route may differ from each other in rounding.
+ *
+ * Selection, bottom-up: best[q] = cost[q] at level `levels`; above, c = ((best[LL] + best[HL]) + best[LH]) + best[HH],
+ * the node is split iff c < cost[q], then best[q] = c, else best[q] = cost[q].  A tie keeps the parent; so does a NaN on
+ * either side.  The total is best[0]. */
+#define DWT_HIP_WP_QTREE_MAX_LEVELS 5
+#define DWT_HIP_WP_QTREE_WORDS 16
+/* Host helpers, no device.  The best quadtree of a table of (4^(levels+1) - 1)/3 node costs in index order: the tree
+ * (DWT_HIP_WP_QTREE_WORDS words) and the total; either output may be NULL.  Returns 0, -1 for bad arguments. */
+int dwt_hip_wp_best_qtree(int levels, const double *cost, uint32_t *tree, double *total);
+/* the leaves of the effective tree, depth first with the children in the order LL, HL, LH, HH: level, ky, kx and the
+ * rectangle (x0, y0, w, h) of each (any array may be NULL; at most 4^levels entries).  Returns the number of leaves, -1
+ * for bad arguments. */
+int dwt_hip_wp_qtree_leaves(int size_x, int size_y, int levels, const uint32_t *tree, int *level, int *ky, int *kx, int *x0, int *y0,
+	int *w, int *h);
+/* The search: the cost of every node of levels 0 .. `levels` of every image, the best quadtree of each image and, where
+ * dst is not NULL, the image in that tree.  Wavelets, stride rules, in place (src == dst), the overlap check, the batch
+ * cap and the memory-space rule are those of dwt_hip_wp2d_batch.  Outputs, each optional, at least one of the four not
+ * NULL, all in the memory space of src: dst; tree -- image i's at (char *)tree + i*tree_stride, tree_stride >= 64 bytes
+ * and a multiple of 4; total -- `batch` doubles; node_cost -- image i's (4^(levels+1) - 1)/3 doubles in index order at
+ * (char *)node_cost + i*cost_stride, cost_stride at least that many doubles and a multiple of 8 bytes.  dst == NULL: costs
+ * and tree only, no coefficient is stored.  Device memory: everything is ordered on the context's stream; the entry
+ * neither waits for the stream nor reads anything back (the selection runs on the device).  Dense device images (stride_y
+ * 4, every address and stride a multiple of 4 bytes) take 2*levels + 2 launches, 3*levels + 2 with dst, whatever the
+ * batch and the shape; strided elements, host memory and every call under option "wp_fused" = 0 run the staged frame
+ * level by level through the exact line passes and small helper kernels.  Host memory: synchronous. */
+int dwt_hip_wp_best2d_batch(int wavelet, int cost, float param, const void *src, void *dst, size_t batch_stride, int batch,
+	int stride_x, int stride_y, int size_x, int size_y, int levels, uint32_t *tree, size_t tree_stride, double *total,
+	double *node_cost, size_t cost_stride);
+/* The transform in given quadtrees, forward or inverse (the inverse rebuilds exactly the nodes that the effective tree
+ * splits).  tree in the memory space of src, image i's at (char *)tree + i*tree_stride; tree_stride 0: one tree for every
+ * image.  Everything else as dwt_hip_wp2d_batch; with the full tree of depth `levels` the bits are those of
+ * dwt_hip_wp2d_batch.  Dense device images take one launch per level. */
+int dwt_hip_wp_tree2d_batch(int wavelet, int inverse, const void *src, void *dst, size_t batch_stride, int batch, int stride_x,
+	int stride_y, int size_x, int size_y, int levels, const uint32_t *tree, size_t tree_stride);
 
 /* The pixel front end: pictures of 8- or 16-bit unsigned pixels <-> the planes the 2-D transforms take,
  * with the DC level shift and the component transforms of ITU-T T.800 Annex G.  An extension: the reference's picture

@@ -262,6 +262,73 @@ struct Wp2dLevelArgs {
 bool wp2d_level_fits(const Wp2dLevelArgs &a); // aligned, every node of the level has two samples or more each way, a grid the launch can take
 hipError_t launch_wp2d_level(Wavelet w, bool inverse, const Wp2dLevelArgs &a, hipStream_t s);
 
+// Pruned packet QUADTREES and the best-basis search of images (dwt_wp2d.hip, dwt_wp_basis2d.hip).  Node
+// (ky, kx) of level j has the index q = (4^j - 1)/3 + ky*2^j + kx; bit q set = the node is split into LL, HL, LH, HH;
+// only what can be reached from the root through set bits counts.  A bitmap decides lift-or-copy and never an address.
+constexpr int WP_QTREE_WORDS = 16, WP_QTREE_MAX_LEVELS = 5; // (DWT_HIP_WP_QTREE_WORDS, DWT_HIP_WP_QTREE_MAX_LEVELS)
+static __host__ __device__ inline int wp_qbase(int j) { return ((1 << (2 * j)) - 1) / 3; } // index of node (0, 0) of level j; nodes of levels 0 .. j-1
+// is node (ky, kx) of level j < WP_QTREE_MAX_LEVELS split in the EFFECTIVE tree: its own bit and that of every ancestor
+static __host__ __device__ inline bool wp_qtree_split(const unsigned *tree, int j, int ky, int kx)
+{
+	for (int a = 0; a <= j; a++) {
+		const int q = wp_qbase(a) + ((ky >> (j - a)) << a) + (kx >> (j - a));
+		if (!((tree[q >> 5] >> (q & 31)) & 1u))
+			return false;
+	}
+	return true;
+}
+// tiles of `tile` samples along an axis of `size` samples per node of `level`: those of the longest node
+static __host__ __device__ inline int wp_tiles(int size, int level, int tile)
+{
+	const int longest = (size >> level) + ((size & ((1 << level) - 1)) != 0);
+	return (longest + tile - 1) / tile;
+}
+// launch_wp2d_level in trees: image b's at tree + b*tree_words (0: one tree for all).  A workgroup whose node is not split
+// in the effective tree copies its tile from src to the same place in dst.  a.level < WP_QTREE_MAX_LEVELS.
+struct Wp2dTreeArgs : Wp2dLevelArgs {
+	const unsigned *tree;
+	long tree_words;
+};
+hipError_t launch_wp2d_level_tree(Wavelet w, bool inverse, const Wp2dTreeArgs &a, hipStream_t s);
+// The cost of every tile of every node of `level` of dense images, the grid of launch_wp2d_level: the tile's terms reduced
+// to ONE double in a fixed order, to part[b*part_stride + ((ky*2^level + kx)*nty + ty)*ntx + tx] (ntx, nty: wp_tiles).
+struct WpQCostArgs {
+	const char *frame;
+	long pitch, bs;
+	int W, H, batch, level;
+	int kind; // WpCost
+	float param;
+	double *part;
+	long part_stride; // doubles between the slots of two images
+};
+hipError_t launch_wp_qcost_tiles(const WpQCostArgs &a, hipStream_t s);
+// the cross-check route's: one thread per (image, node) of `level`, the node's terms in row-major order, to
+// tab[b*tab_doubles + q]
+hipError_t launch_wp_qcost_level(const void *frame, long pitch, long bs, int W, int H, long batch, int level, int kind, float param, double *tab,
+	long tab_doubles, hipStream_t s);
+// The selection, all images in one launch.  part not null: tab[b][q] = the node's tile partials of launch_wp_qcost_tiles in
+// tile-index order first (the slots of level j of an image begin part_off[j] doubles into its block); null: tab holds the
+// costs.  Then bottom-up on a copy; the effective tree to tree_ws (WP_QTREE_WORDS words an image) and, where given, to
+// tree; total; node_cost.
+struct WpQSelectArgs {
+	const double *part;
+	long part_stride;
+	long part_off[WP_QTREE_MAX_LEVELS + 1];
+	double *tab; // batch tables of (4^(levels+1) - 1)/3 doubles, dense
+	int W, H, levels, batch;
+	unsigned *tree_ws;
+	unsigned *tree; // null, or image b's at tree + b*tree_words
+	long tree_words;
+	double *total;     // null, or batch doubles
+	double *node_cost; // null, or image b's table at node_cost + b*cost_doubles
+	long cost_doubles;
+};
+hipError_t launch_wp_qselect(const WpQSelectArgs &a, hipStream_t s);
+// one thread per sample of `batch` dense images: copied from `from` to the same place in `to` where the depth d of the
+// sample's leaf is lev (mode 0) / at most lev (mode 1)
+hipError_t launch_wp_qleaf_copy(const void *from, void *to, long pitch, long bs, int W, int H, long batch, int levels, const unsigned *tree,
+	long tree_words, int lev, int mode, hipStream_t s);
+
 // The pixel front end (dwt_pixels.hip): unsigned 8- / 16-bit pixels <-> wavelet planes, one launch per call.
 // Channel c of pixel (x, y) of picture b at pix + b*pix_bs + y*pix_pitch + x*pix_stride + c*chan_stride, plane (b, c) at
 // planes + (b*channels + c)*plane_stride with rows plane_pitch apart; all in bytes, checked by the driver.

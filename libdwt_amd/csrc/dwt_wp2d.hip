@@ -17,9 +17,12 @@
 //      lanes to adjacent addresses.
 // Windows, steps, end forms and scaling are those of k_line_pass on a line of the node's width / height, so the bits are
 // those of the exact line passes (option "wp_fused" = 0).  Every sample of the frame belongs to one tile of one node, so a
-// level writes the whole destination frame.
+// level writes the whole destination frame.  With the template flag TREE the same kernel runs a level of a pruned
+// quadtree: a workgroup of a node that is not split copies its tile.
 #include "dwt_kernels.h"
 #include "dwt_lift.h"
+
+#include <type_traits>
 
 namespace dwt {
 
@@ -27,8 +30,12 @@ namespace {
 
 constexpr int TW = WP2D_TILE_W, TH = WP2D_TILE_H;
 
-template <class W, bool INV>
-__global__ __launch_bounds__(256) void k_wp2d_level(Wp2dLevelArgs a, int ntx, int nty)
+// TREE: the workgroup derives, once, whether its node is split in the effective tree of its image -- the
+// node's own bit and that of each of its at most 4 ancestors -- and lifts as above, or copies its tile from src to the same
+// place in dst.  The nodes of a level under a leaf tile the leaf's rectangle, so the ping-pong of the levels keeps every leaf
+// intact.  The bitmap decides lift-or-copy only, never an address.
+template <class W, bool INV, bool TREE>
+__global__ __launch_bounds__(256) void k_wp2d_level(std::conditional_t<TREE, Wp2dTreeArgs, Wp2dLevelArgs> a, int ntx, int nty)
 {
 	using T = typename W::T;
 	constexpr int K = W::K;
@@ -50,6 +57,16 @@ __global__ __launch_bounds__(256) void k_wp2d_level(Wp2dLevelArgs a, int ntx, in
 	const T *const src = (const T *)(a.src + (long)blockIdx.z * a.src_bs);
 	T *const dst = (T *)(a.dst + (long)blockIdx.z * a.dst_bs);
 	const long sp = a.src_pitch / 4, dp = a.dst_pitch / 4;
+	if constexpr (TREE) {
+		if (!wp_qtree_split(a.tree + (long)blockIdx.z * a.tree_words, a.level, qy, qx)) {
+			for (int idx = tid; idx < TH * TW; idx += 256) {
+				const int y = y0 + idx / TW, x = x0 + idx % TW;
+				if (y < h && x < w)
+					dst[(long)(sy + y) * dp + sx + x] = src[(long)(sy + y) * sp + sx + x];
+			}
+			return;
+		}
+	}
 
 	// 1. stage
 	const int rows = th + 2 * K, cols = tw + 2 * K;
@@ -129,12 +146,7 @@ __global__ __launch_bounds__(256) void k_wp2d_level(Wp2dLevelArgs a, int ntx, in
 	}
 }
 
-// tiles per node along an axis of `size` samples at `level`: those of the longest node
-int tiles(int size, int level, int tile)
-{
-	const int longest = (size >> level) + ((size & ((1 << level) - 1)) != 0);
-	return (longest + tile - 1) / tile;
-}
+int tiles(int size, int level, int tile) { return wp_tiles(size, level, tile); } // per node along an axis: those of the longest node
 
 template <class W>
 hipError_t wp2d_level_t(bool inverse, const Wp2dLevelArgs &a, hipStream_t s)
@@ -142,9 +154,21 @@ hipError_t wp2d_level_t(bool inverse, const Wp2dLevelArgs &a, hipStream_t s)
 	const int ntx = tiles(a.W, a.level, TW), nty = tiles(a.H, a.level, TH);
 	const dim3 grid(ntx << a.level, nty << a.level, a.batch);
 	if (inverse)
-		k_wp2d_level<W, true><<<grid, 256, 0, s>>>(a, ntx, nty);
+		k_wp2d_level<W, true, false><<<grid, 256, 0, s>>>(a, ntx, nty);
 	else
-		k_wp2d_level<W, false><<<grid, 256, 0, s>>>(a, ntx, nty);
+		k_wp2d_level<W, false, false><<<grid, 256, 0, s>>>(a, ntx, nty);
+	return hipGetLastError();
+}
+
+template <class W>
+hipError_t wp2d_level_tree_t(bool inverse, const Wp2dTreeArgs &a, hipStream_t s)
+{
+	const int ntx = tiles(a.W, a.level, TW), nty = tiles(a.H, a.level, TH);
+	const dim3 grid(ntx << a.level, nty << a.level, a.batch);
+	if (inverse)
+		k_wp2d_level<W, true, true><<<grid, 256, 0, s>>>(a, ntx, nty);
+	else
+		k_wp2d_level<W, false, true><<<grid, 256, 0, s>>>(a, ntx, nty);
 	return hipGetLastError();
 }
 
@@ -167,6 +191,18 @@ hipError_t launch_wp2d_level(Wavelet w, bool inverse, const Wp2dLevelArgs &a, hi
 	case kCdf97S: return wp2d_level_t<Cdf97S>(inverse, a, s);
 	case kCdf53S: return wp2d_level_t<Cdf53S>(inverse, a, s);
 	case kInterp53S: return wp2d_level_t<Interp53S>(inverse, a, s);
+	default: return hipErrorInvalidValue;
+	}
+}
+
+hipError_t launch_wp2d_level_tree(Wavelet w, bool inverse, const Wp2dTreeArgs &a, hipStream_t s)
+{
+	if (!wp2d_level_fits(a) || a.src == a.dst || a.level >= WP_QTREE_MAX_LEVELS || !a.tree || (uintptr_t)a.tree % 4 || a.tree_words < 0)
+		return hipErrorInvalidValue;
+	switch (w) {
+	case kCdf97S: return wp2d_level_tree_t<Cdf97S>(inverse, a, s);
+	case kCdf53S: return wp2d_level_tree_t<Cdf53S>(inverse, a, s);
+	case kInterp53S: return wp2d_level_tree_t<Interp53S>(inverse, a, s);
 	default: return hipErrorInvalidValue;
 	}
 }

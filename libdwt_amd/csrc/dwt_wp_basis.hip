@@ -23,26 +23,13 @@
 #include "dwt_line_lds.h"
 #include "dwt_device.h"
 #include "dwt_wp_level.h"
+#include "dwt_wp_cost.h" // wp_term: one coefficient's term of a cost
 
 #include <cfloat>
 #include <climits>
 #include <cmath>
 
 namespace dwt {
-
-// one coefficient's term of an additive cost (enum dwt_hip_wp_cost); a non-finite coefficient gives NaN
-static __device__ __forceinline__ double wp_term(int kind, float param, float c)
-{
-	if (!(fabsf(c) <= FLT_MAX))
-		return (double)NAN;
-	const double x = (double)c, e = x * x;
-	switch (kind) {
-	case kWpCostShannon: return e == 0 ? 0.0 : -e * log(e);
-	case kWpCostLogEnergy: return e == 0 ? 0.0 : log(e);
-	case kWpCostLp: return param == 1.0f ? fabs(x) : pow(fabs(x), (double)param);
-	default: return fabsf(c) > param ? 1.0 : 0.0;
-	}
-}
 
 // eff: the bits of raw below `levels` that can be reached from the root through set bits; threads 0 .. 31 of the line, one
 // word each.  The caller puts a barrier on either side.

@@ -5,6 +5,8 @@ every level, not only the L node.  A submodule of its own: import it as ``from l
     packets.wp_features1d_batch("wps", x, 4 * N, 4, n_lines, N, levels, packets.FREQUENCY, fv, 1 << levels)
     tree = packets.wp_joint_basis(dwt.CDF97_S, packets.COST_SHANNON, 0.0, x, 4 * N, 4, n_lines, N, levels)   # one tree for all rows
     packets.wp_tree1d_batch(dwt.CDF97_S, False, x, x, 4 * N, 4, n_lines, N, levels, tree, 0)             # 
+    qtree = packets.wp_joint_qtree(dwt.CDF97_S, packets.COST_SHANNON, 0.0, img, 4 * W * H, batch, 4 * W, 4, W, H, levels)
+    packets.wp_tree2d_batch(dwt.CDF97_S, False, img, img, 4 * W * H, batch, 4 * W, 4, W, H, levels, qtree)   # 
 
 Pointers are numpy arrays, torch tensors or integer addresses, host or device memory, as everywhere in libdwt_amd.
 """
@@ -42,6 +44,15 @@ lib.dwt_hip_wp_best1d_batch.argtypes = [_I, _I, _F, _P, _P, _S, _S, _I, _I, _I, 
 lib.dwt_hip_wp_best1d_batch.restype = _I
 lib.dwt_hip_wp_tree1d_batch.argtypes = [_I, _I, _P, _P, _S, _S, _I, _I, _I, _P, _S]
 lib.dwt_hip_wp_tree1d_batch.restype = _I
+QTREE_MAX_LEVELS, QTREE_WORDS = 5, 16  # DWT_HIP_WP_QTREE_MAX_LEVELS, DWT_HIP_WP_QTREE_WORDS
+lib.dwt_hip_wp_best_qtree.argtypes = [_I, C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.POINTER(C.c_double)]
+lib.dwt_hip_wp_best_qtree.restype = _I
+lib.dwt_hip_wp_qtree_leaves.argtypes = [_I, _I, _I, C.POINTER(C.c_uint32)] + [_IP] * 7
+lib.dwt_hip_wp_qtree_leaves.restype = _I
+lib.dwt_hip_wp_best2d_batch.argtypes = [_I, _I, _F, _P, _P, _S, _I, _I, _I, _I, _I, _I, _P, _S, _P, _P, _S]
+lib.dwt_hip_wp_best2d_batch.restype = _I
+lib.dwt_hip_wp_tree2d_batch.argtypes = [_I, _I, _P, _P, _S, _I, _I, _I, _I, _I, _I, _P, _S]
+lib.dwt_hip_wp_tree2d_batch.restype = _I
 
 
 def wp_nodes(size, level):
@@ -180,3 +191,99 @@ def wp_joint_basis(wavelet, cost, param, src, line_stride, elem_stride, n_lines,
     for row in table:
         joint += row
     return wp_best_tree(levels, joint)[0]
+
+
+# ---- quadtrees of image batches ----------------------------------------------------------------------
+def qtree_nodes(levels):
+    """the nodes of levels 0 .. `levels` of a quadtree: the length of a cost table"""
+    return ((4 << (2 * levels)) - 1) // 3
+
+
+def wp_best_qtree(levels, cost):
+    """dwt_hip_wp_best_qtree: (tree, total) of a table of (4^(levels+1) - 1)/3 node costs in index order (node (ky, kx) of
+    level j at (4^j - 1)/3 + ky * 2^j + kx); the tree is a list of QTREE_WORDS words holding effective bits only.  A tie
+    and a NaN keep the parent.  Host only."""
+    cost = [float(c) for c in cost]
+    if not 1 <= levels <= QTREE_MAX_LEVELS or len(cost) < qtree_nodes(levels):
+        raise DwtError("wp_best_qtree: %d levels, a table of %d costs" % (levels, len(cost)))
+    table, tree, total = (C.c_double * len(cost))(*cost), (C.c_uint32 * QTREE_WORDS)(), C.c_double()
+    if lib.dwt_hip_wp_best_qtree(levels, table, tree, C.byref(total)) != 0:
+        raise DwtError("wp_best_qtree: bad arguments")
+    return list(tree), total.value
+
+
+def wp_qtree_leaves(size_x, size_y, levels, tree):
+    """dwt_hip_wp_qtree_leaves: [(level, ky, kx, x0, y0, w, h)] of the leaves of the effective tree, depth first with the
+    children in the order LL, HL, LH, HH.  Host only."""
+    tree = [int(t) for t in tree]
+    if len(tree) != QTREE_WORDS:
+        raise DwtError("wp_qtree_leaves: a quadtree has %d words" % QTREE_WORDS)
+    words = (C.c_uint32 * QTREE_WORDS)(*tree)
+    n = lib.dwt_hip_wp_qtree_leaves(size_x, size_y, levels, words, *([None] * 7))
+    if n < 0:
+        raise DwtError("wp_qtree_leaves: %d levels over an image of %d x %d" % (levels, size_x, size_y))
+    out = [(_I * n)() for _ in range(7)]
+    lib.dwt_hip_wp_qtree_leaves(size_x, size_y, levels, words, *out)
+    return list(zip(*(list(o) for o in out)))
+
+
+def wp_best2d_batch(wavelet, cost, param, src, dst, batch_stride, batch, stride_x, stride_y, size_x, size_y, levels, tree=None,
+                    tree_stride=4 * QTREE_WORDS, total=None, node_cost=None, cost_stride=None):
+    """dwt_hip_wp_best2d_batch: the cost of every node, the best quadtree of every image and (dst not None) the image in
+    that tree.  Every output is optional and lies where src lies; strides in bytes (cost_stride None: dense tables).  Dense
+    device images take 2 * levels + 2 launches (3 * levels + 2 with dst); nothing is read back."""
+    if cost_stride is None:
+        cost_stride = 8 * qtree_nodes(levels) if 0 <= levels <= 12 else 0
+    _check(lib.dwt_hip_wp_best2d_batch(wavelet, cost, float(param), _addr(src), _opt(dst), batch_stride, batch, stride_x, stride_y,
+                                       size_x, size_y, levels, _opt(tree), tree_stride, _opt(total), _opt(node_cost), cost_stride),
+           "dwt_hip_wp_best2d_batch")
+
+
+def wp_tree2d_batch(wavelet, inverse, src, dst, batch_stride, batch, stride_x, stride_y, size_x, size_y, levels, tree, tree_stride=0):
+    """dwt_hip_wp_tree2d_batch: the images in given quadtrees, forward or inverse; tree_stride 0 is one tree for every
+    image.  The trees lie where src lies -- except that a list of QTREE_WORDS ints (what wp_best_qtree returns) is taken
+    for images in either memory space: for device images it is copied to device memory for the length of the call."""
+    tmp = None
+    if isinstance(tree, (list, tuple)):
+        words = (C.c_uint32 * QTREE_WORDS)(*[int(t) for t in tree])
+        tree, tree_stride = C.addressof(words), 0
+        if lib.dwt_hip_is_device_pointer(_addr(src)):
+            tmp = lib.dwt_hip_malloc(4 * QTREE_WORDS)
+            if not tmp or lib.dwt_hip_memcpy_h2d(tmp, tree, 4 * QTREE_WORDS) != 0:
+                raise DwtError("wp_tree2d_batch: no device memory for the tree")
+            tree = tmp
+    try:
+        _check(lib.dwt_hip_wp_tree2d_batch(wavelet, 1 if inverse else 0, _addr(src), _addr(dst), batch_stride, batch, stride_x, stride_y,
+                                           size_x, size_y, levels, _addr(tree), tree_stride), "dwt_hip_wp_tree2d_batch")
+    finally:
+        if tmp:
+            lib.dwt_hip_sync()
+            lib.dwt_hip_free(tmp)
+
+
+def wp_joint_qtree(wavelet, cost, param, src, batch_stride, batch, stride_x, stride_y, size_x, size_y, levels):
+    """One quadtree for all images, the 2-D twin of wp_joint_basis: the search for the cost tables alone, the tables summed
+    over the images on the host in float64 (batch order), wp_best_qtree of the sum.  Returns the tree (a list of
+    QTREE_WORDS words) for wp_tree2d_batch(..., tree_stride=0); src is only read."""
+    import numpy as np
+
+    nq = qtree_nodes(levels)
+    table = np.zeros((max(batch, 0), nq), np.float64)
+    args = (wavelet, cost, param, src, None, batch_stride, batch, stride_x, stride_y, size_x, size_y, levels)
+    if lib.dwt_hip_is_device_pointer(_addr(src)):
+        dev = lib.dwt_hip_malloc(max(table.nbytes, 16))
+        if not dev:
+            raise DwtError("wp_joint_qtree: no device memory for the cost tables")
+        try:
+            wp_best2d_batch(*args, node_cost=dev)
+            lib.dwt_hip_sync()
+            if table.nbytes and lib.dwt_hip_memcpy_d2h(table.ctypes.data, dev, table.nbytes) != 0:
+                raise DwtError("wp_joint_qtree: the cost tables could not be read")
+        finally:
+            lib.dwt_hip_free(dev)
+    else:
+        wp_best2d_batch(*args, node_cost=table)
+    joint = np.zeros(nq, np.float64)
+    for row in table:
+        joint += row
+    return wp_best_qtree(levels, joint)[0]
