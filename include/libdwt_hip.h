@@ -171,6 +171,11 @@ void dwt_hip_alloc_batch_report(int *chunks, int *dst_tried, int *ll_tried, int 
  * "fuse01_ring" (the LDS ring rows per wave of that one launch: 16 = one workgroup of four waves per CU, 8 = two of them, two
  * waves per SIMD; 0 = the launcher's rule -- 8 from 32768 tiles on, else 16 -- or what dwt_hip_tune measured; any other value is
  * refused; same bits),
+ * "fuse01_updown" (which tile rows of that launch march from their lower edge upward, so that vertically adjacent tiles read
+ * the rows around their common edge at the same time and the second read hits in L2: 0 = none, 1 = the odd ones, 2 = the even
+ * ones (for tests), -1 = the launcher's rule -- 1 in launches of 32768 tiles and more that run the 8-row ring, whether the ring's rule or
+ * "fuse01_ring" chose it, else 0 -- or what dwt_hip_tune measured;
+ * any other value is refused; same bits; dwt_hip_get_option("fuse01_last_updown") reads what the last such launch ran with),
  * "ride_copy" (1 = in-place Mallat calls on one image: the copy of level 0's staged subbands rides along with the deeper
  * levels' launches as extra workgroups; 0 = a launch of its own, the cross-check) and "ride_mib" (MiB of it per small level),
  * "host_pipeline" (1 = host-pointer calls on images of 64 MiB and more run band by band under their own

@@ -9,7 +9,8 @@ using namespace dwtb;
 // One table for dwt_hip_set_option / dwt_hip_get_option: the option's name, where it lives in the calling thread's
 // context, whether measured tile heights depend on it (they are forgotten when it changes), how a value is normalised.
 namespace {
-enum OptKind { kPlain, kSweep /* tile heights were measured under it */, kBool, kNonNegative, kRing01 /* kSweep; 0 or a depth the fused pair has a kernel for */ };
+enum OptKind { kPlain, kSweep /* tile heights were measured under it */, kBool, kNonNegative, kRing01 /* kSweep; 0 or a depth the fused pair has a kernel for */,
+	kUpDown01 /* kSweep; -1, 0, 1 or 2 */ };
 struct Opt {
 	const char *name;
 	int *(*ref)(Ctx &);
@@ -20,7 +21,7 @@ const Opt kOpts[] = {
 	DWT_OPT("generic", force_generic, kSweep), DWT_OPT("eaw_two_pass", eaw_two_pass, kBool), DWT_OPT("feat_groups", feat_groups, kNonNegative), DWT_OPT("swt_fused", swt_fused, kBool), DWT_OPT("swt2d_fused", swt2d_fused, kBool), DWT_OPT("wp_fused", wp_fused, kBool), DWT_OPT("pixels_wide", pixels_wide, kBool), DWT_OPT("quant_wide", quant_wide, kBool), DWT_OPT("window_fused", window_fused, kNonNegative), DWT_OPT("cond_fused", cond_fused, kPlain), DWT_OPT("timefreq_tiled", tf_tiled, kBool), DWT_OPT("cpt", tune.cpt, kSweep), DWT_OPT("tile_pairs", tune.tile_pairs, kSweep),
 	DWT_OPT("waves", tune.waves, kSweep), DWT_OPT("xcd_swizzle", tune.xcd_swizzle, kSweep), DWT_OPT("ring", tune.ring, kSweep),
 	DWT_OPT("ring_inv", tune.ring_inv, kSweep), DWT_OPT("inv_ll_temporal", tune.inv_ll_temporal, kSweep), DWT_OPT("inv_pairs", tune.inv_pairs, kSweep), DWT_OPT("nt", tune.nt, kSweep), DWT_OPT("nt_auto", tune.nt_auto, kSweep),
-	DWT_OPT("fma", fma, kSweep), DWT_OPT("fused_d", fused_d, kPlain), DWT_OPT("fuse01", fuse01, kPlain), DWT_OPT("fuse01_ring", tune.fuse01_ring, kRing01), DWT_OPT("ride_copy", ride_copy, kBool), DWT_OPT("ride_mib", ride_mib, kNonNegative), DWT_OPT("il_exact_borders", il_exact_borders, kPlain),
+	DWT_OPT("fma", fma, kSweep), DWT_OPT("fused_d", fused_d, kPlain), DWT_OPT("fuse01", fuse01, kPlain), DWT_OPT("fuse01_ring", tune.fuse01_ring, kRing01), DWT_OPT("fuse01_updown", tune.fuse01_updown, kUpDown01), DWT_OPT("ride_copy", ride_copy, kBool), DWT_OPT("ride_mib", ride_mib, kNonNegative), DWT_OPT("il_exact_borders", il_exact_borders, kPlain),
 	DWT_OPT("il_inplace_shell", il_inplace_shell, kPlain), DWT_OPT("host_pipeline", host_pipeline, kPlain),
 	DWT_OPT("tune_tiles", tune_tiles, kPlain), DWT_OPT("tune_in_call", tune_in_call, kBool), DWT_OPT("place_tries", place_tries, kPlain),
 	DWT_OPT("place_min_mib", place_min_mib, kNonNegative), DWT_OPT("place_max_gib", place_max_gib, kNonNegative),
@@ -234,7 +235,9 @@ int dwt_hip_set_option(const char *name, int value)
 		return fail("unknown option '%s'", name ? name : "(null)");
 	if (o->kind == kRing01 && value != 0 && !fwd01_has_ring(value))
 		return fail("option fuse01_ring: 0, 8 or 16 (the fused pair has no kernel with a ring of %d rows)", value);
-	if (o->kind == kSweep || o->kind == kRing01)
+	if (o->kind == kUpDown01 && !fwd01_has_updown(value))
+		return fail("option fuse01_updown: -1 (the rule), 0, 1 or 2, not %d", value);
+	if (o->kind == kSweep || o->kind == kRing01 || o->kind == kUpDown01)
 		g.tile_cache.clear();
 	*o->ref(g) = o->kind == kBool ? (value ? 1 : 0) : (o->kind == kNonNegative && value < 0) ? 0 : value;
 	return 0;
@@ -259,6 +262,8 @@ int dwt_hip_get_option(const char *name)
 		return (int)g.tile_cache.size();
 	if (!strcmp(name, "fuse01_last_choice")) // the measured choice of the last fused pair: row pairs | ring rows << 24 (0: the rule's)
 		return g.stat_choice01;
+	if (!strcmp(name, "fuse01_last_updown")) // the tile rows that marched upward in the last fused pair's launch: 0 none, 1 odd, 2 even
+		return g.stat_updown01;
 	const Opt *o = find_opt(name);
 	return o ? *o->ref(g) : -1;
 }

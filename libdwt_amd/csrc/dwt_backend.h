@@ -108,6 +108,7 @@ struct Ctx {
 	bool placing = false;       // inside a timed trial: no nested search
 	long stat_launches = 0, stat_allocs = 0; // kernel launches / device allocations made by this context's 2-D drivers (tests)
 	int stat_choice01 = 0; // the measured choice (apply_tile_choice) the last fused pair of levels 0 and 1 ran with; 0: the launcher's rule (tests)
+	int stat_updown01 = 0; // the tile rows that marched upward in that launch (fwd01_updown: 0, 1, 2)
 	double place_ms[8] = {0};   // what the last search measured, per candidate
 	int place_n = 0, place_best = -1;
 	int fused_d = 1; // double-precision wavelets through the fused sweeps (0: exact line passes only)
@@ -250,6 +251,7 @@ bool may_measure(); // inside dwt_hip_tune, or DWT_HIP_TUNE=1 / option "tune_in_
 int tuned_tile_pairs(Wavelet w, const FwdLevelArgs &a); // the measured choice for this level (packed; 0: none) ...
 int tuned_tile_pairs(Wavelet w, const InvLevelArgs &a);
 int tuned_tile_pairs01(Wavelet w, const FwdLevelArgs &a); // the same for the fused pair of levels 0 and 1 (launch_fwd01)
+int tuned_updown01(Wavelet w, const FwdLevelArgs &a, const SweepTuning &t); // the measured direction of the fused pair's tile rows under `t` (0, 1; -1: none)
 enum TileUse { kTileFwd, kTileInv, kTileFwd01 }; // whose launch a measured choice is for: a forward level, an inverse level, the fused pair
 void apply_tile_choice(int choice, SweepTuning *t, TileUse use); // ... applied to the launch's tuning
 int forward2d(const Call2d &c, Img src, Img dst, const Geom &ge, int *jp, int decompose_one, int zero_padding, int batch, long src_bstride, long dst_bstride);

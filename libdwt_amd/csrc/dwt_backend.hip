@@ -471,6 +471,13 @@ int forward2d(const Call2d &c, Img src, Img dst, const Geom &ge, int *jp, int de
 				if (pair)
 					g.stat_choice01 = choice;
 			}
+			if (pair) {
+				// the direction of the tile rows: the option, else what dwt_hip_tune measured at this height and depth, else the rule
+				const int dir = tuned_updown01(w, a, tune);
+				if (dir >= 0)
+					tune.fuse01_updown = dir;
+				g.stat_updown01 = fwd01_updown(tune, a.W, a.H, a.batch);
+			}
 			if (ride.on && ride.next < ride.total && es == 4 && sweep_ride_ok(tune, Wo, Ho, batch, false)) {
 				a.ride = &ride.r;
 				a.ride_lo = ride.next;

@@ -59,6 +59,7 @@ struct SweepTuning {
 	int inv_ll_temporal = 1; // inverse: a level that is not the last stores its result temporal when it fits the Infinity Cache
 	int fuse01_ring = 0; // the fused pair of levels 0 and 1 (launch_fwd01): its ring rows per wave, 16 or 8; 0 = the launcher's rule.
 	                     // Its own knob: `ring` = 8 keeps a call level by level
+	int fuse01_updown = -1; // the fused pair: which tile rows march upward -- 0 none, 1 the odd ones, 2 the even ones; -1 = the launcher's rule
 };
 
 // In-place level of the interleaved layout (input image == output image): a snapshot of what a tile reads of its
@@ -158,6 +159,8 @@ hipError_t launch_fwd_level(Wavelet w, const FwdLevelArgs &a, const SweepTuning 
 bool fwd01_can(Wavelet w, int W, int H);
 int fwd01_tiles(int W);
 bool fwd01_has_ring(int ring); // SweepTuning::fuse01_ring: a depth the sweep has a kernel for
+bool fwd01_has_updown(int v);  // SweepTuning::fuse01_updown: -1, 0, 1 or 2
+int fwd01_updown(const SweepTuning &t, int W, int H, int batch); // the tile rows that march upward in launch_fwd01's launch (0, 1, 2)
 hipError_t launch_fwd01(const FwdLevelArgs &a, const SweepTuning &t, hipStream_t s);
 
 hipError_t launch_inv_level(Wavelet w, const InvLevelArgs &a, const SweepTuning &t, hipStream_t s, const IlStripArgs *strip = nullptr);

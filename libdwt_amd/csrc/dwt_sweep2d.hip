@@ -168,13 +168,14 @@ hipError_t launch_line_pass(Wavelet w, bool inverse, const void *src, void *dst,
 //   - every sample is written once (lanes right of the line's end are dropped by the row's buffer descriptor); the LL band
 //     of level 0 is never written.  `out_ll` is level 1's LL band;
 //   - vertically a tile warms level 1 up with 4 more iterations above (none at the top of the image: the end form cuts
-//     the dependence) and flushes it with 3 more below.
+//     the dependence) and flushes it with 3 more below.  Every second tile row can march the other way, from its lower edge
+//     upward (the kernel's argument `updown`): the same iterations in the mirrored order, same bits -- see `up` below.
 // W and H are multiples of 4 and at least 128 (both levels of 64 x 64 or more); the last column of either level can then
 // be a lane's last own column or the one in the middle of its columns, and both are candidates of the selection.
 // SELV: the vertical pass takes its select form in EVERY iteration (the shallow ring of the level sweeps, see there); the
 // fused pair's shallow ring is for launches of tens of rounds and keeps the deep ring's two bodies.
 template <class W, int CPT, int RING, int NT, bool IL, bool X, bool F01 = false, bool SELV = (RING == 8)>
-static __device__ __forceinline__ void fwd_sweep_tile(const FwdLevelArgs &a, const SweepGeom &g)
+static __device__ __forceinline__ void fwd_sweep_tile(const FwdLevelArgs &a, const SweepGeom &g, [[maybe_unused]] int updown = 0)
 {
 	static_assert(!F01 || (kIsSelEnds<W> && CPT == 8 && !IL && !X && W::K == 4 && !(NT & 8)), "the fused pair: float 9/7 by selection, Mallat");
 	using T = typename W::T;
@@ -215,9 +216,29 @@ static __device__ __forceinline__ void fwd_sweep_tile(const FwdLevelArgs &a, con
 	const int img = blockIdx.y;
 	const int Wd = (a.W + 1) >> 1, Hd = (a.H + 1) >> 1;
 	const int c0 = tx * TW;
-	const int warm = (F01 && A > 0) ? K : 0; // level 1's warm-up above the tile
+	// (F01) the tile's direction, wave-uniform: `up` tiles march from their lower edge to their upper one (`updown`: the odd or
+	// the even tile rows), dir = -1.  Iteration `it` then takes the rows (2q + 1, 2q), q = q0 - it, in place of (2q - 1, 2q),
+	// q = q0 + it: every step has its two neighbours exchanged inside a commutative sum, so the bits are those of the march
+	// downward.  An upward iteration completes the L row q + 2 and the H row q + 1 (downward: both q - 2).
+	[[maybe_unused]] int up = 0;
+	if constexpr (F01)
+		up = (updown && !((ty ^ updown) & 1)) ? 1 : 0;
+	[[maybe_unused]] const int dir = 1 - 2 * up;
+	// level 1's warm-up beyond the edge the tile starts at (none at the image's: the end form cuts the dependence).  An upward
+	// tile starts at q = B + 4 (its LL row B + 2, the last one level 1 needs, takes the input rows up to 2 B + 8) and ends at
+	// A - 6 like a downward one starts there; at the image's bottom it starts at q = Hd + 1 as a downward one at the top at -2
+	const int warm = !F01 ? 0 : up ? (B < Hd ? K : 1) : (A > 0 ? K : 0);
 	const int n_iter = (B - A) + K + warm + (F01 ? 3 : 0);
-	const int q0 = A - K / 2 - warm;
+	const int q0 = (F01 && up) ? B + warm : A - K / 2 - warm;
+	// (F01) the iterations whose rows a vertical neighbour reads too, [0, t_lo) and [t_hi, n_iter): see issue()
+	[[maybe_unused]] int t_lo = 0, t_hi = 0;
+	if constexpr (F01) {
+		t_lo = (up ? B < Hd : A > 0) ? (updown ? 11 : K + warm) : 0;
+		t_hi = (updown && (up ? A > 0 : B < Hd)) ? n_iter - 11 : n_iter;
+	}
+	// (F01) the row step s of iteration `it` acts on (the iteration's own two rows: s = 0 and s = -1); the other sweeps keep
+	// 2 (q0 + it) - 1 - s written out where they need it, as the parent has it
+	[[maybe_unused]] auto row_of_step = [&](int it, int s) { return 2 * (q0 + dir * it) - dir * (1 + s); };
 
 	const T *in = (const T *)a.in + (long)img * a.in_bstride;
 	T *out_ll = (T *)a.out_ll + (long)img * a.ll_bstride;
@@ -251,7 +272,9 @@ static __device__ __forceinline__ void fwd_sweep_tile(const FwdLevelArgs &a, con
 	auto issue = [&](int it) {
 #pragma unroll
 		for (int rr = 0; rr < 2; rr++) {
-			const int ri = 2 * (q0 + it) - 1 + rr;
+			int ri = 2 * (q0 + it) - 1 + rr;
+			if constexpr (F01)
+				ri = row_of_step(it, -rr);
 			const int r = tall ? reflect1(ri, a.H) : reflect(ri, a.H);
 			char *lrow = ring + (size_t)(islot + rr) * RS * 4;
 			const T *grow = in + (long)r * a.in_pitch;
@@ -281,6 +304,27 @@ static __device__ __forceinline__ void fwd_sweep_tile(const FwdLevelArgs &a, con
 			// tile above at the end of its march.  The first read is TEMPORAL whatever the policy, so that the
 			// lines can wait in the Infinity Cache for the second one (every other row is read once).  Round 4,
 			// 32 x 8192^2, one placement: level 0 6108 -> 6240 GB/s; with the halo columns temporal too 6285.
+			// (F01, `updown`) a tile and its vertical neighbour march towards their common edge or away from it together and
+			// read the 22 rows around it within some 11 iterations of each other: both reads of those rows, at either end of the
+			// tile, are temporal and the second one hits in L2 (profiles/fuse01_updown_summary.md: non-temporal loses 5 %).
+			// The fused pair takes its rows in a statement of its own (no shells, no kept columns), so that the other sweeps keep
+			// the parent's statement word for word: any other form of its test compiles to other register counts in the
+			// kernels of the interleaved layout.
+			if constexpr (F01) {
+				auto row_dma = [&](auto aux) {
+#pragma unroll
+					for (int i = 0; i < CPT / 4; i++)
+						dma16_row<decltype(aux)::value>(rs, (unsigned)(c0 + i * 256 + lane * 4) * 4, lrow + i * 1024);
+					if (lane < n_edge)
+						dma4<decltype(aux)::value>(esrc, lrow + (a.W - c0) * 4);
+					if (lane < kHaloLanes)
+						dma4<0>(grow + halo_col, lrow + TW * 4);
+				};
+				if (kLdAux != 0 && (it < t_lo || it >= t_hi))
+					row_dma(std::integral_constant<int, 0>{});
+				else
+					row_dma(std::integral_constant<int, kLdAux>{});
+			} else
 			if (kLdAux != 0 && it < K + warm && A > 0) {
 #pragma unroll
 				for (int i = 0; i < CPT / 4; i++)
@@ -557,13 +601,16 @@ static __device__ __forceinline__ void fwd_sweep_tile(const FwdLevelArgs &a, con
 			else
 				vertical(ColTag<kColNone>{});
 		} else if constexpr (kIsSelEnds<W>) {
-			// step s acts on row 2q-1-s; where that row is an end of its column (wave-uniform, the top and bottom tiles'
-			// first / last iterations) the step's coefficient is doubled and its state tap -- the same values as the other
-			// tap there -- gives way to -0.0.  Deep ring: the iterations that meet no end take the plain body.
+			// step s acts on row 2q-1-s (an upward tile: 2q+1+s); where that row is an end of its column (wave-uniform, the top
+			// and bottom tiles' first / last iterations) the step's coefficient is doubled and its state tap -- the same values as
+			// the other tap there, in either direction -- gives way to -0.0.  Deep ring: the iterations that meet no end take the plain body.
 			bool ve[K], any = false;
 #pragma unroll
 			for (int s_ = 0; s_ < K; s_++) {
-				ve[s_] = row_is_end(2 * (q0 + it) - 1 - s_);
+				if constexpr (F01)
+					ve[s_] = row_is_end(row_of_step(it, s_));
+				else
+					ve[s_] = row_is_end(2 * (q0 + it) - 1 - s_);
 				any = any || ve[s_];
 			}
 			// (F01) the phantom column's pass: the main columns' steps on its one column, in the form they take this iteration
@@ -673,23 +720,29 @@ static __device__ __forceinline__ void fwd_sweep_tile(const FwdLevelArgs &a, con
 		if constexpr (F01) {
 			typedef float f2 __attribute__((ext_vector_type(2)));
 			const f2 nz = f2{-0.0f, -0.0f};
-			const int k = q0 + it - K / 2; // the pair of level 0 this iteration completes (k and `it` are both even or both odd)
+			// the pair of level 0 whose L row this iteration completes (downward q - 2, upward q + 2), and the one whose H row
+			// (downward the same pair, upward the pair below: q + 1)
+			const int k = q0 + dir * (it - K / 2), kh_ = k - up;
+			const unsigned clb = (unsigned)((c0 + lane * CPT) >> 1) * 4;
+			const unsigned nb0 = (unsigned)Wd * 4;
 			if (k >= A && k < B) {
-				const unsigned clb = (unsigned)((c0 + lane * CPT) >> 1) * 4;
-				const T *top = out_h + (long)k * a.h_pitch, *bot = out_h + (long)(Hd + k) * a.h_pitch;
-				const unsigned nb = (unsigned)Wd * 4;
-				store16_row<kNtStore>(row_rsrc(top + Wd, nb), clb, u4{to_bits(lo[1]), to_bits(lo[3]), to_bits(lo[5]), to_bits(lo[7])});
-				store16_row<kNtStore>(row_rsrc(bot, nb), clb, u4{to_bits(hi[0]), to_bits(hi[2]), to_bits(hi[4]), to_bits(hi[6])});
-				store16_row<kNtStore>(row_rsrc(bot + Wd, nb), clb, u4{to_bits(hi[1]), to_bits(hi[3]), to_bits(hi[5]), to_bits(hi[7])});
+				const T *top = out_h + (long)k * a.h_pitch;
+				store16_row<kNtStore>(row_rsrc(top + Wd, nb0), clb, u4{to_bits(lo[1]), to_bits(lo[3]), to_bits(lo[5]), to_bits(lo[7])});
 			}
-			if (it & 1) {
+			if (kh_ >= A && kh_ < B) {
+				const T *bot = out_h + (long)(Hd + kh_) * a.h_pitch;
+				store16_row<kNtStore>(row_rsrc(bot, nb0), clb, u4{to_bits(hi[0]), to_bits(hi[2]), to_bits(hi[4]), to_bits(hi[6])});
+				store16_row<kNtStore>(row_rsrc(bot + Wd, nb0), clb, u4{to_bits(hi[1]), to_bits(hi[3]), to_bits(hi[5]), to_bits(hi[7])});
+			}
+			if (k & 1) {
 				// LL row k, odd: waits for its pair
 #pragma unroll
 				for (int e = 0; e < 4; e++)
 					held[e] = lo[2 * e];
 				heldp = lop;
 			} else {
-				// level 1, iteration q1: its rows 2 q1 - 1 (held) and 2 q1 (this LL row), as the halves of packed operations
+				// level 1, iteration q1: its rows 2 q1 - 1 (held; an upward tile: 2 q1 + 1) and 2 q1 (this LL row), as the halves of
+				// packed operations
 				const int q1 = k >> 1, W1 = Wd, H1 = Hd;
 				f2 y[12];
 				const unsigned pb0 = to_bits(heldp), pb1 = to_bits(lop);
@@ -717,13 +770,16 @@ static __device__ __forceinline__ void fwd_sweep_tile(const FwdLevelArgs &a, con
 					}
 				}
 				const float ze = W::fwd_scale(0, 1.0f), zo = W::fwd_scale(1, 1.0f);
-				// vertical pass: step s acts on row 2 q1 - 1 - s; row 0 drops its older tap, row H1 - 1 its newer one
+				// vertical pass: step s acts on row 2 q1 - 1 - s (upward: 2 q1 + 1 + s).  An end row drops the tap that lies beyond the
+				// band -- what the sweep computes there mirrors level 0's input, not the band --: the end the march meets first
+				// (downward row 0, upward row H1 - 1) its older tap, the other end its newer one
 				bool vt[K], vb[K];
 				T kv[K];
+				const int r_old = up ? H1 - 1 : 0, r_new = up ? 0 : H1 - 1;
 #pragma unroll
 				for (int s_ = 0; s_ < K; s_++) {
-					vt[s_] = 2 * q1 - 1 - s_ == 0;
-					vb[s_] = 2 * q1 - 1 - s_ == H1 - 1;
+					vt[s_] = 2 * q1 - dir * (1 + s_) == r_old;
+					vb[s_] = 2 * q1 - dir * (1 + s_) == r_new;
 					kv[s_] = (vt[s_] || vb[s_]) ? 2.0f * W::fk(s_) : W::fk(s_);
 				}
 				auto older = [&](int s_, f2 v) { return vt[s_] ? nz : v; };
@@ -754,14 +810,18 @@ static __device__ __forceinline__ void fwd_sweep_tile(const FwdLevelArgs &a, con
 					hi1[v] = h2[0];
 					hi1[v + 2] = h2[1];
 				}
-				const int k1 = q1 - K / 2;
+				// level 1's Mallat rows in the LL quadrant of level 0: [LL | HL] at row k1, [LH | HH] at row H1 / 2 + k1h (an upward
+				// iteration completes the H row of the pair below its L row's, as level 0 does)
+				const int k1 = q1 - dir * (K / 2), k1h = k1 - up;
+				const int W2 = W1 >> 1, H2 = H1 >> 1;
+				const unsigned cb = (unsigned)((c0 >> 2) + lane * 2) * 4, nb = (unsigned)W2 * 4;
 				if (k1 >= (A >> 1) && k1 < (B >> 1)) {
-					// level 1's Mallat rows in the LL quadrant of level 0: [LL | HL] at row k1, [LH | HH] at row H1 / 2 + k1
-					const int W2 = W1 >> 1, H2 = H1 >> 1;
-					const unsigned cb = (unsigned)((c0 >> 2) + lane * 2) * 4, nb = (unsigned)W2 * 4;
-					const T *top = out_h + (long)k1 * a.h_pitch, *bot = out_h + (long)(H2 + k1) * a.h_pitch;
+					const T *top = out_h + (long)k1 * a.h_pitch;
 					store8_row<kNtStoreLL>(row_rsrc(out_ll + (long)k1 * a.ll_pitch, nb), cb, u2{to_bits(lo1[0]), to_bits(lo1[2])});
 					store8_row<kNtStore>(row_rsrc(top + W2, nb), cb, u2{to_bits(lo1[1]), to_bits(lo1[3])});
+				}
+				if (k1h >= (A >> 1) && k1h < (B >> 1)) {
+					const T *bot = out_h + (long)(H2 + k1h) * a.h_pitch;
 					store8_row<kNtStore>(row_rsrc(bot, nb), cb, u2{to_bits(hi1[0]), to_bits(hi1[2])});
 					store8_row<kNtStore>(row_rsrc(bot + W2, nb), cb, u2{to_bits(hi1[1]), to_bits(hi1[3])});
 				}
@@ -819,9 +879,9 @@ __global__ __launch_bounds__(256) void k_fwd_sweep(FwdLevelArgs a, SweepGeom g)
 // levels 0 and 1 of a float 9/7 transform in one sweep (fwd_sweep_tile, F01).  RING: the ring rows of a wave -- 16: one
 // workgroup of four waves per CU, one wave per SIMD; 8: built for two such workgroups per CU, two waves per SIMD
 template <int NT, int RING = 16>
-__global__ __launch_bounds__(256, RING == 16 ? 1 : 2) void k_fwd_sweep01(FwdLevelArgs a, SweepGeom g)
+__global__ __launch_bounds__(256, RING == 16 ? 1 : 2) void k_fwd_sweep01(FwdLevelArgs a, SweepGeom g, int updown)
 {
-	fwd_sweep_tile<SelEnds<Cdf97S>, 8, RING, NT, false, false, true, false>(a, g);
+	fwd_sweep_tile<SelEnds<Cdf97S>, 8, RING, NT, false, false, true, false>(a, g, updown);
 }
 
 // a level with a rectangle copy riding along: the workgroups behind the tiles' copy blocks of `r` (FwdLevelArgs::ride)
@@ -998,11 +1058,36 @@ bool fwd01_has_ring(int ring)
 // the whole 5-level call, 16 against 8 rows, one process, alternated, buffers placed by dwt_hip_alloc_batch: 64 x 8192^2
 // 6.77 -> 6.16 ms, 256 x 4096^2 6.81 -> 6.22 ms (the 16-row launches within 0.09 ms of each other); on plain allocations and
 // the two levels alone 6.87 -> 6.93 ms (a tie) and 6.99 -> 6.61 ms.  profiles/fuse01_ring_summary.md.
+// (the launches the pair engages in by itself: 32768 tiles of 64 pairs and more)
+static bool fwd01_large(int W, int H, int batch)
+{
+	return (long)fwd01_tiles(W) * (((H >> 1) + 63) / 64) * batch >= 32768;
+}
+
 static int fwd01_ring(const SweepTuning &t, int W, int H, int batch)
 {
 	if (t.fuse01_ring)
 		return t.fuse01_ring;
-	return (long)fwd01_tiles(W) * (((H >> 1) + 63) / 64) * batch >= 32768 ? 8 : 16;
+	return fwd01_large(W, H, batch) ? 8 : 16;
+}
+
+bool fwd01_has_updown(int v)
+{
+	return v >= -1 && v <= 2;
+}
+
+// Which tile rows of the fused pair's launch march upward: option fuse01_updown or the tuner's choice, else this rule: the odd
+// ones in the launches of 32768 tiles and more that run the 8-row ring (by the ring's rule or by option fuse01_ring), none in the
+// others -- smaller launches, the 16-row ring --, where nothing was measured.  A downward tile and the upward one below it (and the other way round) reach the 22 rows around their common
+// edge at the same time, so the second read of those rows -- 17 % of the launch's reads -- hits in L2: the fused launch of
+// the whole 5-level call, all downward against odd rows upward, one process, alternated, placed buffers: 64 x 8192^2
+// 6.10 -> 6.00 ms, 256 x 4096^2 6.24 -> 5.97 ms (the traffic probe ahead of it: 6.22 -> 6.00 and 6.22 -> 6.12 ms, FETCH_SIZE x 2
+// from 1.172 x to 1.050 x the input; profiles/fuse01_updown_summary.md).
+int fwd01_updown(const SweepTuning &t, int W, int H, int batch)
+{
+	if (t.fuse01_updown >= 0)
+		return t.fuse01_updown;
+	return fwd01_large(W, H, batch) && fwd01_ring(t, W, H, batch) == 8 ? 1 : 0;
 }
 
 hipError_t launch_fwd01(const FwdLevelArgs &a, const SweepTuning &t, hipStream_t s)
@@ -1010,7 +1095,7 @@ hipError_t launch_fwd01(const FwdLevelArgs &a, const SweepTuning &t, hipStream_t
 	if (!fwd01_can(kCdf97S, a.W, a.H) || a.batch < 1 || a.interleaved || a.ride || a.pair_hi > 0 || (t.tile_pairs & 1))
 		return hipErrorInvalidValue;
 	const int ring = fwd01_ring(t, a.W, a.H, a.batch);
-	if (!fwd01_has_ring(ring))
+	if (!fwd01_has_ring(ring) || !fwd01_has_updown(t.fuse01_updown))
 		return hipErrorInvalidValue;
 	const int waves = sweep_waves(t);
 	const int Hd = a.H >> 1;
@@ -1018,6 +1103,7 @@ hipError_t launch_fwd01(const FwdLevelArgs &a, const SweepTuning &t, hipStream_t
 	g.ntx = fwd01_tiles(a.W);
 	g.swz = t.xcd_swizzle;
 	g.wave_horiz = 1;
+	const int updown = fwd01_updown(t, a.W, a.H, a.batch);
 	g.tile_pairs = t.tile_pairs;
 	if (g.tile_pairs <= 0) {
 		// 7 iterations of a tile are level 1's warm-up: tall tiles, unless that leaves too few of them
@@ -1038,7 +1124,7 @@ hipError_t launch_fwd01(const FwdLevelArgs &a, const SweepTuning &t, hipStream_t
 	auto launch = [&](auto k) {
 		if (hipError_t e = allow_lds((const void *)k, lds))
 			return e;
-		k<<<grid, 64 * waves, lds, s>>>(a, g);
+		k<<<grid, 64 * waves, lds, s>>>(a, g, updown);
 		return hipGetLastError();
 	};
 	if (ring == 16)

@@ -57,6 +57,47 @@ static std::recursive_mutex &measure_mutex()
 	return per_device[g.device & 63];
 }
 
+// Times `n` candidates on the stream -- three launches each, the faster of the last two (the first one warms the caches it
+// can) -- and returns the index of the fastest one that ran, -1 if none did.  `launch(i)`: candidate i's launch; `name(i,
+// buf, n)`: its words for DWT_HIP_TUNE_VERBOSE.
+static int fastest_candidate(int n, const std::function<hipError_t(int)> &launch, const std::function<void(int, char *, size_t)> &name)
+{
+	std::lock_guard<std::recursive_mutex> turn(measure_mutex());
+	hipEvent_t e0, e1;
+	if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess)
+		return -1;
+	int best = -1;
+	float best_ms = 0;
+	static const bool verbose = getenv("DWT_HIP_TUNE_VERBOSE") != nullptr;
+	for (int i = 0; i < n; i++) {
+		float ms = 0;
+		bool ok = true;
+		for (int r = 0; r < 3 && ok; r++) {
+			float one = 0;
+			hipEventRecord(e0, g.stream);
+			ok = launch(i) == hipSuccess;
+			hipEventRecord(e1, g.stream);
+			g.stat_launches++;
+			ok = ok && hipEventSynchronize(e1) == hipSuccess && hipEventElapsedTime(&one, e0, e1) == hipSuccess;
+			if (r == 1 || (r == 2 && one < ms))
+				ms = one;
+		}
+		if (verbose) {
+			char what[96];
+			name(i, what, sizeof(what));
+			fprintf(stderr, "tune %s: %.1f us%s\n", what, ms * 1e3, ok ? "" : " (failed)");
+		}
+		if (ok && (best < 0 || ms < best_ms)) {
+			best = i;
+			best_ms = ms;
+		}
+	}
+	hipEventDestroy(e0);
+	hipEventDestroy(e1);
+	(void)hipGetLastError();
+	return best;
+}
+
 static int tune_tile_pairs(unsigned long long key, TileUse use, std::initializer_list<TileCand> cands, const std::function<hipError_t(const SweepTuning &)> &launch)
 {
 	auto it = g.tile_cache.find(key);
@@ -64,14 +105,7 @@ static int tune_tile_pairs(unsigned long long key, TileUse use, std::initializer
 		return it->second;
 	if (!may_measure() || g.placing || stream_is_capturing())
 		return 0; // the launcher's rule; decided by dwt_hip_tune
-	std::lock_guard<std::recursive_mutex> turn(measure_mutex());
-	hipEvent_t e0, e1;
-	if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess)
-		return 0;
-	int best = 0;
-	float best_ms = 0;
-	static const bool verbose = getenv("DWT_HIP_TUNE_VERBOSE") != nullptr;
-	std::vector<int> tried;
+	std::vector<TileCand> todo;
 	for (TileCand c : cands) {
 		if (c.cpt && g.tune.cpt)
 			continue; // a width set by hand stands
@@ -82,35 +116,20 @@ static int tune_tile_pairs(unsigned long long key, TileUse use, std::initializer
 				continue;
 			c.ring = 0;
 		}
-		if (std::find(tried.begin(), tried.end(), pack_choice(c)) != tried.end())
-			continue;
-		tried.push_back(pack_choice(c));
-		SweepTuning t = g.tune;
-		apply_tile_choice(pack_choice(c), &t, use);
-		// three launches, the faster of the last two (the first one warms the caches it can)
-		float ms = 0;
-		bool ok = true;
-		for (int r = 0; r < 3 && ok; r++) {
-			float one = 0;
-			hipEventRecord(e0, g.stream);
-			ok = launch(t) == hipSuccess;
-			hipEventRecord(e1, g.stream);
-			g.stat_launches++;
-			ok = ok && hipEventSynchronize(e1) == hipSuccess && hipEventElapsedTime(&one, e0, e1) == hipSuccess;
-			if (r == 1 || (r == 2 && one < ms))
-				ms = one;
-		}
-		if (verbose)
-			fprintf(stderr, "tune %s W %d: %d pairs, cpt %d, ring %d: %.1f us%s\n", use == kTileInv ? "inv" : use == kTileFwd01 ? "fwd01" : "fwd", (int)((key >> 38) & 0xfffff), c.pairs, c.cpt, c.ring,
-				ms * 1e3, ok ? "" : " (failed)");
-		if (ok && (!best || ms < best_ms)) {
-			best = pack_choice(c);
-			best_ms = ms;
-		}
+		if (std::find_if(todo.begin(), todo.end(), [&](const TileCand &d) { return pack_choice(d) == pack_choice(c); }) == todo.end())
+			todo.push_back(c);
 	}
-	hipEventDestroy(e0);
-	hipEventDestroy(e1);
-	(void)hipGetLastError();
+	const int i = fastest_candidate((int)todo.size(),
+		[&](int k) {
+			SweepTuning t = g.tune;
+			apply_tile_choice(pack_choice(todo[k]), &t, use);
+			return launch(t);
+		},
+		[&](int k, char *buf, size_t n) {
+			snprintf(buf, n, "%s W %d: %d pairs, cpt %d, ring %d", use == kTileInv ? "inv" : use == kTileFwd01 ? "fwd01" : "fwd", (int)((key >> 38) & 0xfffff),
+				todo[k].pairs, todo[k].cpt, todo[k].ring);
+		});
+	const int best = i < 0 ? 0 : pack_choice(todo[i]);
 	g.tile_cache[key] = best;
 	return best;
 }
@@ -152,6 +171,30 @@ int tuned_tile_pairs01(Wavelet w, const FwdLevelArgs &a)
 		return 0;
 	return tune_tile_pairs(tile_key(w, false, a.W, a.H, a.batch) ^ (1ull << 63), kTileFwd01, {{64, 0, 8}, {128, 0, 8}, {32, 0, 8}, {64, 0, 16}, {128, 0, 16}, {32, 0, 16}},
 		[&](const SweepTuning &t) { return launch_fwd01(a, t, g.stream); });
+}
+
+// The direction of the fused pair's tile rows (option fuse01_updown; one set by hand stands), timed at the height and depth
+// ranked first (`t`): every tile row downward against the odd ones upward (fastest_candidate).
+// Kept under a key of its own as direction + 1; -1: nothing measured, the launcher's rule.
+int tuned_updown01(Wavelet w, const FwdLevelArgs &a, const SweepTuning &t)
+{
+	if (t.fuse01_updown >= 0 || !tunable(a.W, a.H, a.batch, a.interleaved))
+		return -1;
+	const unsigned long long key = tile_key(w, false, a.W, a.H, a.batch) ^ (3ull << 62);
+	auto it = g.tile_cache.find(key);
+	if (it != g.tile_cache.end())
+		return it->second - 1;
+	if (!may_measure() || g.placing || stream_is_capturing())
+		return -1;
+	const int best = fastest_candidate(2,
+		[&](int dir) {
+			SweepTuning td = t;
+			td.fuse01_updown = dir;
+			return launch_fwd01(a, td, g.stream);
+		},
+		[&](int dir, char *buf, size_t n) { snprintf(buf, n, "fwd01 W %d: %s", a.W, dir ? "odd tile rows upward" : "every tile row downward"); });
+	g.tile_cache[key] = best + 1;
+	return best;
 }
 
 // the inverse levels alike (32 images of 8192^2: 16 pairs 520 against 507-510 Gsamples/s with the rule's 32)
