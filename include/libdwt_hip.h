@@ -969,6 +969,84 @@ int dwt_hip_codeblock_bitplanes_batch(int index_type, const void *index, size_t 
 	int batch, int size_x, int size_y, int j_max, int cb_log2_x, int cb_log2_y, unsigned char *planes,
 	size_t planes_frame_stride);
 
+/* Sparse coefficient streams: the nonzero elements of coefficient or index planes packed on the device
+ * into (position, value) pairs in a fixed order, and scattered back.  What keep_largest_batch and quantize_batch leave is
+ * almost all zeros; a coder, a store or a peer on the host wants the nonzeros, and only they need to cross PCIe.  An
+ * extension: the reference has nothing of the kind; this comment is the specification (tests/sparse_model.py restates it
+ * in numpy, the device is held to it bit for bit -- there is no arithmetic and no tolerance).
+ *
+ * Frames.  `batch` dense Mallat frames of size_x x size_y elements of `type` (DWT_HIP_SPARSE_F32, _F16, _I16, _I32; 4, 2,
+ * 2, 4 bytes), element (x, y) of frame b at planes + b*batch_stride + y*row_pitch + x*(element size) bytes; J =
+ * dwt_hip_band_levels(size_x, size_y, j_max) levels and the 3J + 1 slots of dwt_hip_band_geometry, j_max as the band
+ * operators take it.
+ *
+ * Kept elements.  An integer element is kept when it is not 0 (INT16_MIN and INT32_MIN are kept).  A float element is
+ * kept when its bits with the sign bit cleared are not 0: NaN, Inf and subnormals are kept with their bits; +0.0 and -0.0
+ * are dropped.  Unpack writes zero BITS where there is no entry, so a -0.0 comes back as +0.0: the one place where a
+ * round trip changes bits.
+ *
+ * Stream order (resolution order).  Bands coarse to fine: slot 3J (LL) first, then the three slots of level J in slot
+ * order (HL, LH, HH), then level J-1, ... down to level 1; inside a band raster order, rows top to bottom, each row left
+ * to right.  Empty bands contribute nothing.  A prefix of a stream is a coarser picture.  dwt_hip_sparse_order (host
+ * code, no device) stores the 3*levels + 1 slot numbers in stream order and returns their count (-1: levels outside
+ * 0 .. 31 or a null pointer).
+ *
+ * An entry is a position and a value in two separate dense arrays: pos[i] = y*size_x + x, a uint32 in frame coordinates
+ * whatever the pitch; val[i] the element's own bits, in the source type.  Frame b's entries start at element
+ * b*stream_stride of each array; stream_stride is the per-frame capacity in entries.  A frame with more kept elements
+ * than stream_stride gets its FIRST stream_stride entries in stream order; the others are not written.  That is no error:
+ * a call on device memory does not wait for the device.
+ * Offsets: uint32, 3J + 2 per frame, frame b's at offsets + b*(3J + 2): off[k] the number of entries in front of stream
+ * band k (k in stream order), off[3J + 1] the frame's total -- always the true counts, whatever the capacity.
+ *
+ * dwt_hip_sparse_pack_batch.  pos == NULL && val == NULL (stream_stride ignored): count only, the sizing call.  `planes`
+ * is only read.  Entries behind a frame's total, and the bytes between the frames' entries, are left alone.
+ * dwt_hip_sparse_unpack_batch writes EVERY own element of every frame: the entry's value where there is one, zero bits
+ * elsewhere; the bytes between a row's end and its pitch and between the frames are left alone.  Frame b has
+ * min(counts[b*counts_stride], stream_stride) entries (counts: uint32; offsets + 3J + 1 with counts_stride 3J + 2 reads
+ * pack's totals where they lie).  An entry whose pos >= size_x*size_y is skipped and never written.  The streams pack
+ * produces hold no position twice; for a foreign stream that does, which entry wins is unspecified.
+ *
+ * Memory.  Three sides -- the planes, the stream (pos and val), the offsets / counts -- each in host or in device memory
+ * on its own.  Device sides are ordered on the context's stream; with all three on the device no call waits for the
+ * device, and after the first call of a size none allocates.  A host side is mirrored in scratch of the context (a
+ * written region is uploaded first, so that the bytes the call leaves alone come back as they were) and the call ends
+ * synchronised.
+ * Kernels.  Pack is THREE launches whatever the batch, the shape and the density: the frames are cut into tiles of
+ * DWT_HIP_SPARSE_TILE_SAMPLES consecutive samples of one band's raster order, enumerated in stream order
+ * (dwt_hip_sparse_bands / _tile below); launch 1 counts every tile's kept elements, launch 2 -- one workgroup per frame --
+ * turns the counts into the tiles' first entries and the frame's offsets, launch 3 reads the tiles again and writes every
+ * entry at its tile's base plus its rank in the tile.  Count only is launches 1 and 2.  Unpack is TWO launches: the zero
+ * fill, the scatter.  The order is fixed by construction: no atomics, no workgroup waits for another.  A lane reads runs
+ * of 16 / (element size) consecutive samples of a row, by one 16-byte access where the planes' base, row pitch and batch
+ * stride are multiples of 16 bytes and the run lies inside the row, element by element elsewhere (option "sparse_wide" =
+ * 0: everywhere); same bits.  dwt_hip_sparse_route: 1 where a call with these addresses takes the 16-byte route, 0 where
+ * not, -1 for arguments the entries refuse (it holds for device planes; host planes run on their aligned mirror).
+ * batch == 0 launches nothing and writes nothing; frames without elements launch nothing, their offsets are written as
+ * zeros.
+ * Errors (nonzero, dwt_hip_last_error, nothing launched, nothing written): a null pointer other than the count-only pair,
+ * val without pos or pos without val, an unknown type, negative sizes, size_x*size_y > INT_MAX, a pitch below its row,
+ * frames closer than they span, addresses or strides that are no multiple of the element size (4 for pos, offsets and
+ * counts), regions that share a byte (the planes with the stream, the offsets or the counts; the stream's arrays and the
+ * offsets with each other).
+ *
+ * dwt_hip_sparse_bands (host code): {x, y, size_x, size_y, first tile} of every band in STREAM order -> table, five ints
+ * per band, and one more row {0, 0, 0, 0, tiles of a frame}; 5 * (3J + 2) ints in all.  Returns 3J + 1, -1 for sizes the
+ * entries refuse.  dwt_hip_sparse_tile: tile `tile` of that table -> its band (stream order), its first sample in the
+ * band's raster order and its sample count; 0, or -1 for a tile the table does not hold. */
+enum dwt_hip_sparse_type { DWT_HIP_SPARSE_F32 = 0, DWT_HIP_SPARSE_F16 = 1, DWT_HIP_SPARSE_I16 = 2, DWT_HIP_SPARSE_I32 = 3 };
+#define DWT_HIP_SPARSE_TILE_SAMPLES 2048 /* samples of a tile */
+#define DWT_HIP_SPARSE_GRID_TILES 4096 /* tiles / frames one trip of the kernels' loops covers */
+#define DWT_HIP_SPARSE_GRID_BATCH 4096
+int dwt_hip_sparse_order(int levels, int *slots);
+int dwt_hip_sparse_bands(int size_x, int size_y, int j_max, int *table);
+int dwt_hip_sparse_tile(const int *table, int bands, int tile, int *band, int *start, int *count);
+int dwt_hip_sparse_pack_batch(int type, const void *planes, size_t batch_stride, size_t row_pitch, int batch, int size_x, int size_y,
+	int j_max, unsigned *pos, void *val, size_t stream_stride, unsigned *offsets);
+int dwt_hip_sparse_unpack_batch(int type, const unsigned *pos, const void *val, size_t stream_stride, const unsigned *counts,
+	size_t counts_stride, void *planes, size_t batch_stride, size_t row_pitch, int batch, int size_x, int size_y);
+int dwt_hip_sparse_route(int type, const void *planes, size_t batch_stride, size_t row_pitch, int batch, int size_x, int size_y);
+
 /* Time-frequency planes of line batches: the Gaussian-window STFT, the complex Morlet CWT and the S transform of
  * src/gabor.c (gabor_ft_s, gabor_wt_s, gabor_st_s and their _arg_ twins; include/gabor.h), DESIGN.md s14.
  *

@@ -639,6 +639,44 @@ struct CodeblockArgs {
 };
 hipError_t launch_codeblock_bitplanes(int index, const CodeblockArgs &a, hipStream_t s);
 
+// Sparse coefficient streams (dwt_sparse.hip): the kept elements of dense Mallat frames as (position,
+// value) entries in stream order, and back.  Element (x, y) of frame b at planes + b*bs + y*pitch + x*es bytes.  A frame is
+// cut into tiles of SPARSE_TILE_SAMPLES consecutive samples of one band's raster order, enumerated in stream order
+// (dwt_sparse_geom.c); the band table rides in the kernel arguments.
+constexpr int SPARSE_TILE_SAMPLES = 2048;
+constexpr int SPARSE_GRID_TILES = 4096; // tiles one trip of the tile loop covers (grid.x); the scatter's workgroups alike
+constexpr int SPARSE_GRID_BATCH = 4096; // frames one trip of the batch loop covers (grid.y)
+struct SparseArgs {
+	const char *planes;
+	long pitch, bs;
+	int batch, W, H;
+	int bands, tiles;   // 3J + 1 bands in stream order; tiles of one frame
+	unsigned keep_mask; // an element is kept when (bits & keep_mask) != 0: everything but a float's sign bit
+	int wide;           // base, pitch and batch stride are multiples of 16 bytes
+	int x0[BAND_MAX_SLOTS], y0[BAND_MAX_SLOTS], w[BAND_MAX_SLOTS], h[BAND_MAX_SLOTS];
+	int first[BAND_MAX_SLOTS + 1]; // prefix of the bands' tile counts
+	unsigned *tile;               // [batch][tiles]: launch 1 the tiles' counts, launch 2 the tiles' first entries
+	unsigned *pos;                 // frame b's entries from b * stream_stride on
+	char *val;
+	unsigned long long stream_stride;
+	unsigned *offsets; // [batch][bands + 1]
+};
+hipError_t launch_sparse_tiles(int es, bool pack, const SparseArgs &a, hipStream_t s); // launch 1 / launch 3
+hipError_t launch_sparse_scan(const SparseArgs &a, hipStream_t s);                     // launch 2
+struct SparseUnpackArgs {
+	char *planes;
+	long pitch, bs;
+	int batch, W, H;
+	int wide, nt; // 16-byte stores; non-temporal ones
+	const unsigned *pos;
+	const char *val;
+	unsigned long long stream_stride;
+	const unsigned *counts;
+	long counts_stride; // in words
+};
+hipError_t launch_sparse_zero(int es, const SparseUnpackArgs &a, hipStream_t s);
+hipError_t launch_sparse_scatter(int es, const SparseUnpackArgs &a, hipStream_t s);
+
 // N-term approximation (dwt_nterm.hip): keep the coefficients of the n largest magnitudes of every group
 // of 1 .. 4 dense frames, zero the rest.  The key of a position is the uint32 image of its float magnitude (sign bit 0:
 // unsigned order is float order); a radix select over 11 + 10 + 10 bits finds the key of descending rank n, one
