@@ -168,6 +168,12 @@ void dwt_hip_alloc_batch_report(int *chunks, int *dst_tried, int *ll_tried, int 
  * levels of 64 x 64 or more: levels 0 and 1 in ONE launch, level 0's LL band never written --
  * 1 = where that pays (launches of 32768 tiles of 512 columns x 64 row pairs and more: 32 images of 8192^2, 128 of 4096^2), 0 = never, 2 = wherever
  * the geometry is legal, for tests; same bits; not with "fma", "cpt" 4, "ring" 8, "nt" 15 or an odd "tile_pairs"),
+ * "fuse_deep" (the same launch for levels 2 and 3, 4 and 5 ... of such a call, each pair from one LL scratch band to the other:
+ * 1 = where that pays -- in calls whose levels 0 and 1 ran in one launch by the size rule above, in launches of 2048 tiles of
+ * 512 columns x 64 row pairs and more (level 2 of 32 images of 8192^2), then with the 8-row ring, the odd tile rows upward and
+ * 128 row pairs unless set by hand or measured by dwt_hip_tune --, 0 = never, 2 = wherever the geometry of the pair's first
+ * level is legal, for tests; same bits, the same workspace; dwt_hip_get_option("fuse_deep_last") reads how many such pairs the
+ * last forward call launched),
  * "fuse01_ring" (the LDS ring rows per wave of that one launch: 16 = one workgroup of four waves per CU, 8 = two of them, two
  * waves per SIMD; 0 = the launcher's rule -- 8 from 32768 tiles on, else 16 -- or what dwt_hip_tune measured; any other value is
  * refused; same bits),
@@ -189,7 +195,8 @@ void dwt_hip_alloc_batch_report(int *chunks, int *dst_tried, int *ll_tried, int 
  * default: DWT_HIP_TUNE), "place_tries" / "place_min_mib" (placement search, below), "place_max_gib" (cap of the
  * arena dwt_hip_alloc_batch / _volumes map for their search; 0 = free memory - 8 GiB).
  * Read-only: "stat_launches" / "stat_allocs" (kernel launches / device allocations of this context's 2-D drivers
- * so far), "tile_cache_size", "place_last_tries", "place_last_best".
+ * so far), "tile_cache_size", "place_last_tries", "place_last_best", "fuse01_last_choice", "fuse01_last_updown",
+ * "fuse_deep_last".
  * 3-D: "vol_fused" (1 = one-pass levels where they pay, 2 = wherever they can run, 0 = two passes),
  * "vol_whole" (0 = the general kernel variant as a cross-check), "vol_direct" (levels >= 1 into their lattice
  * of the destination: 2 = rows shared by levels 0 and 1 written once, 1 = sample-wise stores, 0 = dense

@@ -21,7 +21,7 @@ const Opt kOpts[] = {
 	DWT_OPT("generic", force_generic, kSweep), DWT_OPT("eaw_two_pass", eaw_two_pass, kBool), DWT_OPT("feat_groups", feat_groups, kNonNegative), DWT_OPT("swt_fused", swt_fused, kBool), DWT_OPT("swt2d_fused", swt2d_fused, kBool), DWT_OPT("wp_fused", wp_fused, kBool), DWT_OPT("pixels_wide", pixels_wide, kBool), DWT_OPT("quant_wide", quant_wide, kBool), DWT_OPT("sparse_wide", sparse_wide, kBool), DWT_OPT("window_fused", window_fused, kNonNegative), DWT_OPT("cond_fused", cond_fused, kPlain), DWT_OPT("timefreq_tiled", tf_tiled, kBool), DWT_OPT("cpt", tune.cpt, kSweep), DWT_OPT("tile_pairs", tune.tile_pairs, kSweep),
 	DWT_OPT("waves", tune.waves, kSweep), DWT_OPT("xcd_swizzle", tune.xcd_swizzle, kSweep), DWT_OPT("ring", tune.ring, kSweep),
 	DWT_OPT("ring_inv", tune.ring_inv, kSweep), DWT_OPT("inv_ll_temporal", tune.inv_ll_temporal, kSweep), DWT_OPT("inv_pairs", tune.inv_pairs, kSweep), DWT_OPT("nt", tune.nt, kSweep), DWT_OPT("nt_auto", tune.nt_auto, kSweep),
-	DWT_OPT("fma", fma, kSweep), DWT_OPT("fused_d", fused_d, kPlain), DWT_OPT("fuse01", fuse01, kPlain), DWT_OPT("fuse01_ring", tune.fuse01_ring, kRing01), DWT_OPT("fuse01_updown", tune.fuse01_updown, kUpDown01), DWT_OPT("ride_copy", ride_copy, kBool), DWT_OPT("ride_mib", ride_mib, kNonNegative), DWT_OPT("il_exact_borders", il_exact_borders, kPlain),
+	DWT_OPT("fma", fma, kSweep), DWT_OPT("fused_d", fused_d, kPlain), DWT_OPT("fuse01", fuse01, kPlain), DWT_OPT("fuse_deep", fuse_deep, kNonNegative), DWT_OPT("fuse01_ring", tune.fuse01_ring, kRing01), DWT_OPT("fuse01_updown", tune.fuse01_updown, kUpDown01), DWT_OPT("ride_copy", ride_copy, kBool), DWT_OPT("ride_mib", ride_mib, kNonNegative), DWT_OPT("il_exact_borders", il_exact_borders, kPlain),
 	DWT_OPT("il_inplace_shell", il_inplace_shell, kPlain), DWT_OPT("host_pipeline", host_pipeline, kPlain),
 	DWT_OPT("tune_tiles", tune_tiles, kPlain), DWT_OPT("tune_in_call", tune_in_call, kBool), DWT_OPT("place_tries", place_tries, kPlain),
 	DWT_OPT("place_min_mib", place_min_mib, kNonNegative), DWT_OPT("place_max_gib", place_max_gib, kNonNegative),
@@ -264,6 +264,8 @@ int dwt_hip_get_option(const char *name)
 		return g.stat_choice01;
 	if (!strcmp(name, "fuse01_last_updown")) // the tile rows that marched upward in the last fused pair's launch: 0 none, 1 odd, 2 even
 		return g.stat_updown01;
+	if (!strcmp(name, "fuse_deep_last")) // the pairs below level 1 (levels 2 + 3, 4 + 5 ...) that the last forward call launched
+		return g.stat_deep_pairs;
 	const Opt *o = find_opt(name);
 	return o ? *o->ref(g) : -1;
 }

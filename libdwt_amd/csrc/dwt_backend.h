@@ -115,6 +115,8 @@ struct Ctx {
 	int place_n = 0, place_best = -1;
 	int fused_d = 1; // double-precision wavelets through the fused sweeps (0: exact line passes only)
 	int fuse01 = 1;  // forward float 9/7, out of place: levels 0 and 1 in one launch -- 1 where it pays, 2 wherever it can run, 0 never (pair01_ok)
+	int fuse_deep = 1; // ... and levels (2, 3), (4, 5) ... of the same calls from scratch, one launch each -- 1 where it pays, 2 wherever it can run, 0 never (pair_deep_ok)
+	int stat_deep_pairs = 0; // the pairs below level 1 that the last forward call launched (tests)
 	int ride_copy = 1; // in-place calls on one image: the staged subbands' copy rides along with the deeper levels' launches (0: a launch of its own)
 	int ride_mib = 32; // ... MiB of it per small level (8192^2: 8 / 16 / 24 / 32 / 48 MiB: forward 202 / 202 / 199 / 199 / 199 us, inverse 224 / 227 / 225 / 224 / 229)
 	// profiling

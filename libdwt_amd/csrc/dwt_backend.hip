@@ -11,7 +11,7 @@
 //     level j : scratch[(j-1)&1] -> HL/LH/HH at their final place, LL -> scratch[j&1]
 //     last    :                     LL -> its final place too
 //   (large out-of-place float 9/7 calls: levels 0 and 1 in one launch, image -> both levels' HL/LH/HH, LL -> scratch1;
-//    pair01_ok below)
+//    pair01_ok below -- and levels 2 and 3, 4 and 5 ... of those calls likewise, scratch to scratch: pair_deep_ok)
 //
 // Every level therefore reads its input once and writes its output once: the
 // algorithmic traffic 2*sizeof(T)*sum_j(W_j*H_j).  Only when the caller's source
@@ -294,18 +294,53 @@ bool level_fused_ok(const Call2d &c, const Geom &ge, int j)
 //     to win at (profiles/fuse01_summary.md, profiles/fuse01_seams_summary.md).  Below 3072 tiles level 0 does not take
 //     the deep ring itself -- a round or two of waves wants the shallow ring's 8 waves per CU --; in between nothing was
 //     measured, and a call on 16 images of 8192^2 is held to one launch per level (tests/test_hip_multi.py).
-static bool pair01_ok(const Call2d &c, const Geom &ge, int J, int batch)
+//
+// The same launch takes levels (j, j + 1) at any even j: the kernel reads `in` and addresses both levels' detail quadrants
+// from the image's top left corner, and nothing in it knows its level.  A deeper pair reads the running band from one scratch
+// band and leaves level j + 1's in the other (or in the image when it is the last), greedy from the top: (0, 1), (2, 3),
+// (4, 5) ...; a level left over runs alone.  What a pair at j needs is what the pair at 0 needs, of level j: pair_legal.
+// Option fuse_deep for j >= 2: 0 never, 2 wherever legal, 1 (default) where it was measured to pay
+// (profiles/fuse_deep_summary.md): only in a call whose levels 0 and 1 engaged by their size rule -- so 16 images of 8192^2,
+// every single image and every small call stay at one launch per level --, and only in launches of kDeepTiles tiles of 512
+// columns x 64 pairs and more, the smallest launch the measurement covers and a winner already: levels 2 + 3 against the pair,
+// the whole 5-level call tuned by dwt_hip_tune, one process, alternated, placed buffers: 64 x 8192^2 (4096 tiles) 534 -> 381 us,
+// 256 x 4096^2 (4096 tiles) 478 -> 367 us, 32 x 8192^2 (2048 tiles) 277 -> 223 us, the spread of the two launches 5 us.
+static long pair_tiles(const Geom &ge, int j, int batch)
 {
-	const int W = ge.Wo(0), H = ge.Ho(0);
-	if (!g.fuse01 || g.fma || J < 2 || !level_fused_ok(c, ge, 0) || !level_fused_ok(c, ge, 1) || !fwd01_can(c.w, W, H))
+	return (long)fwd01_tiles(ge.Wo(j)) * (((ge.Ho(j) >> 1) + 63) / 64) * batch;
+}
+
+static bool pair_legal(const Call2d &c, const Geom &ge, int J, int j)
+{
+	if ((j & 1) || g.fma || j + 1 >= J || !level_fused_ok(c, ge, j) || !level_fused_ok(c, ge, j + 1) || !fwd01_can(c.w, ge.Wo(j), ge.Ho(j)))
 		return false;
 	const SweepTuning &t = g.tune;
-	if (t.cpt == 4 || t.ring == 8 || (t.nt & 8) || (t.tile_pairs & 1))
+	return !(t.cpt == 4 || t.ring == 8 || (t.nt & 8) || (t.tile_pairs & 1));
+}
+
+// levels 0 and 1; *by_size: the pair engages by the size rule (whatever fuse01 = 2 adds)
+static bool pair01_ok(const Call2d &c, const Geom &ge, int J, int batch, bool *by_size)
+{
+	*by_size = g.fuse01 && pair_legal(c, ge, J, 0) && pair_tiles(ge, 0, batch) >= 32768;
+	return *by_size || (g.fuse01 >= 2 && pair_legal(c, ge, J, 0));
+}
+
+// levels (j, j + 1), j >= 2; pair01_by_size: this call's levels 0 and 1 ran as a pair, by the size rule
+constexpr long kDeepTiles = 2048;
+// The ring rows, the direction and the tile height of a deeper pair's launch of kDeepTiles tiles and more, where they are
+// neither set by hand nor measured by dwt_hip_tune (below that size: the launcher's rule for small launches, as for the pair
+// at 0): the 8-row ring, odd tile rows upward, 128 row pairs where that leaves two tile rows or more.  Rings 8 / 16 x every
+// row downward / odd rows upward x 32 / 64 / 128 pairs on the three launches above, untuned: this one is first on the two of
+// 4096 tiles -- 128 pairs make them ONE round of the 2048 resident waves -- (381 and 367 us; at 64 pairs 428 and 407, the 16-row
+// ring at its best 417 and 413, every row downward 430 and 372) and within 7 % of the first on 32 x 8192^2 (224 us against 209
+// for the 16-row ring at 128 pairs: half a round either way).  The launcher's rule for this size (16 rows, downward, 64 pairs):
+// 518, 475 and 270 us.  profiles/fuse_deep_summary.md.
+constexpr int kDeepRing = 8, kDeepUpDown = 1, kDeepPairs = 128;
+static bool pair_deep_ok(const Call2d &c, const Geom &ge, int J, int batch, int j, bool pair01_by_size)
+{
+	if (!g.fuse_deep || j < 2 || !pair_legal(c, ge, J, j))
 		return false;
-	if (g.fuse01 >= 2)
-		return true;
-	const long ntx = fwd01_tiles(W), nty = ((H >> 1) + 63) / 64;
-	return ntx * nty * batch >= 32768;
+	return g.fuse_deep >= 2 || (pair01_by_size && pair_tiles(ge, j, batch) >= kDeepTiles);
 }
 
 // ---- the line-pass route of the float 9/7 on binary16 storage (kCdf97H) ----------------
@@ -403,6 +438,8 @@ int forward2d(const Call2d &c, Img src, Img dst, const Geom &ge, int *jp, int de
 	int ll_in = -1;
 	Img cur = src;
 	RideCopy ride;
+	bool pair01_by_size = false; // levels 0 and 1 ran as a pair by the size rule: what the deeper pairs' own rule asks first
+	g.stat_deep_pairs = 0;
 	// the fused levels from j on that can carry copy blocks (one image, a sweep variant with the ride-along kernel)
 	auto carriers_from = [&](int j0) {
 		int n = 0;
@@ -414,8 +451,15 @@ int forward2d(const Call2d &c, Img src, Img dst, const Geom &ge, int *jp, int de
 		const int Wo = ge.Wo(j), Ho = ge.Ho(j), Wi = ge.Wi(j), Hi = ge.Hi(j);
 		const int Wd = ge.Wo(j + 1), Hd = ge.Ho(j + 1);
 		if (level_fused_ok(c, ge, j)) {
-			// (a fused pair: levels 0 and 1 of an out-of-place call; jl: the level whose LL band leaves the launch)
-			const bool pair = j == 0 && ll_in < 0 && cur.p != dst.p && pair01_ok(c, ge, J, batch);
+			// (a fused pair: levels 0 and 1 of an out-of-place call, or levels (j, j + 1) from scratch while no copy waits for a
+			// launch to ride along with; jl: the level whose LL band leaves the launch)
+			bool by_size = false;
+			const bool pair = j == 0 ? ll_in < 0 && cur.p != dst.p && pair01_ok(c, ge, J, batch, &by_size)
+			                         : ll_in >= 0 && !(ride.on && ride.next < ride.total) && pair_deep_ok(c, ge, J, batch, j, pair01_by_size);
+			if (j == 0)
+				pair01_by_size = pair && by_size;
+			else if (pair)
+				g.stat_deep_pairs++;
 			const int jl = pair ? j + 1 : j;
 			const bool last = (jl == J - 1) || !level_fused_ok(c, ge, jl + 1);
 			FwdLevelArgs a;
@@ -451,7 +495,8 @@ int forward2d(const Call2d &c, Img src, Img dst, const Geom &ge, int *jp, int de
 			a.h_pitch = hdst.sx / es;
 			a.h_bstride = h_bstride / es;
 			// ping-pong: the other buffer than the one read; band j+1 fits either for j >= 1.  A fused pair writes level 1's
-			// band where the two launches would have left it, in scratch 1 (scratch 0 is sized for level 0's band, unused then)
+			// band where the two launches would have left it, in scratch 1 (scratch 0 is sized for level 0's band, unused then);
+			// a deeper pair reads one scratch band and writes the other, which holds any band below level 1's
 			const int ll_out = last ? -1 : (ll_in < 0 ? (jl & 1) : 1 - ll_in);
 			if (last) {
 				a.out_ll = hdst.p;
@@ -463,20 +508,30 @@ int forward2d(const Call2d &c, Img src, Img dst, const Geom &ge, int *jp, int de
 				a.ll_bstride = a.ll_pitch * ge.Ho(jl + 1);
 			}
 			SweepTuning tune = g.tune;
-			if (pair)
+			if (pair && j == 0)
 				g.stat_choice01 = 0;
+			// (a deeper pair of the size its rule engages it at: ring, direction and height by that rule (kDeepRing ...) unless set
+			// by hand or measured -- the launcher's rule for launches of this size is that of the small forced pairs)
+			const bool deep_rule = pair && j > 0 && pair_tiles(ge, j, batch) >= kDeepTiles;
+			if (deep_rule && !tune.fuse01_ring)
+				tune.fuse01_ring = kDeepRing;
 			if (es == 4 && tune.tile_pairs <= 0) {
 				const int choice = pair ? tuned_tile_pairs01(w, a) : tuned_tile_pairs(w, a); // (0, nothing measured: the launcher's own rule)
 				apply_tile_choice(choice, &tune, pair ? kTileFwd01 : kTileFwd);
-				if (pair)
+				if (pair && j == 0)
 					g.stat_choice01 = choice;
+				if (deep_rule && choice <= 0 && (Ho >> 1) >= 2 * kDeepPairs)
+					tune.tile_pairs = kDeepPairs;
 			}
 			if (pair) {
 				// the direction of the tile rows: the option, else what dwt_hip_tune measured at this height and depth, else the rule
 				const int dir = tuned_updown01(w, a, tune);
 				if (dir >= 0)
 					tune.fuse01_updown = dir;
-				g.stat_updown01 = fwd01_updown(tune, a.W, a.H, a.batch);
+				else if (deep_rule && tune.fuse01_updown < 0)
+					tune.fuse01_updown = kDeepUpDown;
+				if (j == 0)
+					g.stat_updown01 = fwd01_updown(tune, a.W, a.H, a.batch);
 			}
 			if (ride.on && ride.next < ride.total && es == 4 && sweep_ride_ok(tune, Wo, Ho, batch, false)) {
 				a.ride = &ride.r;
