@@ -1054,6 +1054,98 @@ int dwt_hip_sparse_unpack_batch(int type, const unsigned *pos, const void *val, 
 	size_t counts_stride, void *planes, size_t batch_stride, size_t row_pitch, int batch, int size_x, int size_y);
 int dwt_hip_sparse_route(int type, const void *planes, size_t batch_stride, size_t row_pitch, int batch, int size_x, int size_y);
 
+/* User-defined lifting wavelets: a multi-level Mallat transform of a batch of dense frames by a lifting
+ * scheme that the CALLER describes in a small table -- Haar, Daubechies D4, 13/7, 2/6, the S transform, a filter of one's
+ * own --, binary32 or reversible int32.  An extension: the reference has Haar and D4 as cores only (examples/cores/
+ * cores-haar.c, cores-d4.c); this comment is the specification, tests/lifting_model.py restates it in numpy, and the
+ * device is held to it bit for bit.  The planes are plain Mallat planes (dwt_hip_band_levels / dwt_hip_band_geometry), so
+ * the band operators, the quantizer, the sparse streams, the N-term selection and the feature statistics take them.
+ *
+ * The scheme (struct dwt_hip_lifting: fixed size, no pointers).  `type` DWT_HIP_LIFT_F32 (binary32 samples) or
+ * DWT_HIP_LIFT_I32 (int32 samples).  `n_steps` 1 .. 8 steps; a step updates the samples of one `parity` of a line (1: the
+ * odd ones, 0: the even ones; consecutive steps may share a parity) from `n_terms` 1 .. 4 terms.  A term has two tap offsets
+ * relative to the target sample: off_a odd, -7 .. 7; off_b odd, -7 .. 7, or 0 for "no second tap".  A step therefore reads
+ * only the other parity and runs in place without a race.
+ *   float step:  t_k = coef_k * (x[i+off_a] + x[i+off_b]), or coef_k * x[i+off_a] for a single tap;
+ *                sum = ((t_0 + t_1) + t_2) + t_3 over the terms there are; x[i] = x[i] + sum forward, x[i] - sum inverse.
+ *                Every product and every sum is rounded on its own (no FMA).  coef finite.  num, sign, add, shift unused.
+ *   int step:    v = (SUM_k num_k * (a_k + b_k) + add) >> shift (b_k absent for a single tap), wrapping 32-bit arithmetic,
+ *                arithmetic shift, shift 0 .. 31; x[i] += sign * v forward, x[i] -= sign * v inverse; sign +1 or -1.
+ *                coef unused.
+ * Scaling, float only, indexed by parity: forward, after the last step, x *= fwd_scale[parity]; inverse, first x *=
+ * inv_scale[parity], then the steps last to first.  All four values are explicit (CDF 9/7's 1.0f / zeta and (float)(1 /
+ * zeta) are different floats) and finite; a factor of exactly 1.0f is skipped.  Int schemes do not scale.
+ * A 2-D level: the forward lifts every row, then every column.  The inverse lifts rows, then columns when
+ * inverse_cols_first is 0 (the order of the reference's float drivers) and columns, then rows when it is 1 (the exact
+ * mirror).  Int schemes must say 1: they are then reversible bit for bit, wrapped values included.
+ * Line ends: whole-sample symmetric reflection of the INDEX of every tap, at every step, into [0, N): i < 0 -> -i,
+ * i > N-1 -> 2(N-1) - i, repeated until it lies inside (lines shorter than the reach bounce more than once).  Reflection
+ * keeps parity, so every scheme is invertible whatever its taps.  A line of ONE sample runs no step: it is only scaled by
+ * the factor of parity 0 (float) or left as it is (int).
+ * The reach of a scheme is R = the sum over its steps of the largest |offset| of the step.
+ *
+ * dwt_hip_lifting_check (host code, no device): 0 for a scheme that holds to all of the above, and *reach = R (reach may
+ * be NULL); nonzero with dwt_hip_last_error for any other.  dwt_hip_lifting_builtin (host code): the scheme of `id` ->
+ * *scheme, 0; nonzero for an unknown id.  CDF97, CDF53, INTERP53 (float) and CDF53_INT, CDF97_INT give the bits of
+ * DWT_HIP_CDF97_S, _CDF53_S, _INTERP53_S, _CDF53_I, _CDF97_I wherever a line has two samples or more and no doubled
+ * end tap overflows (|x| <= FLT_MAX / 2; int 5/3: |x| < 2^30).  HAAR: odd += -1 x[i-1], even += 0.5 x[i+1], scales 1 (the
+ * reference's element step).  HAAR_INT, the S transform: odd -= x[i-1], even += x[i+1] >> 1.  D4: the reference's
+ * factorization, odd += alpha x[i+1]; even += beta x[i-1] + gamma x[i+1]; odd += delta x[i-1]; alpha = -1/sqrt 3, beta =
+ * (6 - 3 sqrt 3)/4, gamma = sqrt 3 / 4, delta = -1/3, scales (3 +- sqrt 3)/(3 sqrt 2) forward and their own reciprocal
+ * expressions inverse, each the float the reference's expression yields (tests/golden/lifting.npz).
+ *
+ * dwt_hip_lifting2d_batch: `batch` dense frames (size_o == size_i) of size_x x size_y samples, element (x, y) of frame b
+ * at base + b*batch_stride + y*stride_x + x*stride_y bytes, src -> dst (the same strides on both sides); src == dst is
+ * allowed, any other overlap of the two is refused.  J = dwt_hip_band_levels(size_x, size_y, *j) levels, stored to *j;
+ * level k acts on the ceil(size / 2^k) LL rectangle; L takes ceil(N/2) samples at offset 0, H floor(N/2) samples at offset
+ * ceil(N/2).  `scheme` is host memory, copied at the call.  src / dst are host or device memory, both the same; dense
+ * device frames (stride_y == 4, addresses and strides multiples of 4 bytes) run where they lie and the call does not
+ * wait for the device; host and strided frames go through the staging path and end synchronised.
+ * Routes.  FUSED (R <= 8): ONE launch per level for the whole batch -- a workgroup owns a 64 x 64 tile of the level, stages
+ * it with a halo of R samples in LDS, runs the row steps and the column steps in place there (the halo is recomputed, never
+ * exchanged; positions outside the frame are never lifted: every tap reflects its index and reads the cell of the sample it
+ * lands on), scales and writes the four subbands; LL goes through scratch of the context.  src == dst costs one more
+ * launch and a copy of the batch in scratch (the tiles read halos that other tiles overwrite).  STEPS (option
+ * "lifting_fused" = 0, and R > 8): per level one copy of the LL rectangle into dense scratch, one elementwise launch per
+ * step and direction, one launch that scales and places the subbands.  Same bits.  dwt_hip_lifting_route: DWT_HIP_LIFT_FUSED
+ * or DWT_HIP_LIFT_STEPS for a call with this scheme under the current options, -1 for a scheme the entries refuse.
+ * Errors (nonzero, dwt_hip_last_error, nothing launched, nothing written): a bad scheme, a null pointer, sizes < 1, batch
+ * < 1 or > DWT_HIP_LIFT_MAX_BATCH, strides below the element, a row or a frame, src and dst in different memory spaces or
+ * overlapping. */
+enum dwt_hip_lifting_type { DWT_HIP_LIFT_F32 = 0, DWT_HIP_LIFT_I32 = 1 };
+enum dwt_hip_lifting_id {
+	DWT_HIP_LIFT_CDF97 = 0, DWT_HIP_LIFT_CDF53, DWT_HIP_LIFT_INTERP53, DWT_HIP_LIFT_CDF53_INT, DWT_HIP_LIFT_CDF97_INT,
+	DWT_HIP_LIFT_HAAR, DWT_HIP_LIFT_HAAR_INT, DWT_HIP_LIFT_D4
+};
+enum dwt_hip_lifting_route_id { DWT_HIP_LIFT_STEPS = 0, DWT_HIP_LIFT_FUSED = 1 };
+#define DWT_HIP_LIFT_MAX_STEPS 8
+#define DWT_HIP_LIFT_MAX_TERMS 4
+#define DWT_HIP_LIFT_MAX_OFFSET 7
+#define DWT_HIP_LIFT_FUSED_REACH 8 /* the largest reach the fused route takes */
+#define DWT_HIP_LIFT_MAX_BATCH 65535 /* frames of one call (the tile kernels' grid.z) */
+struct dwt_hip_lifting_term {
+	float coef;       /* float schemes */
+	int num;          /* int schemes */
+	int off_a, off_b; /* tap offsets; off_b 0: no second tap */
+};
+struct dwt_hip_lifting_step {
+	int parity, n_terms;
+	int sign, add, shift; /* int schemes */
+	int reserved[3];      /* 0 */
+	struct dwt_hip_lifting_term terms[DWT_HIP_LIFT_MAX_TERMS];
+};
+struct dwt_hip_lifting {
+	int type, n_steps, inverse_cols_first;
+	int reserved; /* 0 */
+	float fwd_scale[2], inv_scale[2];
+	struct dwt_hip_lifting_step steps[DWT_HIP_LIFT_MAX_STEPS];
+}; /* 800 bytes */
+int dwt_hip_lifting_check(const struct dwt_hip_lifting *scheme, int *reach);
+int dwt_hip_lifting_builtin(int id, struct dwt_hip_lifting *scheme);
+int dwt_hip_lifting2d_batch(const struct dwt_hip_lifting *scheme, int inverse, const void *src, void *dst, size_t batch_stride,
+	int batch, int stride_x, int stride_y, int size_x, int size_y, int *j);
+int dwt_hip_lifting_route(const struct dwt_hip_lifting *scheme);
+
 /* Time-frequency planes of line batches: the Gaussian-window STFT, the complex Morlet CWT and the S transform of
  * src/gabor.c (gabor_ft_s, gabor_wt_s, gabor_st_s and their _arg_ twins; include/gabor.h), DESIGN.md s14.
  *

@@ -677,6 +677,47 @@ struct SparseUnpackArgs {
 hipError_t launch_sparse_zero(int es, const SparseUnpackArgs &a, hipStream_t s);
 hipError_t launch_sparse_scatter(int es, const SparseUnpackArgs &a, hipStream_t s);
 
+// User-defined lifting wavelets (dwt_lifting.hip): the caller's scheme as the kernels take it, by value in
+// the kernel arguments (wave-uniform).  Samples are 4-byte words (binary32 or int32); pitches and batch strides below are
+// in ELEMENTS.
+constexpr int LIFT_MAX_STEPS = 8, LIFT_MAX_TERMS = 4;
+constexpr int LIFT_TILE = 64;       // side of a workgroup's tile of the level
+constexpr int LIFT_FUSED_REACH = 8; // the largest halo the tile kernels stage
+struct LiftStep {
+	int parity, n_terms, reach; // reach: the largest |offset| of the step
+	int sign, add, shift;       // int schemes
+	int off_a[LIFT_MAX_TERMS], off_b[LIFT_MAX_TERMS];
+	float coef[LIFT_MAX_TERMS];
+	int num[LIFT_MAX_TERMS];
+};
+struct LiftTable {
+	int is_int, n_steps, inv_cols_first, reach;
+	float fwd_scale[2], inv_scale[2];
+	LiftStep steps[LIFT_MAX_STEPS];
+};
+// One fused level on the W x H rectangle.  Forward: `in` -> LL to `out`, HL / LH / HH to `det` at their Mallat offsets of
+// the rectangle.  Inverse: LL from `in`, HL / LH / HH from `det` -> the W x H result to `out`.  No tile reads what another
+// writes: `in` and `det` (inverse) share no element with `out` and `det` (forward).
+struct LiftLevelArgs {
+	int W, H, batch;
+	const void *in;
+	long pin, bi_in;
+	void *det;
+	long pd, bi_det;
+	void *out;
+	long pout, bi_out;
+};
+hipError_t launch_lift_tile(bool inverse, const LiftTable &tb, const LiftLevelArgs &a, hipStream_t s);
+// the step-by-step route on a dense scratch x[batch][H][W]
+hipError_t launch_lift_copy(const void *src, long ps, long bs, void *dst, long pd, long bd, int W, int H, int batch, hipStream_t s);
+hipError_t launch_lift_step(bool is_int, bool inverse, void *x, int W, int H, int batch, const LiftStep &st, bool rows, hipStream_t s);
+hipError_t launch_lift_scale(void *x, int W, int H, int batch, bool along_x, float f0, float f1, hipStream_t s);
+// x -> the four subbands at their Mallat places of dst's W x H rectangle, scaled by the parity of y (scale: float schemes)
+hipError_t launch_lift_place(const void *x, void *dst, long pd, long bd, int W, int H, int batch, bool scale, float f0, float f1, hipStream_t s);
+// LL (from ll) and HL / LH / HH (from det) of the W x H rectangle -> x in sample order, scaled by the parity along x or y
+hipError_t launch_lift_gather(const void *ll, long pll, long bll, const void *det, long pd, long bd, void *x, int W, int H, int batch,
+	bool scale, bool along_x, float f0, float f1, hipStream_t s);
+
 // N-term approximation (dwt_nterm.hip): keep the coefficients of the n largest magnitudes of every group
 // of 1 .. 4 dense frames, zero the rest.  The key of a position is the uint32 image of its float magnitude (sign bit 0:
 // unsigned order is float order); a radix select over 11 + 10 + 10 bits finds the key of descending rank n, one
