@@ -1146,6 +1146,53 @@ int dwt_hip_lifting2d_batch(const struct dwt_hip_lifting *scheme, int inverse, c
 	int batch, int stride_x, int stride_y, int size_x, int size_y, int *j);
 int dwt_hip_lifting_route(const struct dwt_hip_lifting *scheme);
 
+/* User-defined lifting wavelets of LINE batches, and the quantizer norms of a scheme.  An extension like
+ * the one above; this comment is the specification, tests/lifting1d_model.py restates it in numpy (on the line pass of
+ * tests/lifting_model.py), and the device is held to it bit for bit.
+ *
+ * dwt_hip_lifting1d_batch: `n_lines` dense lines (size_o == size_i) of `size` samples, element i of line n at base +
+ * n*line_stride + i*elem_stride bytes, src -> dst with the same strides on both sides.  The result is the multi-level 1-D
+ * Mallat layout of dwt_hip_transform1d_batch: level k acts on the first ceil(size / 2^k) samples of every line; L takes
+ * ceil(n/2) samples at offset 0, H floor(n/2) samples at offset ceil(n/2).  So dwt_hip_features1d_batch, the packet and
+ * the conditioning entries take the lines as they are.
+ * Levels.  With limit = ceil_log2(size): forward, a *j outside 0 .. limit becomes the limit, and the count used is stored
+ * to *j; inverse, a *j inside 0 .. limit - 1 is used as it is, any other value stands for the limit, and *j is only read.
+ * (Both as dwt_hip_transform1d_batch does it.)  No level: the lines are copied, or left alone when src == dst.
+ * One level of one line is the line pass of the 2-D specification above, unchanged: the scheme's steps first to last,
+ * every tap reflecting its INDEX into [0, n) bounce by bounce, then x *= fwd_scale[parity]; the inverse applies
+ * inv_scale[parity] first, then the steps last to first, float schemes subtracting the sum and int schemes sign * v.  A line
+ * of one sample runs no step and is only scaled by the factor of parity 0.  inverse_cols_first has no meaning here (and
+ * dwt_hip_lifting_check still asks int schemes to say 1).
+ * src == dst is allowed (a line is read whole before any of it is written); any other overlap of the two is refused.
+ * Memory.  src and dst are both host or both device memory.  Device lines whose addresses and strides are multiples of 4
+ * bytes run where they lie -- any such elem_stride, so one channel of interleaved data does -- and the call does not wait
+ * for the device.  Host memory and every other device layout go through the staging path and end synchronised.
+ * Routes.  FUSED: every level whose input line has at most 8192 samples runs in ONE launch for the whole batch, whatever
+ * the depth and whatever the scheme's reach -- the line lies in LDS whole, so there is no halo and no reach limit.  STEPS
+ * (option "lifting_fused" = 0, and the leading levels of lines longer than 8192 samples): per level the lines' prefix is
+ * copied into dense scratch, every step is one elementwise launch there, and one launch scales and places the result; a
+ * longer line runs its over-long levels this way and the rest in one fused launch.  Same bits.  dwt_hip_lifting1d_route:
+ * DWT_HIP_LIFT_FUSED where a call with this scheme and this size runs in one launch under the current options,
+ * DWT_HIP_LIFT_STEPS where not, -1 for a scheme or a size the entry refuses.
+ * Errors (nonzero, dwt_hip_last_error, nothing launched, nothing written): a bad scheme, a null pointer, size < 1, n_lines
+ * < 1, an elem_stride below 4, a line_stride below what a line spans, src and dst in different memory spaces or overlapping.
+ *
+ * dwt_hip_lifting_norms (host code, no device; float schemes only): norm_l[j-1] and norm_h[j-1], j = 1 .. levels <=
+ * DWT_HIP_QUANT_MAX_LEVELS, the L2 norms of the scheme's 1-D synthesis functions: a 1 at the middle L (resp. H) coefficient
+ * of level j, every other coefficient 0, inverted j levels in double -- inv_scale first, the steps last to first, coef * (a
+ * + b) and ((t0 + t1) + t2) + t3 evaluated in double on the binary32 constants widened --, the root of the sum of the
+ * squares.  The line is sized from the scheme's reach (4 (R + 2) << (j - 1) samples) so that no tap reflects.  With the
+ * CDF97, CDF53 and INTERP53 tables this is dwt_hip_quant_norms of the wavelet.
+ * dwt_hip_lifting_quant_steps (host code): the 3*levels + 1 steps of dwt_hip_quant_steps, by its formula, from those
+ * norms; the table goes to dwt_hip_quantize_batch as it is.  levels 0 .. 16, base_step finite and > 0.
+ * Both return 0, or nonzero with dwt_hip_last_error: a bad or an int scheme, a null pointer, levels out of range, a bad base
+ * step. */
+int dwt_hip_lifting1d_batch(const struct dwt_hip_lifting *scheme, int inverse, const void *src, void *dst, size_t line_stride,
+	int elem_stride, int n_lines, int size, int *j);
+int dwt_hip_lifting1d_route(const struct dwt_hip_lifting *scheme, int size);
+int dwt_hip_lifting_norms(const struct dwt_hip_lifting *scheme, int levels, double *norm_l, double *norm_h);
+int dwt_hip_lifting_quant_steps(const struct dwt_hip_lifting *scheme, int levels, float base_step, float *steps);
+
 /* Time-frequency planes of line batches: the Gaussian-window STFT, the complex Morlet CWT and the S transform of
  * src/gabor.c (gabor_ft_s, gabor_wt_s, gabor_st_s and their _arg_ twins; include/gabor.h), DESIGN.md s14.
  *

@@ -62,6 +62,8 @@ NEVER_PREFILLED = frozenset((
     # queries of a previous call or of a pointer: a fill in front of them would change the answer or is pointless
     "dwt_hip_last_error", "dwt_hip_is_device_pointer", "dwt_hip_rows_warnings", "dwt_hip_features_raw_sums", "dwt_hip_placement_report",
     "dwt_hip_alloc_batch_note", "dwt_hip_alloc_batch_report", "dwt_hip_prof_enable", "dwt_hip_prof_read", "dwt_hip_prof_read_levels",
+    # host arithmetic on a lifting scheme, and the route query: no device work, no scratch
+    "dwt_hip_lifting_norms", "dwt_hip_lifting_quant_steps", "dwt_hip_lifting1d_route",
 ))
 _poison = None  # the word, or None: off
 

@@ -11,6 +11,10 @@
 // STEPS: per level a dense copy of the LL rectangle (forward) or the gathered subbands (inverse) in scratch, one
 // elementwise launch per step and direction in place there, and one launch that places the result.  Any size, any reach.
 // Host memory and strided device frames are packed into a dense device stack first, as the other drivers do.
+//
+// Line batches (dwt_hip_lifting1d_batch): every level whose line has at most N1D_MAX samples in ONE launch
+// of k_lift_lines, straight from src to dst, any reach.  Option "lifting_fused" = 0, and the leading levels of longer
+// lines, go level by level through the dense scratch (frame_b) with one launch per step -- the split of dwt_backend_1d.hip.
 #include "dwt_backend.h"
 
 #include <climits>
@@ -152,6 +156,71 @@ int run_device(bool inverse, const LiftTable &tb, const Frames &f, const char *s
 	return fused_route(tb) ? run_fused(inverse, tb, f, src, dst) : run_steps(inverse, tb, f, src, dst);
 }
 
+// ---- a batch of lines (dwt_hip_lifting1d_batch) -------------------------------------------------------------
+
+struct Lines {
+	int N, n_lines, J;
+	long ls, es; // of src and dst alike, in WORDS
+	int len(int j) const { return ceil_div_pow2(N, j); }
+};
+
+// levels whose line is longer than the fused kernel takes (the split of dwt_backend_1d.hip)
+int lines_long_levels(int N, int J)
+{
+	int j = 0;
+	while (j < J && ceil_div_pow2(N, j) > N1D_MAX)
+		j++;
+	return j;
+}
+
+bool lines_fused_route(int size) { return g.lifting_fused != 0 && size <= N1D_MAX; }
+
+int line_move(int mode, const void *ll, const void *det, long sls, long ses, void *dst, long dls, long des, int W, int H, bool scale, const float *fs)
+{
+	return launched(launch_lift_line_move(mode, ll, det, sls, ses, dst, dls, des, W, H, scale, fs[0], fs[1], g.stream), "lifting", "line move");
+}
+
+// Level j of every line step by step: the level's prefix of the lines into the dense scratch (a frame of W = the prefix, H
+// = n_lines, lifted along rows only), one launch per step there, the result back to dst's prefix.  Forward: the prefix of
+// `ll` in sample order -> Mallat order.  Inverse: L from `ll`, H from `det` -> sample order.
+int lines_steps_level(bool inverse, const LiftTable &tb, const Lines &l, int j, const char *ll, const char *det, char *dst)
+{
+	const int W = l.len(j), H = l.n_lines;
+	void *x = g.frame_b.p;
+	const float *fs = inverse ? tb.inv_scale : tb.fwd_scale;
+	const bool scale = !tb.is_int && (fs[0] != 1.0f || fs[1] != 1.0f);
+	if (line_move(inverse ? 1 : 0, ll, det, l.ls, l.es, x, W, 1, W, H, scale, fs) || steps_pass(inverse, tb, x, W, H, 1, true))
+		return 1;
+	return line_move(inverse ? 0 : 2, x, x, W, 1, dst, l.ls, l.es, W, H, scale, fs);
+}
+
+// device lines whose addresses and strides are multiples of 4 bytes, src == dst or apart
+int run_lines(bool inverse, const LiftTable &tb, const Lines &l, const char *src, char *dst)
+{
+	const int J = l.J;
+	if (J == 0) // no level: the lines as they are
+		return src == dst ? 0 : line_move(0, src, src, l.ls, l.es, dst, l.ls, l.es, l.N, l.n_lines, false, tb.fwd_scale);
+	const int jg = g.lifting_fused != 0 ? lines_long_levels(l.N, J) : J; // levels 0 .. jg-1 step by step
+	if (jg > 0 && grow(g.frame_b, (size_t)l.N * 4 * l.n_lines))
+		return 1;
+	auto fused = [&](const char *s) {
+		return launched(launch_lift_lines(inverse, tb, s, dst, l.ls * 4, l.es * 4, l.n_lines, l.len(jg), J - jg, g.stream), "lifting", "lines");
+	};
+	if (!inverse) {
+		for (int j = 0; j < jg; j++)
+			if (lines_steps_level(false, tb, l, j, j == 0 ? src : dst, nullptr, dst))
+				return 1;
+		return jg < J ? fused(jg == 0 ? src : dst) : 0;
+	}
+	// (the inverse reads every H band from src; what a level has rebuilt lies in dst)
+	if (jg < J && fused(src))
+		return 1;
+	for (int j = jg - 1; j >= 0; j--)
+		if (lines_steps_level(true, tb, l, j, j == J - 1 ? src : dst, src, dst))
+			return 1;
+	return 0;
+}
+
 } // namespace
 
 } // namespace dwtb
@@ -222,6 +291,73 @@ int dwt_hip_lifting_route(const struct dwt_hip_lifting *scheme)
 	if (table_of(scheme, &tb))
 		return -1;
 	return fused_route(tb) ? DWT_HIP_LIFT_FUSED : DWT_HIP_LIFT_STEPS;
+}
+
+int dwt_hip_lifting1d_batch(const struct dwt_hip_lifting *scheme, int inverse, const void *src, void *dst, size_t line_stride, int elem_stride,
+	int n_lines, int size, int *j)
+{
+	LiftTable tb;
+	if (table_of(scheme, &tb))
+		return 1;
+	if (!src || !dst || !j)
+		return fail("null pointer argument");
+	if (size < 1)
+		return fail("lifting: bad sizes: %d samples a line (at least 1)", size);
+	if (n_lines < 1)
+		return fail("lifting: %d lines (at least 1)", n_lines);
+	const long es = elem_stride;
+	const long one = es * (size - 1) + 4; // bytes a line spans
+	if (es < 4 || line_stride > (size_t)LONG_MAX / 2 / (size_t)n_lines || (n_lines > 1 && (long)line_stride < one))
+		return fail("lifting: bad strides: line %zu bytes, element %d bytes", line_stride, elem_stride);
+	const long ls = n_lines > 1 ? (long)line_stride : 0;
+	const size_t extent = (size_t)ls * (n_lines - 1) + one;
+	if (src != dst && overlap(src, extent, dst, extent))
+		return fail("lifting: src and dst overlap (src == dst is the in-place call)");
+	if (check_inited())
+		return 1;
+	const bool dev = dwt_hip_is_device_pointer(src);
+	if (dev != (bool)dwt_hip_is_device_pointer(dst))
+		return fail("lifting: src and dst must both be host or both be device memory");
+	// the level count, clamped as transform1d (dwt_backend_1d.hip) clamps it
+	const int j_limit = ceil_log2(size);
+	Lines l;
+	l.N = size, l.n_lines = n_lines;
+	if (!inverse) {
+		if (*j < 0 || *j > j_limit)
+			*j = j_limit;
+		l.J = *j;
+	} else {
+		l.J = *j >= 0 && *j < j_limit ? *j : j_limit;
+	}
+	if (l.J == 0 && src == dst)
+		return 0;
+	if (dev && es % 4 == 0 && ls % 4 == 0 && (uintptr_t)src % 4 == 0 && (uintptr_t)dst % 4 == 0) {
+		l.ls = ls / 4, l.es = es / 4;
+		return run_lines(inverse != 0, tb, l, (const char *)src, (char *)dst);
+	}
+	// host memory, device lines that are not made of aligned words: the staging detour (dwt_backend.h), in place on the dense frame
+	const Frame fs{const_cast<void *>(src), ls ? ls : one, es, 4, size, n_lines, dev};
+	if (frame_check(fs))
+		return 1;
+	Img A;
+	if (frame_stage(fs, g.frame_a, &A))
+		return 1;
+	l.ls = A.sx / 4, l.es = 1;
+	if (run_lines(inverse != 0, tb, l, A.p, A.p))
+		return 1;
+	return frame_unpack(Frame{dst, fs.sx, es, 4, size, n_lines, dev}, A.p, A.sx);
+}
+
+int dwt_hip_lifting1d_route(const struct dwt_hip_lifting *scheme, int size)
+{
+	LiftTable tb;
+	if (table_of(scheme, &tb))
+		return -1;
+	if (size < 1) {
+		fail("lifting: bad sizes: %d samples a line (at least 1)", size);
+		return -1;
+	}
+	return lines_fused_route(size) ? DWT_HIP_LIFT_FUSED : DWT_HIP_LIFT_STEPS;
 }
 
 } // extern "C"

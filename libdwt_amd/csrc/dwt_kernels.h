@@ -717,6 +717,19 @@ hipError_t launch_lift_place(const void *x, void *dst, long pd, long bd, int W, 
 // LL (from ll) and HL / LH / HH (from det) of the W x H rectangle -> x in sample order, scaled by the parity along x or y
 hipError_t launch_lift_gather(const void *ll, long pll, long bll, const void *det, long pd, long bd, void *x, int W, int H, int batch,
 	bool scale, bool along_x, float f0, float f1, hipStream_t s);
+// Every level of `n_lines` lines of N <= N1D_MAX samples in ONE launch (k_lift_lines), any reach: line i at
+// src + i*line_stride, elements `elem_stride` bytes apart (multiples of 4); the result in the 1-D Mallat order of
+// launch_line_levels goes to the same places in dst, which may be src.  Forward: `levels` levels from the full line down;
+// inverse: the `levels` coarsest levels back to the full line.  Lines of up to LIFT_LINE_WAVE samples get a wave each,
+// up to LIFT_LINE_HALF half a workgroup, longer ones the whole of it.
+constexpr int LIFT_LINE_WAVE = 512, LIFT_LINE_HALF = 2048;
+hipError_t launch_lift_lines(bool inverse, const LiftTable &tb, const void *src, void *dst, long line_stride, long elem_stride, int n_lines,
+	int N, int levels, hipStream_t s);
+// the step-by-step route of lines: W words of H lines, element i of line y at y*ls + i*es WORDS (source: sls, ses; dst:
+// dls, des).  mode 0: a copy (ll).  mode 1: Mallat order (L from ll, H from det, both by the source's strides) -> sample
+// order; mode 2: sample order (ll) -> Mallat order; scale: times f0 / f1 by the parity of the sample (float schemes)
+hipError_t launch_lift_line_move(int mode, const void *ll, const void *det, long sls, long ses, void *dst, long dls, long des, int W, int H,
+	bool scale, float f0, float f1, hipStream_t s);
 
 // N-term approximation (dwt_nterm.hip): keep the coefficients of the n largest magnitudes of every group
 // of 1 .. 4 dense frames, zero the rest.  The key of a position is the uint32 image of its float magnitude (sign bit 0:

@@ -15,7 +15,11 @@
 //    reflection and lifted like interior samples is right only for symmetric steps.
 //  * k_lift_step and its companions: the step-by-step route on a dense copy of the level, one elementwise launch per step
 //    and direction.  The cross-check, and the route of schemes whose reach exceeds 8.
+//  * k_lift_lines: every level of a batch of LINES of up to N1D_MAX samples in one launch, the line whole in LDS as two
+//    parity arrays: no halo, so any reach.  k_lift_line_move gathers and places the lines of the
+//    step-by-step route.
 #include "dwt_kernels.h"
+#include "dwt_line_lds.h"
 
 #include <type_traits>
 
@@ -333,7 +337,228 @@ __global__ __launch_bounds__(256) void k_lift_gather(const T *__restrict__ ll, l
 	}
 }
 
+// ---- a batch of lines (dwt_hip_lifting1d_batch) -----------------------------------------------------------
+
+// `mode` 0: W words of H lines, src -> dst as they are.  1: the lines of the source in Mallat order (L from ll, H from det)
+// -> sample order, 2: sample order -> Mallat order; both scaled by the parity of the sample.  Element i of line y at
+// y*ls + i*es WORDS on either side; threads enumerate the Mallat side.
+template <class T>
+__global__ __launch_bounds__(256) void k_lift_line_move(const T *__restrict__ ll, const T *__restrict__ det, long sls, long ses, T *__restrict__ dst,
+	long dls, long des, int W, int H, int mode, float f0, float f1)
+{
+	const long total = (long)W * H;
+	const int Wd = (W + 1) >> 1;
+	for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long)gridDim.x * blockDim.x) {
+		const int ox = (int)(t % W);
+		const long y = t / W;
+		const int gx = ox < Wd ? 2 * ox : 2 * (ox - Wd) + 1;
+		if (mode == 0)
+			dst[y * dls + ox * des] = ll[y * sls + ox * ses];
+		else if (mode == 1)
+			dst[y * dls + gx * des] = lift_scaled((ox < Wd ? ll : det)[y * sls + ox * ses], (gx & 1) ? f1 : f0);
+		else
+			dst[y * dls + ox * des] = lift_scaled(ll[y * sls + gx * ses], (gx & 1) ? f1 : f0);
+	}
+}
+
+static __host__ __device__ __forceinline__ int lift_r4(int n) { return (n + 3) & ~3; }
+static __host__ __device__ __forceinline__ int lift_len(int N, int j) { return (N + (1 << j) - 1) >> j; }
+// words of LDS one line takes, each part rounded up to 16 B: forward the line and the next level's input, inverse the line
+// and the outputs of two consecutive levels
+static __host__ __device__ __forceinline__ int lift_line_words(bool inverse, int N)
+{
+	return lift_r4(N) + lift_r4(lift_len(N, 1)) + (inverse ? lift_r4(lift_len(N, 2)) : 0);
+}
+
+struct LiftLinesArgs {
+	const char *src;
+	char *dst;
+	long line_stride, elem_stride; // bytes
+	int n_lines, N, levels;
+	int tpl; // threads per line: 64, 128 or 256
+	int vec; // dense lines whose every address is a multiple of 16 bytes
+};
+
+// Every step of one level of one line, in place.  The line of n samples lies as two parity arrays, E its even samples and
+// O its odd ones, so the lanes of a step walk both with unit stride (sample 2k + p of an interleaved line would put them on
+// every second bank): sample i is ((i & 1) ? O : E)[i >> 1].  A step writes one array and reads the other: one barrier a step.
+template <class T, bool INV>
+static __device__ __forceinline__ void lift_line_steps(const LiftTable &tb, T *E, T *O, int n, int t, int tpl, bool active)
+{
+	auto at = [&](int i) { return ((i & 1) ? O : E)[i >> 1]; };
+	for (int si = 0; si < tb.n_steps && n >= 2; si++) {
+		const LiftStep &st = tb.steps[INV ? tb.n_steps - 1 - si : si];
+		T *const own = st.parity ? O : E;
+		const int cnt = st.parity ? n >> 1 : (n + 1) >> 1;
+		if (active)
+			for (int k = t; k < cnt; k += tpl) {
+				const int g = 2 * k + st.parity;
+				// a sample whose every tap lies inside the line reflects nothing
+				own[k] = g >= st.reach && g + st.reach < n ? lift_eval<T, INV, false>(st, g, n, at) : lift_eval<T, INV, true>(st, g, n, at);
+			}
+		__syncthreads();
+	}
+}
+
+// Every level of `n_lines` lines of N <= N1D_MAX samples in ONE launch, any scheme of any reach: a line lies in LDS whole,
+// so there is no halo.  `tpl` threads work on a line, 256 / tpl lines share the workgroup; all lines have the same length and
+// depth, so every thread meets the same barriers.
+// Forward: the line is split by parity as it arrives -- even samples at [0, ceil(n/2)), odd ones behind them, which are
+// the level's Mallat places.  Per level the steps run in place; H, scaled, goes to its Mallat offset in global memory; L,
+// scaled, is split by parity into the other buffer, the next level's input; the last level's L goes to global memory.
+// Inverse: the whole line is loaded (line_to_lds) and scaled once, L_J by inv_scale[0], every H band by inv_scale[1].  A
+// level's E is its L part -- the previous level's output, the line's prefix at the coarsest level --, its O is its H band
+// where it was loaded; after the steps the two are interleaved, scaled by inv_scale[0] as the next level's L, into the
+// other buffer (the finest level: into global memory, unscaled).
+template <class T, bool INV>
+__global__ __launch_bounds__(256) void k_lift_lines(const LiftTable tb, const LiftLinesArgs a)
+{
+	extern __shared__ float lift_lds[];
+	constexpr bool kFloat = std::is_same<T, float>::value;
+	using V2 = typename std::conditional<kFloat, float2, int2>::type;
+	using V4 = typename std::conditional<kFloat, float4, int4>::type;
+	const int tpl = a.tpl, N = a.N;
+	const int sub = threadIdx.x / tpl, t = threadIdx.x % tpl;
+	const long line = (long)blockIdx.x * (blockDim.x / tpl) + sub;
+	const bool active = line < a.n_lines;
+	T *const A = (T *)lift_lds + (long)sub * lift_line_words(INV, N);
+	T *const B = A + lift_r4(N);
+	const char *s = a.src + line * a.line_stride;
+	char *d = a.dst + line * a.line_stride;
+	const long es = a.elem_stride;
+	auto ld = [&](int i) { return *(const T *)(s + i * es); };
+	auto st = [&](int i, T v) { *(T *)(d + i * es) = v; };
+
+	if constexpr (!INV) {
+		if (active) {
+			const int nl = (N + 1) >> 1;
+			const int n4 = a.vec ? N >> 2 : 0;
+			for (int i = t; i < n4; i += tpl) {
+				const V4 v = *(const V4 *)(s + 16l * i);
+				A[2 * i] = v.x, A[2 * i + 1] = v.z, A[nl + 2 * i] = v.y, A[nl + 2 * i + 1] = v.w;
+			}
+			for (int i = 4 * n4 + t; i < N; i += tpl)
+				A[lift_pos(i, N)] = ld(i);
+		}
+		__syncthreads();
+		T *cur = A, *nxt = B;
+		int n = N;
+		for (int lev = 0; lev < a.levels; lev++) {
+			const int nl = (n + 1) >> 1, nh = n >> 1;
+			const bool last = lev == a.levels - 1;
+			T *const E = cur, *const O = cur + nl;
+			lift_line_steps<T, false>(tb, E, O, n, t, tpl, active);
+			if (active) {
+				for (int k = t; k < nh; k += tpl)
+					st(nl + k, lift_scaled(O[k], tb.fwd_scale[1])); // H: final, to its Mallat offset
+				for (int k = t; k < nl; k += tpl) {
+					const T v = lift_scaled(E[k], tb.fwd_scale[0]);
+					if (last)
+						st(k, v);
+					else
+						nxt[lift_pos(k, nl)] = v;
+				}
+			}
+			if (!last)
+				__syncthreads();
+			cur = nxt, nxt = E, n = nl;
+		}
+	} else {
+		T *const C = B + lift_r4(lift_len(N, 1));
+		if (active) {
+			if constexpr (kFloat) {
+				line_to_lds(A, s, N, es, t, tpl, a.vec);
+			} else {
+				const int n4 = a.vec ? N >> 2 : 0;
+				for (int i = t; i < n4; i += tpl)
+					*(V4 *)(A + 4 * i) = *(const V4 *)(s + 16l * i);
+				for (int i = 4 * n4 + t; i < N; i += tpl)
+					A[i] = ld(i);
+			}
+		}
+		__syncthreads();
+		if (kFloat && (tb.inv_scale[0] != 1.0f || tb.inv_scale[1] != 1.0f)) {
+			const int nj = lift_len(N, a.levels);
+			if (active)
+				for (int i = t; i < N; i += tpl)
+					A[i] = lift_scaled(A[i], tb.inv_scale[i < nj ? 0 : 1]);
+			__syncthreads();
+		}
+		for (int lev = a.levels - 1; lev >= 0; lev--) {
+			const int n = lift_len(N, lev), nl = (n + 1) >> 1, nh = n >> 1;
+			T *const E = lev == a.levels - 1 ? A : ((lev + 1) & 1) ? B : C;
+			T *const O = A + nl;
+			T *const out = (lev & 1) ? B : C; // (lev >= 1: B holds ceil(N/2) samples, C ceil(N/4))
+			lift_line_steps<T, true>(tb, E, O, n, t, tpl, active);
+			if (active)
+				for (int k = t; k < nl; k += tpl) {
+					if (lev > 0) {
+						const T e = lift_scaled(E[k], tb.inv_scale[0]);
+						if (k < nh) {
+							V2 v;
+							v.x = e, v.y = lift_scaled(O[k], tb.inv_scale[0]);
+							*(V2 *)(out + 2 * k) = v;
+						} else {
+							out[2 * k] = e;
+						}
+					} else if (a.vec && k < nh) {
+						V2 v;
+						v.x = E[k], v.y = O[k];
+						*(V2 *)(d + 8l * k) = v;
+					} else {
+						st(2 * k, E[k]);
+						if (k < nh)
+							st(2 * k + 1, O[k]);
+					}
+				}
+			if (lev > 0)
+				__syncthreads();
+		}
+	}
+}
+
 } // namespace
+
+hipError_t launch_lift_lines(bool inverse, const LiftTable &tb, const void *src, void *dst, long line_stride, long elem_stride, int n_lines,
+	int N, int levels, hipStream_t s)
+{
+	// (levels <= 30: 1 << level stays inside int)
+	if (n_lines < 1 || levels < 1 || levels > 30 || N < 1 || N > N1D_MAX || elem_stride < 4 || elem_stride % 4 || line_stride % 4)
+		return hipErrorInvalidValue;
+	LiftLinesArgs a;
+	a.src = (const char *)src, a.dst = (char *)dst, a.line_stride = line_stride, a.elem_stride = elem_stride;
+	a.n_lines = n_lines, a.N = N, a.levels = levels;
+	// threads per line: one wave for short lines (four lines per workgroup), the whole workgroup for long ones
+	a.tpl = N <= LIFT_LINE_WAVE ? 64 : N <= LIFT_LINE_HALF ? 128 : 256;
+	a.vec = elem_stride == 4 && line_stride % 16 == 0 && (uintptr_t)src % 16 == 0 && (uintptr_t)dst % 16 == 0;
+	const int lpw = 256 / a.tpl;
+	const size_t lds = (size_t)lpw * lift_line_words(inverse, N) * 4;
+	// (no cap on n_lines: an int's worth of lines is fewer workgroups than grid.x takes)
+	const dim3 grid((unsigned)(((long)n_lines + lpw - 1) / lpw));
+	if (tb.is_int) {
+		if (inverse)
+			k_lift_lines<int, true><<<grid, 256, lds, s>>>(tb, a);
+		else
+			k_lift_lines<int, false><<<grid, 256, lds, s>>>(tb, a);
+	} else {
+		if (inverse)
+			k_lift_lines<float, true><<<grid, 256, lds, s>>>(tb, a);
+		else
+			k_lift_lines<float, false><<<grid, 256, lds, s>>>(tb, a);
+	}
+	return hipGetLastError();
+}
+
+hipError_t launch_lift_line_move(int mode, const void *ll, const void *det, long sls, long ses, void *dst, long dls, long des, int W, int H,
+	bool scale, float f0, float f1, hipStream_t s)
+{
+	const dim3 grid = lift_grid((long)W * H);
+	if (scale && mode != 0)
+		k_lift_line_move<float><<<grid, 256, 0, s>>>((const float *)ll, (const float *)det, sls, ses, (float *)dst, dls, des, W, H, mode, f0, f1);
+	else
+		k_lift_line_move<int><<<grid, 256, 0, s>>>((const int *)ll, (const int *)det, sls, ses, (int *)dst, dls, des, W, H, mode, 1.0f, 1.0f);
+	return hipGetLastError();
+}
 
 hipError_t launch_lift_tile(bool inverse, const LiftTable &tb, const LiftLevelArgs &a, hipStream_t s)
 {

@@ -1,13 +1,15 @@
 /*
  * dwt_lifting_scheme.c -- the host side of the user-defined lifting wavelets (include/libdwt_hip.h): the
- * check of a scheme and its reach, and the built-in schemes.  Plain C99, no device; tests/san/san_lifting.c builds this
- * file alone under the sanitizers.
+ * check of a scheme and its reach, the built-in schemes, and the synthesis norms and quantizer step tables of a float
+ * scheme.  Plain C99, no device; tests/san/san_lifting.c and san_lifting_norms.c build this file alone
+ * under the sanitizers.
  */
 #include "../../include/libdwt_hip.h"
 
 #include <math.h>
 #include <stdarg.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 
 /* the library's error text (dwt_backend_lifting.hip); absent where this file is built alone */
@@ -74,6 +76,135 @@ int dwt_hip_lifting_check(const struct dwt_hip_lifting *s, int *reach)
 	}
 	if (reach)
 		*reach = r;
+	return 0;
+}
+
+/* ---- the synthesis norms of a float scheme (host arithmetic in double) ---- */
+
+/* One inverse level in place: x holds the level's L coefficients, its H is a 1 at index h_at (h_at < 0: all zeros); x
+ * becomes the samples, twice as many.  Nothing outside [*lo, *hi] is nonzero, before and after; the caller's line keeps
+ * that span farther from both ends than any tap reaches, so no tap reflects. */
+static void norm_inverse_level(const struct dwt_hip_lifting *s, double *x, long h_at, long *lo, long *hi)
+{
+	const double f0 = (double)s->inv_scale[0], f1 = (double)s->inv_scale[1];
+	for (long i = *hi; i >= *lo; i--) { /* (backwards: 2i >= i, a coefficient is read before its place is written) */
+		const double v = x[i];
+		x[2 * i + 1] = 0.0;
+		x[2 * i] = v * f0;
+	}
+	for (long i = *lo; i <= *hi && i < 2 * *lo; i++) /* (coefficients the samples did not overwrite) */
+		x[i] = 0.0;
+	*lo = 2 * *lo, *hi = 2 * *hi + 1;
+	if (h_at >= 0)
+		x[2 * h_at + 1] = f1;
+	for (int k = s->n_steps - 1; k >= 0; k--) {
+		const struct dwt_hip_lifting_step *st = &s->steps[k];
+		int reach = 0;
+		for (int t = 0; t < st->n_terms; t++) {
+			const int a = abs(st->terms[t].off_a), b = abs(st->terms[t].off_b);
+			reach = a > reach ? a : reach;
+			reach = b > reach ? b : reach;
+		}
+		long first = *lo - reach, last = *hi + reach;
+		first += (first ^ st->parity) & 1;
+		for (long i = first; i <= last; i += 2) {
+			double sum = 0.0;
+			for (int t = 0; t < st->n_terms; t++) {
+				const struct dwt_hip_lifting_term *tm = &st->terms[t];
+				double a = x[i + tm->off_a];
+				if (tm->off_b != 0)
+					a = a + x[i + tm->off_b];
+				const double p = (double)tm->coef * a;
+				sum = t == 0 ? p : sum + p;
+			}
+			x[i] = x[i] - sum;
+		}
+		*lo -= reach, *hi += reach;
+	}
+}
+
+/* The square root of a finite v > 0 by Heron's iteration from above: it falls until it has reached the root to the last
+ * bit or two (the norms are specified to 1e-12).  Not sqrt(): this file is also built alone, into programs that are linked
+ * without libm (tests/san/san_lifting.c). */
+static double norm_root(double v)
+{
+	double r = v > 1.0 ? v : 1.0;
+	for (int k = 0; k < 1100; k++) {
+		const double next = 0.5 * (r + v / r);
+		if (!(next < r))
+			break;
+		r = next;
+	}
+	return r;
+}
+
+/* coefficients of L (and of H) at the level of the impulse */
+static long norm_line(int reach) { return 2 * ((long)reach + 2); }
+
+/* the L2 norm of the line that a unit L (high 0) or H (high 1) coefficient of level j turns into; x: room for
+ * norm_line(reach) << j doubles */
+static double synthesis_norm(const struct dwt_hip_lifting *s, int reach, int j, int high, double *x)
+{
+	/* level j: norm_line(reach) coefficients each of L and H, the impulse in the middle.  A level turns a margin m of zeros
+	 * at either end into at least 2m - reach, so the margins reach + 2 and reach + 1 stay above reach at every level. */
+	const long mid = norm_line(reach) / 2;
+	long lo = mid, hi = mid;
+	memset(x, 0, (size_t)(norm_line(reach) << j) * sizeof(double));
+	if (!high)
+		x[mid] = 1.0;
+	for (int level = j; level >= 1; level--)
+		norm_inverse_level(s, x, high && level == j ? mid : -1, &lo, &hi);
+	double sum = 0.0;
+	for (long i = lo; i <= hi; i++)
+		sum += x[i] * x[i];
+	return norm_root(sum);
+}
+
+static int norms_of(const struct dwt_hip_lifting *s, int levels, double *norm_l, double *norm_h)
+{
+	int reach = 0;
+	if (dwt_hip_lifting_check(s, &reach))
+		return 1;
+	if (s->type != DWT_HIP_LIFT_F32)
+		return refuse("lifting: an int scheme has no synthesis norms (float schemes only)");
+	if (levels < 0 || levels > DWT_HIP_QUANT_MAX_LEVELS)
+		return refuse("lifting: %d levels (0 .. %d)", levels, DWT_HIP_QUANT_MAX_LEVELS);
+	if (levels == 0)
+		return 0;
+	double *x = malloc((size_t)(norm_line(reach) << levels) * sizeof(double));
+	if (!x)
+		return refuse("lifting: no memory for a line of %ld samples", norm_line(reach) << levels);
+	for (int j = 1; j <= levels; j++) {
+		norm_l[j - 1] = synthesis_norm(s, reach, j, 0, x);
+		norm_h[j - 1] = synthesis_norm(s, reach, j, 1, x);
+	}
+	free(x);
+	return 0;
+}
+
+int dwt_hip_lifting_norms(const struct dwt_hip_lifting *scheme, int levels, double *norm_l, double *norm_h)
+{
+	if (!norm_l || !norm_h)
+		return refuse("lifting: null pointer argument");
+	return norms_of(scheme, levels, norm_l, norm_h);
+}
+
+int dwt_hip_lifting_quant_steps(const struct dwt_hip_lifting *scheme, int levels, float base_step, float *steps)
+{
+	if (!steps)
+		return refuse("lifting: null pointer argument");
+	if (!(base_step > 0.f) || !isfinite(base_step))
+		return refuse("lifting: base step %g (finite and > 0)", (double)base_step);
+	double nl[DWT_HIP_QUANT_MAX_LEVELS + 1], nh[DWT_HIP_QUANT_MAX_LEVELS + 1];
+	if (norms_of(scheme, levels, nl + 1, nh + 1))
+		return 1;
+	nl[0] = 1.0; /* (no level: the samples themselves) */
+	for (int j = 1; j <= levels; j++) {
+		steps[3 * (j - 1) + 0] = (float)((double)base_step / (nh[j] * nl[j]));
+		steps[3 * (j - 1) + 1] = (float)((double)base_step / (nl[j] * nh[j]));
+		steps[3 * (j - 1) + 2] = (float)((double)base_step / (nh[j] * nh[j]));
+	}
+	steps[3 * levels] = (float)((double)base_step / (nl[levels] * nl[levels]));
 	return 0;
 }
 

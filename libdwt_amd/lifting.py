@@ -11,6 +11,12 @@ reversible int32.  A submodule of its own: import it as ``from libdwt_amd import
 
 Pointers are numpy arrays, torch tensors or integer addresses, src and dst both host or both device memory.  The planes are
 plain Mallat planes: bands_apply_batch, the quantizer, the sparse streams and the feature statistics take them.
+
+Line batches: lifting1d_batch leaves the 1-D Mallat layout of transform1d_batch, every level of lines of up
+to 8192 samples in one launch; norms and quant_steps give a float scheme's synthesis norms and the quantizer's step table.
+
+    J = lifting.lifting1d_batch(d4, False, rows, rows, 4 * N, 4, n_rows, N)               # forward, all levels, in place
+    steps = lifting.quant_steps(d4, J, 1 / 256)
 """
 import ctypes as C
 
@@ -53,8 +59,14 @@ lib.dwt_hip_lifting_check.argtypes = [C.POINTER(Scheme), C.POINTER(_I)]
 lib.dwt_hip_lifting_builtin.argtypes = [_I, C.POINTER(Scheme)]
 lib.dwt_hip_lifting2d_batch.argtypes = [C.POINTER(Scheme), _I, _P, _P, _S, _I, _I, _I, _I, _I, C.POINTER(_I)]
 lib.dwt_hip_lifting_route.argtypes = [C.POINTER(Scheme)]
-for _n in ("dwt_hip_lifting_check", "dwt_hip_lifting_builtin", "dwt_hip_lifting2d_batch", "dwt_hip_lifting_route"):
+lib.dwt_hip_lifting1d_batch.argtypes = [C.POINTER(Scheme), _I, _P, _P, _S, _I, _I, _I, C.POINTER(_I)]
+lib.dwt_hip_lifting1d_route.argtypes = [C.POINTER(Scheme), _I]
+lib.dwt_hip_lifting_norms.argtypes = [C.POINTER(Scheme), _I, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+lib.dwt_hip_lifting_quant_steps.argtypes = [C.POINTER(Scheme), _I, C.c_float, C.POINTER(C.c_float)]
+for _n in ("dwt_hip_lifting_check", "dwt_hip_lifting_builtin", "dwt_hip_lifting2d_batch", "dwt_hip_lifting_route", "dwt_hip_lifting1d_batch",
+           "dwt_hip_lifting1d_route", "dwt_hip_lifting_norms", "dwt_hip_lifting_quant_steps"):
     getattr(lib, _n).restype = _I
+MAX_LINE_FUSED, QUANT_MAX_LEVELS = 8192, 16  # the longest line of the one-launch route; DWT_HIP_QUANT_MAX_LEVELS
 
 
 def step(parity, terms, sign=1, add=0, shift=0):
@@ -111,3 +123,37 @@ def route(s):
     if r < 0:
         raise DwtError("dwt_hip_lifting_route: " + lib.dwt_hip_last_error().decode(errors="replace"))
     return r
+
+
+def lifting1d_batch(s, inverse, src, dst, line_stride, elem_stride, n_lines, size, j=-1):
+    """dwt_hip_lifting1d_batch: n_lines lines of `size` samples -> the 1-D Mallat layout of transform1d_batch.
+    Returns the level count: the one the forward call used; the inverse only reads j and returns it as given."""
+    jj = _I(j)
+    _check(lib.dwt_hip_lifting1d_batch(C.byref(s), int(bool(inverse)), _addr(src), _addr(dst), line_stride, elem_stride, n_lines, size,
+                                       C.byref(jj)), "dwt_hip_lifting1d_batch")
+    return jj.value
+
+
+def route1d(s, size):
+    """dwt_hip_lifting1d_route: FUSED where lines of `size` samples run every level in one launch under the current options,
+    STEPS where not"""
+    r = lib.dwt_hip_lifting1d_route(C.byref(s), size)
+    if r < 0:
+        raise DwtError("dwt_hip_lifting1d_route: " + lib.dwt_hip_last_error().decode(errors="replace"))
+    return r
+
+
+def norms(s, levels):
+    """dwt_hip_lifting_norms -> (norm_l, norm_h): two lists of `levels` floats, the L2 norms of the float scheme's synthesis
+    functions of levels 1 .. levels (host arithmetic)"""
+    nl, nh = (C.c_double * max(levels, 1))(), (C.c_double * max(levels, 1))()
+    _check(lib.dwt_hip_lifting_norms(C.byref(s), levels, nl, nh), "dwt_hip_lifting_norms")
+    return list(nl[:max(levels, 0)]), list(nh[:max(levels, 0)])
+
+
+def quant_steps(s, levels, base_step):
+    """dwt_hip_lifting_quant_steps -> the 3*levels + 1 steps of a float scheme as a ctypes float array, in the layout of
+    quant.quant_steps: what quantize_batch takes for planes made with this scheme"""
+    steps = (C.c_float * (3 * max(levels, 0) + 1))()
+    _check(lib.dwt_hip_lifting_quant_steps(C.byref(s), levels, base_step, steps), "dwt_hip_lifting_quant_steps")
+    return steps
