@@ -272,7 +272,8 @@ long dwt_hip_eaw53_weights_layout(int layout, int size_o_x, int size_o_y, int si
 	long *off_h, long *off_v);
 
 /* Batch of independent equally sized dense images resident in HBM, `batch_stride`
- * bytes apart; one launch per level covers the whole batch. */
+ * bytes apart; one launch per level covers the whole batch.  Addresses and strides are multiples of the element
+ * size (this entry has no staging detour: anything else is refused). */
 int dwt_hip_transform2d_batch(int wavelet, int inverse, const void *src, void *dst,
 	size_t batch_stride, int batch, int stride_x, int size_x, int size_y, int *j);
 
@@ -323,7 +324,9 @@ int dwt_hip_transform2d_interleaved(int wavelet, int inverse, int flavour, const
  * (src/volume-dwt.c:677, 1115); `levels` > 1 re-applies it on the LLL lattice
  * (strides doubled) as SURVEY.md s8 a11 describes.  Device pointer, dense x.  Levels of 512^3 and
  * more (256 tiles of 256 x 64 voxel columns or more) run in ONE pass in place (tile halos read from a
- * snapshot, ~10.8 B per voxel), smaller ones in two passes through a scratch volume. */
+ * snapshot, ~10.8 B per voxel), smaller ones in two passes through a scratch volume.  The volume's address and
+ * both strides are multiples of 4 bytes, in this entry, in dwt_hip_transform3d_op and for the device volumes of the
+ * struct volume_t entries below: anything else is refused with a message and nothing is written. */
 int dwt_hip_transform3d(int inverse, void *vol, size_t stride_y, size_t stride_z,
 	int size_x, int size_y, int size_z, int levels);
 

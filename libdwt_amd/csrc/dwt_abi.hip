@@ -494,6 +494,9 @@ int dwt_hip_transform2d_batch(int wavelet, int inverse, const void *src, void *d
 		return fail("batched transforms take device pointers");
 	if ((stride_x % es) || stride_x < size_x * es || (batch_stride % es) || batch_stride < (size_t)stride_x * size_y)
 		return fail("bad strides");
+	// (the images are read and written as elements where they lie: no staging detour in this entry)
+	if ((uintptr_t)src % es || (uintptr_t)dst % es)
+		return fail("batched transforms take addresses that are multiples of the element size (%d bytes)", es);
 	if (batch > 1 && src == dst)
 		return fail("in-place batches are not supported; use distinct src and dst");
 	const Geom ge{size_x, size_y, size_x, size_y};

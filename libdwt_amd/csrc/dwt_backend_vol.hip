@@ -150,6 +150,8 @@ int dwt_hip_transform3d_op(const void *src, void *dst, size_t stride_y, size_t s
 		return fail("dwt_hip_transform3d_op takes device pointers");
 	if (src == dst)
 		return fail("dwt_hip_transform3d_op is out of place; use dwt_hip_transform3d for in-place volumes");
+	if (check_dev_align({src, dst}, {}))
+		return 1;
 	if ((stride_y & 3) || (stride_z & 3) || stride_y < (size_t)nx * 4 || stride_z < stride_y * (size_t)ny)
 		return fail("bad volume strides");
 	if (levels > kMaxVolLevels)
@@ -166,6 +168,8 @@ int dwt_hip_transform3d(int inverse, void *vol, size_t stride_y, size_t stride_z
 		return 1;
 	if (!vol || !dwt_hip_is_device_pointer(vol))
 		return fail("dwt_hip_transform3d takes a device pointer");
+	if (check_dev_align({vol}, {}))
+		return 1;
 	if ((stride_y & 3) || (stride_z & 3) || stride_y < (size_t)nx * 4 || stride_z < stride_y * (size_t)ny)
 		return fail("bad volume strides");
 	if (levels < 1)
@@ -353,6 +357,8 @@ static int vol_check(const void *p, size_t sy, size_t sz, int nx, int ny, int nz
 		return fail("%s: bad volume strides", who);
 	if (dwt_hip_is_device_pointer(p) && ((sy & 3) || (sz & 3)))
 		return fail("%s: device volumes need strides that are multiples of 4 bytes", who);
+	if (dwt_hip_is_device_pointer(p) && check_dev_align({p}, {}))
+		return 1;
 	return 0;
 }
 

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 from conftest import bits, golden_cases
+from hipdev import Dev
 
 pytestmark = pytest.mark.gpu
 
@@ -544,4 +545,21 @@ def test_volume_entry_errors(dwt):
     assert L.dwt_hip_volume_ip(0, d.ptr, sy + 2, (sy + 2) * 10, 12, 10, 9) != 0  # device strides must be whole samples
     assert "multiples of 4" in dwt.last_error()
     d.free()
+    # a device volume 2 bytes off a sample boundary: every entry refuses it with a message, and no byte of it changes
+    # (the frame lies 2 bytes into an allocation with room behind it, so that the refused call stays inside it)
+    raw = np.random.default_rng(4).integers(0, 256, size=v.nbytes + 64, dtype=np.uint8)
+    d = Dev(dwt, raw)
+    o = Dev(dwt, raw)
+    for call in (lambda: L.dwt_hip_transform3d(0, d.ptr + 2, sy, sz, 12, 10, 9, 1),
+                 lambda: L.dwt_hip_transform3d(1, d.ptr + 2, sy, sz, 12, 10, 9, 1),
+                 lambda: L.dwt_hip_transform3d_op(d.ptr + 2, o.ptr, sy, sz, 12, 10, 9, 1),
+                 lambda: L.dwt_hip_transform3d_op(d.ptr, o.ptr + 2, sy, sz, 12, 10, 9, 1),
+                 lambda: L.dwt_hip_volume_ip(0, d.ptr + 2, sy, sz, 12, 10, 9),
+                 lambda: L.dwt_hip_volume_fwd_op(d.ptr + 2, sy, sz, o.ptr, sy, sz, 12, 10, 9, 7),
+                 lambda: L.dwt_hip_volume_fwd_op(d.ptr, sy, sz, o.ptr + 2, sy, sz, 12, 10, 9, 7)):
+        assert call() != 0
+        assert "multiples of 4 bytes" in dwt.last_error()
+    assert np.array_equal(d.get(), raw) and np.array_equal(o.get(), raw)
+    d.free()
+    o.free()
     assert np.array_equal(v, keep) and not out.any()
