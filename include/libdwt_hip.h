@@ -1057,6 +1057,95 @@ int dwt_hip_sparse_unpack_batch(int type, const unsigned *pos, const void *val, 
 	size_t counts_stride, void *planes, size_t batch_stride, size_t row_pitch, int batch, int size_x, int size_y);
 int dwt_hip_sparse_route(int type, const void *planes, size_t batch_stride, size_t row_pitch, int batch, int size_x, int size_y);
 
+/* Embedded bit-plane streams of code-blocks: the code-blocks of index planes packed on the device into a
+ * sign plane and as many magnitude planes as the block's largest magnitude has bits, and unpacked again, with the least
+ * significant planes left out on request.  Where 5 % to 100 % of the indices are nonzero -- every visually useful step --
+ * the sparse streams cost more than the planes themselves; a block whose largest magnitude has p bits needs p + 1 bits a
+ * sample, a block of zeros nothing.  An extension: the reference has nothing of the kind; this comment is the
+ * specification (tests/bitplane_model.py restates it in numpy, the device is held to it bit for bit -- there is no
+ * arithmetic and no tolerance).
+ *
+ * Frames.  `batch` index planes of size_x x size_y elements of `index_type` (DWT_HIP_INDEX_I16, _I32), element (x, y) of
+ * frame b at index + b*batch_stride + y*row_pitch + x*(element size) bytes: the addressing of the quantizer's index side,
+ * base and strides multiples of the element size.
+ *
+ * Blocks.  The code-blocks of dwt_hip_codeblock_layout(size_x, size_y, j_max, cb_log2_x, cb_log2_y, ...): each exponent
+ * 2 .. 10, their sum at most 12, so that a block holds at most 4096 samples.  Blocks are enumerated in STREAM ORDER: the
+ * bands in the order of dwt_hip_sparse_order (LL, then HL, LH, HH of level J, ... down to level 1), inside a band the
+ * blocks in raster order.  S is the number of blocks of a frame.  A block of cw x ch samples (partial blocks at the right
+ * and at the bottom keep their own width) has n = cw*ch samples; sample i is the one at column i % cw, row i / cw of the
+ * block; G = ceil(n / 64).
+ *
+ * A block's words.  p is the bit length (0 .. 32) of the block's largest |q| -- the value
+ * dwt_hip_codeblock_bitplanes_batch stores; INT16_MIN gives 16, INT32_MIN 32.  p == 0: no words.  Otherwise the block
+ * holds (p + 1)*G 64-bit words (uint64_t, native byte order), plane-major: plane 0 is the sign plane (bit set where
+ * q < 0), plane k = 1 .. p is bit p - k of |q|, most significant first.  Inside a plane word g holds samples 64g .. 64g +
+ * 63, sample 64g + i in bit i (bit 0 the least significant); bits past sample n - 1 are 0.
+ * The stream is EMBEDDED: a prefix of a block's planes is the same block at a coarser step, a prefix of the blocks in
+ * stream order a coarser picture.
+ *
+ * A frame's stream.  Frame b's words start at words + b*stream_stride (counted in words), the blocks in stream order
+ * without gaps.  Offsets: uint32, S + 1 per frame, frame b's at offsets + b*(S + 1): off[s] the number of words in front
+ * of block s, off[S] the frame's total -- always the true sizes, whatever the capacity.  p is not stored:
+ * (off[s+1] - off[s]) / G - 1 is p.
+ * Capacity.  Block s is written only if off[s+1] <= stream_stride; later blocks are not written, and the words behind the
+ * last written block are left alone.  That is no error: a call on device memory does not wait for the device.
+ *
+ * dwt_hip_bitplane_pack_batch.  words == NULL (stream_stride ignored): count only, the sizing call.  `index` is only read.
+ * dwt_hip_bitplane_unpack_batch writes EVERY own element of every frame and nothing else.  drop in 0 .. 32: the
+ * min(drop, p) least significant magnitude planes of every block are not read.  With m = |q| >> min(drop, p) taken from
+ * the planes that are read, mode DWT_HIP_BITPLANE_KEEP stores the magnitude m << min(drop, p) (the element keeps its
+ * step), DWT_HIP_BITPLANE_SHIFT stores m (the caller dequantizes with steps * 2^drop and r = 0.5, the midpoint of the
+ * coarser cell).  A magnitude of 0 stores 0 whatever the sign bit; otherwise the sign plane negates the magnitude.  The
+ * value is stored truncated to the element type: INT16_MIN and INT32_MIN come back, a foreign stream's oversized magnitude
+ * wraps.
+ * Foreign and cut streams.  Unpack never reads a word outside [frame base, frame base + stream_stride) and never an
+ * offset outside the frame's S + 1.  A block is written as zeros when off[s+1] < off[s], when off[s+1] > stream_stride,
+ * when off[s+1] - off[s] is no multiple of G, or when its p exceeds 16 (int16) / 32 (int32).  That is also how a stream
+ * cut by pack's capacity comes back: a prefix of the blocks, zeros for the rest.
+ *
+ * Memory.  Three sides -- the planes, the words, the offsets -- each in host or in device memory on its own.  Device
+ * sides are ordered on the context's stream; with all three on the device no call waits for the device, and after the
+ * first call of a size none allocates.  A host side is mirrored in scratch of the context (a written region is uploaded
+ * first, so that the bytes the call leaves alone come back as they were) and the call ends synchronised.
+ * Kernels.  Pack is THREE launches whatever the batch, the shape and the content: launch 1 reads every block's largest
+ * magnitude (a wave per block; the reading code of dwt_hip_codeblock_bitplanes_batch with its 16-byte route, option
+ * "quant_wide") and stores the block's size, launch 2 -- one workgroup per frame -- turns the sizes into the offsets,
+ * launch 3 -- a workgroup per block, DWT_HIP_BITPLANE_GRID_BLOCKS of them per trip of its loop -- reads the block again, a
+ * wave per group of 64 samples, builds each plane's word by one 64-bit ballot, assembles the words in LDS and stores them
+ * as one run.  Count only is launches 1 and 2.  Unpack is ONE launch: the planes that are read go contiguously into LDS
+ * (dropped planes cost no bytes) and every element of every block is written, by 16-byte runs of a row where the planes'
+ * base, row pitch and batch stride and the block's first column are multiples of 16 bytes, element by element elsewhere;
+ * same bytes.  No atomics, no workgroup waits for another.
+ * Option "bitplane_wave" = 0: launch 3 and unpack take a plain route, one lane per word touching its 64 samples itself --
+ * same bytes, the on-device cross-check.  dwt_hip_bitplane_route: 1 where a call with these arguments runs the wave
+ * kernels, 0 for the cross-check route, -1 for arguments the entries refuse.
+ * batch == 0 launches nothing and writes nothing; frames without elements launch nothing, their offsets are written as
+ * zeros.
+ * Errors (nonzero, dwt_hip_last_error, nothing launched, nothing written): a null pointer other than `words` of the
+ * count-only call, an unknown type or mode, drop outside 0 .. 32, bad exponents, negative sizes, size_x*size_y > INT_MAX, a
+ * pitch below its row, frames closer than they span, addresses or strides that are no multiple of the element size (8 for
+ * words, 4 for offsets), regions that share a byte.
+ *
+ * Host geometry (no device).  dwt_hip_bitplane_bands: {x, y, size_x, size_y, first stream block} of every band in stream
+ * order -> table, five ints per band, and one more row {0, 0, 0, 0, S}; 5 * (3J + 2) ints in all.  Returns 3J + 1, -1 for
+ * arguments the entries refuse.  dwt_hip_bitplane_block: stream block s of that table -> its rectangle in frame
+ * coordinates; 0, or -1 for a block the table does not hold.  dwt_hip_bitplane_words: the size rule, (p + 1) * ceil(n / 64)
+ * words for p > 0, 0 for p == 0; -1 for n outside 1 .. 4096 or p outside 0 .. 32. */
+#define DWT_HIP_BITPLANE_KEEP 0
+#define DWT_HIP_BITPLANE_SHIFT 1
+#define DWT_HIP_BITPLANE_GRID_BLOCKS 16384 /* code-blocks one trip of the pack / unpack kernels' loops covers */
+#define DWT_HIP_BITPLANE_GRID_BATCH 4096 /* frames one trip of the scan's loop covers */
+int dwt_hip_bitplane_bands(int size_x, int size_y, int j_max, int cb_log2_x, int cb_log2_y, int *table);
+int dwt_hip_bitplane_block(const int *table, int bands, int cb_log2_x, int cb_log2_y, int s, int *x, int *y, int *w, int *h);
+int dwt_hip_bitplane_words(int n, int p);
+int dwt_hip_bitplane_pack_batch(int index_type, const void *index, size_t batch_stride, size_t row_pitch, int batch, int size_x,
+	int size_y, int j_max, int cb_log2_x, int cb_log2_y, uint64_t *words, size_t stream_stride, unsigned *offsets);
+int dwt_hip_bitplane_unpack_batch(int index_type, const uint64_t *words, size_t stream_stride, const unsigned *offsets, void *index,
+	size_t batch_stride, size_t row_pitch, int batch, int size_x, int size_y, int j_max, int cb_log2_x, int cb_log2_y, int drop, int mode);
+int dwt_hip_bitplane_route(int index_type, const void *index, size_t batch_stride, size_t row_pitch, int batch, int size_x, int size_y,
+	int j_max, int cb_log2_x, int cb_log2_y);
+
 /* User-defined lifting wavelets: a multi-level Mallat transform of a batch of dense frames by a lifting
  * scheme that the CALLER describes in a small table -- Haar, Daubechies D4, 13/7, 2/6, the S transform, a filter of one's
  * own --, binary32 or reversible int32.  An extension: the reference has Haar and D4 as cores only (examples/cores/

@@ -18,7 +18,7 @@ struct Opt {
 };
 #define DWT_OPT(name_, member_, kind_) {name_, [](Ctx &c) -> int * { return &c.member_; }, kind_}
 const Opt kOpts[] = {
-	DWT_OPT("generic", force_generic, kSweep), DWT_OPT("eaw_two_pass", eaw_two_pass, kBool), DWT_OPT("feat_groups", feat_groups, kNonNegative), DWT_OPT("swt_fused", swt_fused, kBool), DWT_OPT("swt2d_fused", swt2d_fused, kBool), DWT_OPT("wp_fused", wp_fused, kBool), DWT_OPT("pixels_wide", pixels_wide, kBool), DWT_OPT("quant_wide", quant_wide, kBool), DWT_OPT("sparse_wide", sparse_wide, kBool), DWT_OPT("lifting_fused", lifting_fused, kBool), DWT_OPT("window_fused", window_fused, kNonNegative), DWT_OPT("cond_fused", cond_fused, kPlain), DWT_OPT("timefreq_tiled", tf_tiled, kBool), DWT_OPT("cpt", tune.cpt, kSweep), DWT_OPT("tile_pairs", tune.tile_pairs, kSweep),
+	DWT_OPT("generic", force_generic, kSweep), DWT_OPT("eaw_two_pass", eaw_two_pass, kBool), DWT_OPT("feat_groups", feat_groups, kNonNegative), DWT_OPT("swt_fused", swt_fused, kBool), DWT_OPT("swt2d_fused", swt2d_fused, kBool), DWT_OPT("wp_fused", wp_fused, kBool), DWT_OPT("pixels_wide", pixels_wide, kBool), DWT_OPT("quant_wide", quant_wide, kBool), DWT_OPT("sparse_wide", sparse_wide, kBool), DWT_OPT("bitplane_wave", bitplane_wave, kBool), DWT_OPT("lifting_fused", lifting_fused, kBool), DWT_OPT("window_fused", window_fused, kNonNegative), DWT_OPT("cond_fused", cond_fused, kPlain), DWT_OPT("timefreq_tiled", tf_tiled, kBool), DWT_OPT("cpt", tune.cpt, kSweep), DWT_OPT("tile_pairs", tune.tile_pairs, kSweep),
 	DWT_OPT("waves", tune.waves, kSweep), DWT_OPT("xcd_swizzle", tune.xcd_swizzle, kSweep), DWT_OPT("ring", tune.ring, kSweep),
 	DWT_OPT("ring_inv", tune.ring_inv, kSweep), DWT_OPT("inv_ll_temporal", tune.inv_ll_temporal, kSweep), DWT_OPT("inv_pairs", tune.inv_pairs, kSweep), DWT_OPT("nt", tune.nt, kSweep), DWT_OPT("nt_auto", tune.nt_auto, kSweep),
 	DWT_OPT("fma", fma, kSweep), DWT_OPT("fused_d", fused_d, kPlain), DWT_OPT("fuse01", fuse01, kPlain), DWT_OPT("fuse_deep", fuse_deep, kNonNegative), DWT_OPT("fuse01_ring", tune.fuse01_ring, kRing01), DWT_OPT("fuse01_updown", tune.fuse01_updown, kUpDown01), DWT_OPT("ride_copy", ride_copy, kBool), DWT_OPT("ride_mib", ride_mib, kNonNegative), DWT_OPT("il_exact_borders", il_exact_borders, kPlain),

@@ -61,11 +61,12 @@ struct Ctx {
 	Buf win_ws; // windows of the inverse: the cross-check route's full result, the window kernels' regions between the levels (dwt_backend_window.hip)
 	Buf q_coef, q_index, q_planes, q_ws; // quantization: the device mirrors of a host call's coefficients, indices and bit-plane maps; the step tables and the band counters (dwt_backend_quant.hip)
 	Buf sp_planes, sp_pos, sp_val, sp_ws; // sparse streams: the device mirrors of a host call's planes, positions and values; the tiles' counts and the mirror of host offsets / counts (dwt_backend_sparse.hip)
+	Buf bp_planes, bp_words, bp_off, bp_ws; // bit-plane streams: the device mirrors of a host call's planes, words and offsets; the blocks' sizes (dwt_backend_bitplane.hip)
 	Buf lift_ll[2]; // user-defined lifting wavelets: the LL ping-pong of the fused levels (dwt_backend_lifting.hip)
 	// every device scratch buffer above: a new one is declared there, listed here, and named nowhere else for freeing
 	auto bufs()
 	{
-		return std::array{&stage_img, &ll[0], &ll[1], &frame_a, &frame_b, &vol_out, &vol_host[0], &vol_host[1], &eaw_w, &eaw_ll[0], &eaw_ll[1], &feat_ws, &swt_ws, &cond_ws, &band_ws, &nterm_ws, &half_f32, &px_pix, &px_planes, &px_tmp, &wp_ws, &q_coef, &q_index, &q_planes, &q_ws, &win_ws, &sp_planes, &sp_pos, &sp_val, &sp_ws, &lift_ll[0], &lift_ll[1]};
+		return std::array{&stage_img, &ll[0], &ll[1], &frame_a, &frame_b, &vol_out, &vol_host[0], &vol_host[1], &eaw_w, &eaw_ll[0], &eaw_ll[1], &feat_ws, &swt_ws, &cond_ws, &band_ws, &nterm_ws, &half_f32, &px_pix, &px_planes, &px_tmp, &wp_ws, &q_coef, &q_index, &q_planes, &q_ws, &win_ws, &sp_planes, &sp_pos, &sp_val, &sp_ws, &bp_planes, &bp_words, &bp_off, &bp_ws, &lift_ll[0], &lift_ll[1]};
 	}
 	hipEvent_t dl_ev[8] = {}; // strip events of the host downloads (dwt_host_xfer.hip), created once
 	hipEvent_t switch_ev = nullptr; // dwt_hip_set_stream: orders a newly set stream behind the old one's work
@@ -83,6 +84,7 @@ struct Ctx {
 	int pixels_wide = 1; // pixel front end: aligned sides move by 16-byte accesses (0: element by element everywhere, the cross-check)
 	int quant_wide = 1; // quantization: aligned sides move by 16-byte accesses (0: element by element everywhere, the cross-check)
 	int sparse_wide = 1; // sparse streams: aligned planes move by 16-byte accesses (0: element by element everywhere, the cross-check)
+	int bitplane_wave = 1; // bit-plane streams: the ballot / LDS kernels (0: one lane per word, the cross-check)
 	int lifting_fused = 1; // user-defined lifting wavelets: schemes of reach <= 8 one tile launch per level (0: one launch per step and direction on a dense copy, the cross-check)
 	int window_fused = 1; // windows of the inverse: 2 the window kernels wherever they can run, 0 the inverse driver into scratch and a rectangle copy (the cross-check), 1 the kernels where they were measured to win
 	int swt_fused = 1; // SWT lines of up to N1D_MAX samples in one launch (0: one launch per level, the cross-check)

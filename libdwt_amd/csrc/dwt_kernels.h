@@ -677,6 +677,35 @@ struct SparseUnpackArgs {
 hipError_t launch_sparse_zero(int es, const SparseUnpackArgs &a, hipStream_t s);
 hipError_t launch_sparse_scatter(int es, const SparseUnpackArgs &a, hipStream_t s);
 
+// Embedded bit-plane streams of code-blocks (dwt_bitplane.hip): every code-block of an index frame as a
+// sign plane and its magnitude planes, most significant first, in 64-bit words of 64 samples.  Sample (x, y) of frame b at
+// index + b*bs + y*pitch + x*es bytes.  The bands ride in the kernel arguments in STREAM order (dwt_bitplane_geom.c), with
+// the prefix of their block counts.
+constexpr int BITPLANE_WG_BLOCKS = 4;      // launch 1: code-blocks per workgroup, one per wave
+constexpr int BITPLANE_GRID_BLOCKS = 16384; // blocks one trip of the pack / unpack kernels' loops covers (one per workgroup); launch 1: workgroups
+constexpr int BITPLANE_GRID_BATCH = 4096;  // frames one trip of the scan's loop covers
+constexpr int BITPLANE_MAX_WORDS = 33 * 64; // of one block: 33 planes of 4096 samples
+enum BitplaneMode { kBitplaneKeep = 0, kBitplaneShift = 1 }; // (DWT_HIP_BITPLANE_*)
+struct BitplaneArgs {
+	char *index;
+	long pitch, bs;
+	int batch, bands, blocks; // 3J + 1 bands in stream order; blocks of one frame
+	int cbx, cby;
+	int wide; // launch 1, unpack: base, pitch and batch stride are multiples of 16 bytes (16-byte reads of launch 1, 16-byte stores of unpack)
+	int x0[BAND_MAX_SLOTS], y0[BAND_MAX_SLOTS], w[BAND_MAX_SLOTS], h[BAND_MAX_SLOTS];
+	int first[BAND_MAX_SLOTS + 1]; // prefix of the bands' block counts
+	int blocks_x[BAND_MAX_SLOTS];
+	unsigned *sizes;   // [batch][blocks]: the blocks' sizes in words (launch 1 -> launch 2)
+	unsigned *offsets; // [batch][blocks + 1]
+	unsigned long long *words; // frame b's from b * stream_stride on
+	unsigned long long stream_stride;
+	int drop, mode, nt; // unpack: planes left out, KEEP / SHIFT, non-temporal stores
+};
+hipError_t launch_bitplane_sizes(int index, const BitplaneArgs &a, hipStream_t s);             // launch 1
+hipError_t launch_bitplane_scan(const BitplaneArgs &a, hipStream_t s);                         // launch 2
+hipError_t launch_bitplane_pack(int index, bool wave, const BitplaneArgs &a, hipStream_t s);   // launch 3
+hipError_t launch_bitplane_unpack(int index, bool wave, const BitplaneArgs &a, hipStream_t s);
+
 // User-defined lifting wavelets (dwt_lifting.hip): the caller's scheme as the kernels take it, by value in
 // the kernel arguments (wave-uniform).  Samples are 4-byte words (binary32 or int32); pitches and batch strides below are
 // in ELEMENTS.

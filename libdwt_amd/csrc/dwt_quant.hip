@@ -17,8 +17,10 @@
 //
 // k_codeblock_bitplanes.  A wave owns a code-block: its lanes walk the block's rows -- by whole 16-byte chunks where the
 // frames' rows are 16-byte aligned, the elements outside the block left out; element by element elsewhere --, reduce the
-// largest magnitude across the wave and one lane stores the byte.  The index planes are read once.
+// largest magnitude across the wave and one lane stores the byte.  The index planes are read once.  (The reading code is
+// dwt_codeblock_read.h, shared with the size launch of dwt_bitplane.hip.)
 #include "dwt_device.h"
+#include "dwt_codeblock_read.h"
 #include "dwt_runs.h"
 
 #include <algorithm>
@@ -244,55 +246,11 @@ __global__ __launch_bounds__(256) void k_codeblock_bitplanes(CodeblockArgs a)
 	for (long g = (long)blockIdx.x * CODEBLOCK_WG_BLOCKS + wave; g < total; g += (long)gridDim.x * CODEBLOCK_WG_BLOCKS) {
 		const long b = g / per;
 		const int t = (int)(g % per);
-		// the last slot whose first block is not behind t (slots without blocks share their successor's first)
-		int lo = 0, hi = a.nslots - 1;
-		while (lo < hi) {
-			const int mid = (lo + hi + 1) >> 1;
-			if (a.first[mid] <= t)
-				lo = mid;
-			else
-				hi = mid - 1;
-		}
-		const int k = lo, ls = t - a.first[k], bx = ls % a.blocks_x[k], by = ls / a.blocks_x[k];
+		const int k = codeblock_band(a.first, a.nslots, t), ls = t - a.first[k], bx = ls % a.blocks_x[k], by = ls / a.blocks_x[k];
 		const int bx0 = bx << a.cbx, by0 = by << a.cby;
 		const int cw = min(1 << a.cbx, a.w[k] - bx0), ch = min(1 << a.cby, a.h[k] - by0);
 		const char *const p = a.index + b * a.index_bs + (long)(a.y0[k] + by0) * a.index_pitch + (long)(a.x0[k] + bx0) * ES;
-		unsigned mx = 0;
-		if (a.wide) {
-			// Rows start on 16-byte boundaries and span a multiple of 16 bytes (the driver asked base, pitch and batch stride):
-			// the block's bytes of a row, widened to whole 16-byte chunks, stay inside the row's span.  A lane takes a chunk
-			// and leaves out the elements in front of and behind the block.
-			const long lead = ((long)(a.x0[k] + bx0) * ES) & 15; // the block's first byte within its chunk
-			const int chunks = (int)((lead + (long)cw * ES + 15) >> 4);
-			const int span = cw * ES;
-			for (int i = lane; i < ch * chunks; i += 64) {
-				const int y = i / chunks, c = i - y * chunks;
-				const long off = ((long)c << 4) - lead; // of the chunk's first byte from the block's first byte of the row
-				const u4 t = __builtin_nontemporal_load((const u4 *)(p + (long)y * a.index_pitch + off));
-				const unsigned raw[4] = {t.x, t.y, t.z, t.w};
-#pragma unroll
-				for (int e = 0; e < 16 / ES; e++) {
-					const long at = off + e * ES;
-					const int q = INDEX == kIndexI16 ? (int)(short)run_get<ES>(raw, e) : (int)raw[e];
-					const unsigned mag = q < 0 ? 0u - (unsigned)q : (unsigned)q;
-					mx = at >= 0 && at < span ? max(mx, mag) : mx;
-				}
-			}
-		} else {
-			const int cells = ch << a.cbx; // the rows of the block at its full width: a cell past a partial block's edge is skipped
-#pragma unroll 4
-			for (int i = lane; i < cells; i += 64) {
-				const int x = i & ((1 << a.cbx) - 1), y = i >> a.cbx;
-				if (x < cw) {
-					const unsigned bits = elem_load<ES>(p + (long)y * a.index_pitch + (long)x * ES);
-					const int q = INDEX == kIndexI16 ? (int)(short)bits : (int)bits;
-					mx = max(mx, q < 0 ? 0u - (unsigned)q : (unsigned)q);
-				}
-			}
-		}
-#pragma unroll
-		for (int o = 32; o; o >>= 1)
-			mx = max(mx, __shfl_xor(mx, o));
+		const unsigned mx = codeblock_max_magnitude<INDEX>(p, a.index_pitch, (long)(a.x0[k] + bx0) * ES, cw, ch, a.cbx, a.wide, lane);
 		if (lane == 0)
 			a.planes[b * a.planes_bs + t] = (unsigned char)(mx ? 32 - __clz(mx) : 0);
 	}
